@@ -12,8 +12,13 @@ the first one overlapped with the rest of the backward pass).  No optimizer, no 
 (SURVEY.md §8d).  Rank 0 prints ONE JSON line.
 
 N = 1 times BASELINE.json configs[2] (CISTGCN-64, B=256, 50->25 frames, 22 joints: the largest
-single-GPU configuration and the one the %HBM metric is quoted on) as the headline and configs[1]
-(CISTGCN-8, B=16) under "secondary"; both carry a CPU baseline timed on this box's host cores.
+single-GPU configuration and the one the %HBM metric is quoted on) as the headline.  A plain run does
+only that: set up, warm up, time --steps steps, print the line.  --full adds, at N = 1, the eval-mode
+forward, the block / family rooflines, configs[1] (CISTGCN-8, B=16) under "secondary" and the
+configs[4] shape, the CPU baselines timed on this box's host cores and the data-parallel overhead.
+
+--dump-outputs DIR writes what the last timed step computed (loss, gradients, BatchNorm running
+statistics) as DIR/*.npy; with the same arguments the inputs are the same from run to run.
 """
 import argparse
 import ctypes
@@ -473,9 +478,26 @@ def dp_overhead(net, device, reps=20):
 
 
 # ---------------------------------------------------------------------------------------------------------------------
-def timed_training(workload, args, device, rank, world, steps, warmup, batch=None):
+def dump_outputs(out_dir, step, net, world):
+    """What the last timed step handed its caller, as float32 .npy files: the loss, the gradient of every trainable
+    parameter (in net.parameters() order, flattened and concatenated; for N > 1 the averaged flat buffer) and the
+    BatchNorm running statistics the step updated.  About 8 MB at C = 64."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    torch.cuda.synchronize()
+    if world > 1:
+        grads = step.flat.flat
+    else:
+        grads = torch.cat([p.grad.reshape(-1) for p in net.parameters() if p.requires_grad])
+    stats = torch.cat([b.reshape(-1) for b in net.buffers() if b.is_floating_point()])
+    for name, t in (("loss", step.loss), ("param_grads", grads), ("bn_running_stats", stats)):
+        np.save(os.path.join(out_dir, name + ".npy"), t.detach().float().cpu().numpy())
+
+
+def timed_training(workload, args, device, rank, world, steps, warmup, batch=None, dump_dir=None):
     """Builds the model and the captured step for `workload`, runs `warmup` untimed and exactly `steps` timed steps
-    bracketed by barrier + synchronize; returns (result dict, net, x, tgt) - the step object is released."""
+    bracketed by barrier + synchronize; returns (result dict, net, x, tgt) - the step object is released.  `dump_dir`:
+    rank 0 writes the outputs of the last timed step there (dump_outputs)."""
     import torch.distributed as dist
     from cistgcn_amd import ops
     from cistgcn_amd.models import CISTGCN_0
@@ -525,6 +547,8 @@ def timed_training(workload, args, device, rank, world, steps, warmup, batch=Non
         per = [None] * world
         dist.all_gather_object(per, {"rank": rank, "batch": B, "shard_weight": getattr(step, "weight", None)})
         res["per_rank"] = per
+    if dump_dir and rank == 0:
+        dump_outputs(dump_dir, step, net, world)
     del step
     for p in net.parameters():
         p.grad = None
@@ -578,11 +602,16 @@ def main():
     ap.add_argument("--no-graph", action="store_true", help="eager launches instead of HIP-graph replay")
     ap.add_argument("--branches", action="store_true", help="(default at N = 1) capture independent branches - the ContextLayer beside the output block - on forked streams")
     ap.add_argument("--no-branches", action="store_true", help="capture the step on one stream")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
-    ap.add_argument("--no-eval", action="store_true", help="skip the eval-mode forward-only timing")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the configs[1] (CISTGCN-8, B=16) and configs[4]-shape lines")
-    ap.add_argument("--no-dp-overhead", action="store_true", help="skip the one-GPU timing of gather + one-rank RCCL all-reduce + scale")
+    ap.add_argument("--full", action="store_true",
+                    help="N=1: after the headline, also the eval forward, rooflines, CPU baselines, secondary workloads and the "
+                         "data-parallel overhead (each can be left out with its --no-* option)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the loss, parameter gradients and BatchNorm running statistics of the last timed step as DIR/*.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baselines")
+    ap.add_argument("--no-roofline", action="store_true", help="--full: skip the block / family rooflines")
+    ap.add_argument("--no-eval", action="store_true", help="--full: skip the eval-mode forward-only timing")
+    ap.add_argument("--no-secondary", action="store_true", help="--full: skip the configs[1] (CISTGCN-8, B=16) and configs[4]-shape lines")
+    ap.add_argument("--no-dp-overhead", action="store_true", help="--full: skip the one-GPU timing of gather + one-rank RCCL all-reduce + scale")
     ap.add_argument("--capture-tries", type=int, default=3,
                     help="graphs captured before the run; the MEDIAN one is kept (buffer placement moves the step by +-3 %%)")
     ap.add_argument("--data-seed", type=int, default=1234, help="base seed of the synthetic batch (rank is added)")
@@ -617,7 +646,7 @@ def main():
 
     C, B, T, V = WORKLOADS[args.workload]
     batch = MIXED_BATCHES[rank % len(MIXED_BATCHES)] if (args.mixed_batches and world > 1) else None
-    res, net, x, tgt = timed_training(args.workload, args, device, rank, world, args.steps, args.warmup, batch)
+    res, net, x, tgt = timed_training(args.workload, args, device, rank, world, args.steps, args.warmup, batch, args.dump_outputs)
     out = {
         "metric": "sequences/sec (fwd+bwd) H3.6M 22-joint 50->25" if (T, V) == (50, 22) else "sequences/sec (fwd+bwd)",
         "value": res["value"], "unit": "sequences/sec", "n_gpus": world, "steps": args.steps,
@@ -634,6 +663,7 @@ def main():
     }
     if rank == 0 and world == 1:
         out["step_roofline"] = step_roofline(C, T, V, out["value"])
+    if rank == 0 and world == 1 and args.full:
         if not args.no_eval:
             out["eval_forward"] = eval_forward(net, x, args.steps, args.warmup)
         if not args.no_roofline:

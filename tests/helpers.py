@@ -8,7 +8,8 @@ import torch
 
 GOLDEN_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 # model fixtures (tools/gen_golden.py); eval_*.npz belong to the evaluation-harness counterpart (tools/gen_golden_eval.py)
-CASES = sorted(n for n in (os.path.splitext(os.path.basename(p))[0] for p in glob.glob(os.path.join(GOLDEN_DIR, "*.npz"))) if not n.startswith(("eval_", "aug_")))
+# (a model fixture is stored as <case>.part0.npz, <case>.part1.npz, ...: tools/gen_golden.save_case keeps each file under 1 MiB)
+CASES = sorted({n for n in (os.path.basename(p).split(".")[0] for p in glob.glob(os.path.join(GOLDEN_DIR, "*.npz"))) if not n.startswith(("eval_", "aug_"))})
 
 
 def make_cfg(C, T, V, dropout=0.0, To=25, hidden=64, interp=None, interp_o=(True,), blocks=4, txc=4):
@@ -26,10 +27,24 @@ def make_cfg(C, T, V, dropout=0.0, To=25, hidden=64, interp=None, interp_o=(True
 _cache = {}
 
 
+def case_files(name):
+    """<name>.npz, or the parts <name>.part0.npz, <name>.part1.npz, ... in order"""
+    whole = os.path.join(GOLDEN_DIR, name + ".npz")
+    if os.path.exists(whole):
+        return [whole]
+    parts = glob.glob(os.path.join(GOLDEN_DIR, glob.escape(name) + ".part*.npz"))
+    if not parts:
+        raise FileNotFoundError("no golden fixture %s(.part*).npz under %s" % (name, GOLDEN_DIR))
+    return sorted(parts, key=lambda p: int(p[:-len(".npz")].rsplit(".part", 1)[1]))
+
+
 def load_case(name):
     if name not in _cache:
-        z = np.load(os.path.join(GOLDEN_DIR, name + ".npz"))
-        _cache[name] = {k: z[k] for k in z.files}
+        rec = {}
+        for path in case_files(name):
+            z = np.load(path)
+            rec.update({k: z[k] for k in z.files})
+        _cache[name] = rec
     return _cache[name]
 
 

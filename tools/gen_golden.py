@@ -3,9 +3,10 @@
 
 Runs only in the build container, where the upstream sources are mounted read-only at
 /root/reference.  Nothing of the reference travels: this script imports it, runs it on seeded
-inputs and writes *data* (inputs, weights, outputs, gradients) to tests/golden/*.npz.
+inputs and writes *data* (inputs, weights, outputs, gradients) to tests/golden/<case>.part<k>.npz
+(tests/helpers.load_case merges the parts; each part file stays under 1 MiB).
 
-    python tools/gen_golden.py            # writes tests/golden/*.npz
+    python tools/gen_golden.py            # writes tests/golden/*.part*.npz
 
 The reference package's __init__ pulls in plotting/FLOP-count dependencies that are not in the
 image (fvcore); the model file itself only needs torch, so the package is pre-registered as an
@@ -32,6 +33,28 @@ CASES = {
     "cmu_c8_t50_v25": (8, 50, 25, 4),      # BASELINE.json "25-joint" shape
 }
 FULL_GRADS = {"h36m_c8_t10_v22"}      # these also keep the unit-scale run and the Adj maps of every block
+PART_BYTES = 900 * 1024                # array bytes + a per-array allowance for the zip / .npy headers, per part file
+
+
+def save_case(name, rec, out_dir=OUT_DIR):
+    """Writes `rec` (insertion order kept) as <name>.part0.npz, <name>.part1.npz, ... of at most PART_BYTES each; returns the paths."""
+    import glob
+    for old in glob.glob(os.path.join(out_dir, name + ".part*.npz")) + glob.glob(os.path.join(out_dir, name + ".npz")):
+        os.remove(old)
+    parts, cur, size = [], {}, 0
+    for k, v in rec.items():
+        need = np.asarray(v).nbytes + 400
+        if cur and size + need > PART_BYTES:
+            parts.append(cur)
+            cur, size = {}, 0
+        cur[k] = v
+        size += need
+    parts.append(cur)
+    paths = []
+    for i, part in enumerate(parts):
+        paths.append(os.path.join(out_dir, "%s.part%d.npz" % (name, i)))
+        np.savez_compressed(paths[-1], **part)
+    return paths
 
 
 class BranchRecorder:
@@ -206,10 +229,10 @@ def main():
         for k, v in attrs(net64, blocks_with_adj).items():
             rec["train64/attr/" + k] = v
 
-        path = os.path.join(OUT_DIR, name + ".npz")
-        np.savez_compressed(path, **rec)
-        print("%-22s %4d arrays  %.2f MB  |pred|max %.1f  loss(train) %.3f" % (
-            name, len(rec), os.path.getsize(path) / 1e6, float(np.abs(rec["train/pred"]).max()), float(rec["train/loss"])))
+        paths = save_case(name, rec)
+        print("%-22s %4d arrays  %.2f MB in %d parts  |pred|max %.1f  loss(train) %.3f" % (
+            name, len(rec), sum(os.path.getsize(p) for p in paths) / 1e6, len(paths), float(np.abs(rec["train/pred"]).max()),
+            float(rec["train/loss"])))
 
 
 if __name__ == "__main__":
