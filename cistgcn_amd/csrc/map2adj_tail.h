@@ -21,4 +21,4 @@ struct CgAdjTail {
 };
 // launch geometry of one tower (internal): padded slab count, LDS strides, tile width (KcM * PT = 4096), chunking, magic divisors
 struct CgAdjGeom { int KcM, WS, JS, Pn, PT, PS, NP, lgq, ntiles, nch; unsigned magicJ, magicKc, magicPad; int tpw; };
-struct CgAdjTailPair { int n, nch_max, dbg, pad; CgAdjGeom g[2]; CgAdjTail t[2]; };   // dbg: tuning aid (CG_ADJ_DBG), phases of the backward kernels skipped
+struct CgAdjTailPair { int n, nch_max; CgAdjGeom g[2]; CgAdjTail t[2]; };

@@ -13,7 +13,6 @@
 #include "cg_common.h"
 #include "cg_phase.h"
 #include "map2adj_tail.h"
-#include <cstdlib>
 
 HIP_DYNAMIC_SHARED(unsigned char, cg_dyn_lds)
 
@@ -366,7 +365,7 @@ __global__ __launch_bounds__(CG_ADJ_THREADS, 2) void cg_adj_m2_kernel(CgAdjTailP
 // N1: dh = W4^T dAdj;  g = dh PReLU'(u) keep -> HBM;  red = { sum g, sum g e_hat }, d alpha;  dW4 += dAdj h^T
 // ======================================================================================================================
 template <int KCM, bool VEC>
-__device__ __forceinline__ void cg_adj_n1_body(const CgAdjTail& t, const CgAdjGeom& g, int b, int tile0, int tile1, int dbg) {
+__device__ __forceinline__ void cg_adj_n1_body(const CgAdjTail& t, const CgAdjGeom& g, int b, int tile0, int tile1) {
   using K = CgAdjK<KCM>;
   float* sE = reinterpret_cast<float*>(cg_dyn_lds);              // [KcM][PS] e_hat
   float* sP = sE + K::KcM * K::PS;                             // [KcM][PS] dropout keep factors
@@ -407,7 +406,6 @@ __device__ __forceinline__ void cg_adj_n1_body(const CgAdjTail& t, const CgAdjGe
     for (int h = 0; h < NS; ++h) wacc[u][h] = cg_f32x4{0.f, 0.f, 0.f, 0.f};
   float* gb = t.g + (long long)b * Kc * Pn;
   float racc[2][2] = {{0.f, 0.f}, {0.f, 0.f}}, sa = 0.f;   // per lane: sums of g and g e_hat (one channel per dh task), d alpha
-  if (dbg & 64) tile1 = tile0;
   for (int tile = tile0; tile < tile1; ++tile) {
     const int p0 = tile * K::PT, np = min(K::PT, Pn - p0);
     __syncthreads();
@@ -422,13 +420,13 @@ __device__ __forceinline__ void cg_adj_n1_body(const CgAdjTail& t, const CgAdjGe
       cg_adj_put<KCM, VEC>(sD, c, pp, d);
     });
     __syncthreads();
-    if (tile + 1 < tile1 && !(dbg & 8)) {
+    if (tile + 1 < tile1) {
       const int q0 = p0 + K::PT, nq = min(K::PT, Pn - q0);
       cg_adj_fetch<KCM, VEC>(eb, Kc, Pn, q0, nq, ebuf);
       cg_adj_fetch<KCM, VEC>(db, Kc, Pn, q0, nq, dbuf);
     }
     // dW4[u'][u] += sum_p dAdj[u'][p] h[u][p],  h rebuilt from e_hat and the keep factors in the B fragments (lane = channel u)
-    if (!(dbg & 1) && (MT * MT >= nw || wave < MT * MT)) {       // 1 tile (wave 0), 4 tiles (one per wave) or 16 (four per wave)
+    if (MT * MT >= nw || wave < MT * MT) {       // 1 tile (wave 0), 4 tiles (one per wave) or 16 (four per wave)
 #pragma unroll
       for (int k0 = 0; k0 < K::PT; k0 += 16) {
 #pragma unroll
@@ -456,27 +454,24 @@ __device__ __forceinline__ void cg_adj_n1_body(const CgAdjTail& t, const CgAdjGe
     cg_f32x4 dacc[2][2];
 #pragma unroll
     for (int ti = 0; ti < 2; ++ti) dacc[ti][0] = dacc[ti][1] = cg_f32x4{0.f, 0.f, 0.f, 0.f};
-    if (!(dbg & 2)) {
 #pragma unroll
-      for (int k0 = 0; k0 < K::KcM; k0 += 16) {
+    for (int k0 = 0; k0 < K::KcM; k0 += 16) {
 #pragma unroll
-        for (int ti = 0; ti < 2; ++ti) {
-          const int w = wave + nw * ti, mt = w / K::NP, n0 = 32 * (w - mt * K::NP), n1 = n0 + 16;
-          float av[4], b0v[4], b1v[4];
-          cg_tfrag<1>(cg_tfrag_ptr<1>(sW + 16 * mt, K::WS, l15, slot), K::WS, k0, av);
-          cg_tfrag<1>(cg_tfrag_ptr<1>(sD + n0, K::PS, l15, slot), K::PS, k0, b0v);
-          cg_tfrag<1>(cg_tfrag_ptr<1>(sD + n1, K::PS, l15, slot), K::PS, k0, b1v);
+      for (int ti = 0; ti < 2; ++ti) {
+        const int w = wave + nw * ti, mt = w / K::NP, n0 = 32 * (w - mt * K::NP), n1 = n0 + 16;
+        float av[4], b0v[4], b1v[4];
+        cg_tfrag<1>(cg_tfrag_ptr<1>(sW + 16 * mt, K::WS, l15, slot), K::WS, k0, av);
+        cg_tfrag<1>(cg_tfrag_ptr<1>(sD + n0, K::PS, l15, slot), K::PS, k0, b0v);
+        cg_tfrag<1>(cg_tfrag_ptr<1>(sD + n1, K::PS, l15, slot), K::PS, k0, b1v);
 #pragma unroll
-          for (int s = 0; s < 4; ++s) {                     // C[position][channel]: four consecutive positions per lane
-            dacc[ti][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(b0v[s], av[s], dacc[ti][0], 0, 0, 0);
-            dacc[ti][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(b1v[s], av[s], dacc[ti][1], 0, 0, 0);
-          }
+        for (int s = 0; s < 4; ++s) {                     // C[position][channel]: four consecutive positions per lane
+          dacc[ti][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(b0v[s], av[s], dacc[ti][0], 0, 0, 0);
+          dacc[ti][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(b1v[s], av[s], dacc[ti][1], 0, 0, 0);
         }
       }
     }
 #pragma unroll
     for (int ti = 0; ti < 2; ++ti) {
-      if (dbg & 2) break;
       const int w = wave + nw * ti, mt = w / K::NP, n0 = 32 * (w - mt * K::NP), n1 = n0 + 16;
       const cg_f32x4 c0 = dacc[ti][0], c1 = dacc[ti][1];
       const int u = 16 * mt + l15;
@@ -518,7 +513,6 @@ __device__ __forceinline__ void cg_adj_n1_body(const CgAdjTail& t, const CgAdjGe
   }
   if (l15 == 0) atomicAdd(&sRed[2 * K::KcM], (double)sa);
   __syncthreads();
-  if (dbg & 32) return;
   double* red = t.red + (long long)(blockIdx.x % CG_ADJ_REPLICAS) * (2 * Kc + 1);
   for (int e = tid; e < 2 * Kc; e += CG_ADJ_THREADS) atomicAdd(&red[e], sRed[e]);
   if (tid == 0) atomicAdd(&red[2 * Kc], sRed[2 * K::KcM]);
@@ -543,8 +537,8 @@ __global__ __launch_bounds__(CG_ADJ_THREADS, 2) void cg_adj_n1_kernel(CgAdjTailP
   const int b = blockIdx.x / pr.nch_max, ch = blockIdx.x - b * pr.nch_max;
   if (ch >= g.nch) return;
   const int tile0 = ch * g.tpw, tile1 = min(g.ntiles, tile0 + g.tpw);
-  if ((g.Pn & 3) == 0) { CG_ADJ_DISPATCH(g.KcM, (cg_adj_n1_body<KCM, true>(t, g, b, tile0, tile1, pr.dbg))) }
-  else { CG_ADJ_DISPATCH(g.KcM, (cg_adj_n1_body<KCM, false>(t, g, b, tile0, tile1, pr.dbg))) }
+  if ((g.Pn & 3) == 0) { CG_ADJ_DISPATCH(g.KcM, (cg_adj_n1_body<KCM, true>(t, g, b, tile0, tile1))) }
+  else { CG_ADJ_DISPATCH(g.KcM, (cg_adj_n1_body<KCM, false>(t, g, b, tile0, tile1))) }
 }
 
 // Diagnostic build only (tools/stamps_adj.py compiles a private copy of the library with -DCG_ADJ_STAMPS): thread 0 of every workgroup
@@ -567,7 +561,7 @@ extern "C" int cg_adj_set_stamps(void* p) { return (int)hipMemcpyToSymbol(HIP_SY
 // N2: de = BN'(g);  do = W0^T de;  dS[k][a] += do Q[k][b'],  dQ[k][b'] += do S[k][a];  dW0 += de (S x Q)^T
 // ======================================================================================================================
 template <int KCM, bool VEC>
-__device__ __forceinline__ void cg_adj_n2_body(const CgAdjTail& t, const CgAdjGeom& g, int b, int ch, int tile0, int tile1, int dbg) {
+__device__ __forceinline__ void cg_adj_n2_body(const CgAdjTail& t, const CgAdjGeom& g, int b, int ch, int tile0, int tile1) {
   using K = CgAdjK<KCM>;
   float* sS = reinterpret_cast<float*>(cg_dyn_lds);
   float* sQ = sS + K::KcM * g.JS;
@@ -668,7 +662,7 @@ __device__ __forceinline__ void cg_adj_n2_body(const CgAdjTail& t, const CgAdjGe
     CG_ASTAMP();                                        // A2: seed image written
     __syncthreads();
     CG_ASTAMP();                                        // A3: barrier
-    if (tile + 1 < tile1 && !(dbg & 8)) {
+    if (tile + 1 < tile1) {
       const int q0 = p0 + K::PT, nq = min(K::PT, Pn - q0);
       cg_adj_fetch<KCM, VEC>(gsrc, Kc, Pn, q0, nq, gbuf);
       if (train) cg_adj_fetch<KCM, VEC>(eb, Kc, Pn, q0, nq, ebuf);
@@ -676,7 +670,7 @@ __device__ __forceinline__ void cg_adj_n2_body(const CgAdjTail& t, const CgAdjGe
     CG_ASTAMP();                                        // B: images committed, prefetch issued
     // dW0[u][k] += sum_p de[u][p] o[k][p]: the (up to four) output tiles of a wave advance together through the tile's positions, so
     // their MFMA chains are independent and the LDS reads of a step are issued in front of all of them
-    if (!(dbg & 1) && (MT * MT >= nw || wave < MT * MT)) {       // 1 tile (wave 0), 4 tiles (one per wave) or 16 (four per wave)
+    if (MT * MT >= nw || wave < MT * MT) {       // 1 tile (wave 0), 4 tiles (one per wave) or 16 (four per wave)
 #pragma unroll
       for (int k0 = 0; k0 < K::PT; k0 += 16) {
 #pragma unroll
@@ -701,26 +695,24 @@ __device__ __forceinline__ void cg_adj_n2_body(const CgAdjTail& t, const CgAdjGe
     cg_f32x4 dacc[2][2];
 #pragma unroll
     for (int ti = 0; ti < 2; ++ti) dacc[ti][0] = dacc[ti][1] = cg_f32x4{0.f, 0.f, 0.f, 0.f};
-    if (!(dbg & 2)) {
 #pragma unroll
-      for (int k0 = 0; k0 < K::KcM; k0 += 16) {
+    for (int k0 = 0; k0 < K::KcM; k0 += 16) {
 #pragma unroll
-        for (int ti = 0; ti < 2; ++ti) {
-          const int w = wave + nw * ti, mt = w / K::NP, n0 = 32 * (w - mt * K::NP), n1 = n0 + 16;
-          float av[4], b0v[4], b1v[4];
-          cg_tfrag<1>(cg_tfrag_ptr<1>(sW + 16 * mt, K::WS, l15, slot), K::WS, k0, av);
-          cg_tfrag<1>(cg_tfrag_ptr<1>(sDE + n0, K::PS, l15, slot), K::PS, k0, b0v);
-          cg_tfrag<1>(cg_tfrag_ptr<1>(sDE + n1, K::PS, l15, slot), K::PS, k0, b1v);
+      for (int ti = 0; ti < 2; ++ti) {
+        const int w = wave + nw * ti, mt = w / K::NP, n0 = 32 * (w - mt * K::NP), n1 = n0 + 16;
+        float av[4], b0v[4], b1v[4];
+        cg_tfrag<1>(cg_tfrag_ptr<1>(sW + 16 * mt, K::WS, l15, slot), K::WS, k0, av);
+        cg_tfrag<1>(cg_tfrag_ptr<1>(sDE + n0, K::PS, l15, slot), K::PS, k0, b0v);
+        cg_tfrag<1>(cg_tfrag_ptr<1>(sDE + n1, K::PS, l15, slot), K::PS, k0, b1v);
 #pragma unroll
-          for (int s = 0; s < 4; ++s) {
-            dacc[ti][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(b0v[s], av[s], dacc[ti][0], 0, 0, 0);
-            dacc[ti][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(b1v[s], av[s], dacc[ti][1], 0, 0, 0);
-          }
+        for (int s = 0; s < 4; ++s) {
+          dacc[ti][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(b0v[s], av[s], dacc[ti][0], 0, 0, 0);
+          dacc[ti][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(b1v[s], av[s], dacc[ti][1], 0, 0, 0);
         }
       }
     }
 #pragma unroll
-    for (int ti = 0; ti < 2 && !(dbg & 2); ++ti) {
+    for (int ti = 0; ti < 2; ++ti) {
       const int w = wave + nw * ti, mt = w / K::NP, n0 = 32 * (w - mt * K::NP), n1 = n0 + 16;
       // C[position][slab]: lane = slab k, four consecutive positions: the do image in one float4
       const int k = 16 * mt + l15;
@@ -744,46 +736,45 @@ __device__ __forceinline__ void cg_adj_n2_body(const CgAdjTail& t, const CgAdjGe
     // tile: 25 000 cycles, against 6 000 for this pass); four lanes per dS cell with a DPP sum, register-resident dQ cells: no gain -
     // the pass is bound by the index arithmetic in front of each term, not by its LDS reads.
     const int a0 = (int)cg_adj_div((unsigned)p0, magicJ), r0 = p0 - a0 * J;
-    if (!(dbg & 16)) {
-      for (int cell = tid; cell < KJ; cell += CG_ADJ_THREADS) {
-        const int k = (int)cg_adj_div((unsigned)cell, magicJ), bq = cell - k * J;
-        const float* img = sDO + k * K::PS; const float* srow = sS + k * JS + a0;
-        float acc = 0.f;
-        int m = bq < r0 ? 1 : 0;
-        for (int pp = bq - r0 + J * m; pp < np; pp += J, ++m) acc += img[pp] * srow[m];
-        sDQ[k * JS + bq] += acc;
+    for (int cell = tid; cell < KJ; cell += CG_ADJ_THREADS) {
+      const int k = (int)cg_adj_div((unsigned)cell, magicJ), bq = cell - k * J;
+      const float* img = sDO + k * K::PS; const float* srow = sS + k * JS + a0;
+      float acc = 0.f;
+      int m = bq < r0 ? 1 : 0;
+      for (int pp = bq - r0 + J * m; pp < np; pp += J, ++m) acc += img[pp] * srow[m];
+      sDQ[k * JS + bq] += acc;
+    }
+    if (J >= 16) {
+      // dS by (slab, 16 consecutive positions) like the seed image above: at most one step of a inside the run, so a thread ends with
+      // two partial sums, for rows a and a + 1 (clamped to the pad column behind the last row).  The PT / 16 threads of a slab are
+      // adjacent lanes of one wave: they add their sums to the slab's cells one after the other - the LDS operations of a wave are
+      // executed in order, the wave barrier keeps the compiler from merging the phases
+      constexpr int per_row = K::PT >> 4;
+      const int k = tid / per_row, sub = tid - k * per_row, pp0 = 16 * sub, p = p0 + pp0;
+      const int a = (int)cg_adj_div((unsigned)p, magicJ), bp = p - a * J;
+      const float* img = sDO + k * K::PS + pp0; const float* qrow = sQ + k * JS;
+      float s0 = 0.f, s1 = 0.f;
+#pragma unroll
+      for (int j4 = 0; j4 < 4; ++j4) {
+        const float4 d4 = *reinterpret_cast<const float4*>(img + 4 * j4);
+        const float dv[4] = {d4.x, d4.y, d4.z, d4.w};
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          const int bj = bp + 4 * j4 + j;
+          const bool wrap = bj >= J;
+          const float pr = dv[j] * qrow[wrap ? bj - J : bj];        // the image is zero beyond np and in the rows k >= Kc
+          s0 += wrap ? 0.f : pr; s1 += wrap ? pr : 0.f;
+        }
       }
-      if (J >= 16) {
-        // dS by (slab, 16 consecutive positions) like the seed image above: at most one step of a inside the run, so a thread ends with
-        // two partial sums, for rows a and a + 1 (clamped to the pad column behind the last row).  The PT / 16 threads of a slab are
-        // adjacent lanes of one wave: they add their sums to the slab's cells one after the other - the LDS operations of a wave are
-        // executed in order, the wave barrier keeps the compiler from merging the phases
-        constexpr int per_row = K::PT >> 4;
-        const int k = tid / per_row, sub = tid - k * per_row, pp0 = 16 * sub, p = p0 + pp0;
-        const int a = (int)cg_adj_div((unsigned)p, magicJ), bp = p - a * J;
-        const float* img = sDO + k * K::PS + pp0; const float* qrow = sQ + k * JS;
-        float s0 = 0.f, s1 = 0.f;
+      float* c0 = sDS + k * JS + min(a, J); float* c1 = sDS + k * JS + min(a + 1, J);
 #pragma unroll
-        for (int j4 = 0; j4 < 4; ++j4) {
-          const float4 d4 = *reinterpret_cast<const float4*>(img + 4 * j4);
-          const float dv[4] = {d4.x, d4.y, d4.z, d4.w};
-#pragma unroll
-          for (int j = 0; j < 4; ++j) {
-            const int bj = bp + 4 * j4 + j;
-            const bool wrap = bj >= J;
-            const float pr = dv[j] * qrow[wrap ? bj - J : bj];        // the image is zero beyond np and in the rows k >= Kc
-            s0 += wrap ? 0.f : pr; s1 += wrap ? pr : 0.f;
-          }
-        }
-        float* c0 = sDS + k * JS + min(a, J); float* c1 = sDS + k * JS + min(a + 1, J);
-#pragma unroll
-        for (int j = 0; j < per_row; ++j) {
-          if (sub == j) { *c0 += s0; *c1 += s1; }
-          __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-          __builtin_amdgcn_wave_barrier();
-          __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-        }
-      } else {
+      for (int j = 0; j < per_row; ++j) {
+        if (sub == j) { *c0 += s0; *c1 += s1; }
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+      }
+    } else {
       const int M = (r0 + np - 1) / J + 1;               // rows a of the position grid that the tile touches
       for (int cell = tid; cell < Kc * M; cell += CG_ADJ_THREADS) {
         const int k = cell / M, m = cell - k * M;
@@ -795,13 +786,11 @@ __device__ __forceinline__ void cg_adj_n2_body(const CgAdjTail& t, const CgAdjGe
         if (pp < hi) acc0 += img[pp] * qrow[pp];
         if (a0 + m < J) sDS[k * JS + a0 + m] += acc0 + acc1;
       }
-      }
     }
   }
   __syncthreads();
   CG_ASTAMP();
   // this chunk's share of dS / dQ: [b][chunk][2][Kc * J], summed over the chunks by cg_adj_finish_kernel
-  if (dbg & 32) return;
   float* part = t.part + ((long long)b * g.nch + ch) * 2 * KJ;
   for (int cell = tid; cell < KJ; cell += CG_ADJ_THREADS) {
     const int k = (int)cg_adj_div((unsigned)cell, g.magicJ), a = cell - k * t.J;
@@ -831,8 +820,8 @@ __global__ __launch_bounds__(CG_ADJ_THREADS, 2) void cg_adj_n2_kernel(CgAdjTailP
   const int b = blockIdx.x / pr.nch_max, ch = blockIdx.x - b * pr.nch_max;
   if (ch >= g.nch) return;
   const int tile0 = ch * g.tpw, tile1 = min(g.ntiles, tile0 + g.tpw);
-  if ((g.Pn & 3) == 0) { CG_ADJ_DISPATCH(g.KcM, (cg_adj_n2_body<KCM, true>(t, g, b, ch, tile0, tile1, pr.dbg))) }
-  else { CG_ADJ_DISPATCH(g.KcM, (cg_adj_n2_body<KCM, false>(t, g, b, ch, tile0, tile1, pr.dbg))) }
+  if ((g.Pn & 3) == 0) { CG_ADJ_DISPATCH(g.KcM, (cg_adj_n2_body<KCM, true>(t, g, b, ch, tile0, tile1))) }
+  else { CG_ADJ_DISPATCH(g.KcM, (cg_adj_n2_body<KCM, false>(t, g, b, ch, tile0, tile1))) }
 }
 
 // per-channel parameter gradients, fold of the replicated weight gradients and of the per-chunk dS / dQ (both towers)
@@ -887,13 +876,6 @@ static CgAdjGeom cg_adj_geometry(int B, int Kc, int J) {
   g.magicJ = cg_adj_magic(J); g.magicKc = cg_adj_magic(Kc); g.magicPad = cg_adj_magic(g.WS - Kc);
   return g;
 }
-// ablation mask of the backward kernels (a private library built with -DCG_ABLATION; profiles/r02_ablations.txt): results are WRONG
-// with it set; the shipped library is compiled without the flag and cannot skip a phase
-#ifdef CG_ABLATION
-static int cg_adj_dbg() { static const int v = getenv("CG_ADJ_DBG") ? atoi(getenv("CG_ADJ_DBG")) : 0; return v; }
-#else
-static int cg_adj_dbg() { return 0; }
-#endif
 static int cg_adj_tile(int Kc) { const int KcM = cg_adj_kcm(Kc); return KcM > 32 ? 64 : KcM > 16 ? 128 : 256; }
 
 static int cg_adj_check(const CgAdjTail* it, int n) {
@@ -939,7 +921,7 @@ extern "C" int cg_map2adj_tail_fwd(const CgAdjTail* items, int n, int phase, voi
   int st = cg_adj_check(items, n);
   if (st != CG_OK) return st;
   CgAdjTailPair pr;
-  pr.n = n; pr.nch_max = cg_adj_max_chunks(items, n); pr.dbg = cg_adj_dbg(); pr.pad = 0;
+  pr.n = n; pr.nch_max = cg_adj_max_chunks(items, n);
   for (int i = 0; i < n; ++i) pr.g[i] = cg_adj_geometry(items[i].B, items[i].Kc, items[i].J);
   for (int i = 0; i < n; ++i) {
     pr.t[i] = items[i];
@@ -965,7 +947,7 @@ extern "C" int cg_map2adj_tail_bwd(const CgAdjTail* items, int n, int phase, voi
   int st = cg_adj_check(items, n);
   if (st != CG_OK) return st;
   CgAdjTailPair pr;
-  pr.n = n; pr.nch_max = cg_adj_max_chunks(items, n); pr.dbg = cg_adj_dbg(); pr.pad = 0;
+  pr.n = n; pr.nch_max = cg_adj_max_chunks(items, n);
   for (int i = 0; i < n; ++i) pr.g[i] = cg_adj_geometry(items[i].B, items[i].Kc, items[i].J);
   for (int i = 0; i < n; ++i) {
     const CgAdjTail& t = items[i];

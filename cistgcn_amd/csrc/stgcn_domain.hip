@@ -24,17 +24,10 @@
 
 HIP_DYNAMIC_SHARED(unsigned char, cg_dyn_lds)
 
-// Kernel-generation switches for A/B runs (tools/bench_planes.py).  They are honoured only in a process started with
-// CISTGCN_ABLATION=1 (read once); a production process never calls getenv() per launch and a stray variable cannot change
-// which kernel runs.  INTEGRATION.md lists them.
-static const char* cg_dom_env(const char* name) {
-  static const bool ablation = getenv("CISTGCN_ABLATION") != nullptr;
-  return ablation ? getenv(name) : nullptr;
-}
 // grid size from which the plane kernels fill the chip
 // A process-wide switch read by every forward and backward launch: atomic, and changes are refused (the current value is returned, nothing
-// moves) unless the process runs with CISTGCN_ABLATION=1 like the other kernel-generation switches - a test or tool that dies between
-// setting and restoring it cannot silently change what production launches and captured HIP graphs run.
+// moves) unless the process runs with CISTGCN_ABLATION=1 (read once) - a test or tool that dies between setting and restoring it cannot
+// silently change what production launches and captured HIP graphs run.
 static std::atomic<long long> cg_dom_planes_min{256};
 static long long cg_dom_planes_min_wgs() { return cg_dom_planes_min.load(std::memory_order_relaxed); }
 extern "C" long long cg_stgcn_domain_planes_min_workgroups(long long n) {
@@ -572,7 +565,6 @@ static int cg_dom_geom(CgDomainGeom& g, int B, int Cin, int Cout, int T, int V, 
   // (fewer than 1024 single-group tiles) instead aim at one wave of ~256 workgroups: one round on the 256 CUs.
   const long long tiles1 = (long long)B * g.NG;
   const int want_wgs = tiles1 < 1024 ? 256 : 1024;
-  const char* env_gt = cg_dom_env("CG_DOM_GT");          // tuning aid (tools/bench_planes.py); unset in production
   int best = 0;
   for (int gt = 1; gt <= g.NG; ++gt) {
     g.GT = gt; g.PP = gt * g.Jp;
@@ -582,7 +574,6 @@ static int cg_dom_geom(CgDomainGeom& g, int B, int Cin, int Cout, int T, int V, 
       best = 1;
       continue;
     }
-    if (env_gt) { if (gt > atoi(env_gt) || bytes > 150 * 1024) break; best = gt; continue; }
     if (bytes > 64 * 1024) break;
     if ((long long)B * ((g.NG + gt - 1) / gt) < want_wgs) break;
     best = gt;
@@ -600,8 +591,6 @@ static int cg_dom_geom(CgDomainGeom& g, int B, int Cin, int Cout, int T, int V, 
   // space-domain forward: more tiles in flight per XCD than its 4 MiB L2 can hold let partially written y lines
   // escape to HBM (PMC: 91 MB written per launch instead of 53 MB) -> one tile per workgroup there
   if (domain == 0 && !bwd) per = 1;
-  const char* env_per = cg_dom_env("CG_DOM_PER");        // tuning aid
-  if (env_per) per = atoi(env_per) > 0 ? atoi(env_per) : per;
   g.per = (int)per;
   return CG_OK;
 }
@@ -615,29 +604,28 @@ extern "C" int cg_stgcn_domain_fwd(const float* x, const float* adj, const float
   // wide layers, third generation: plane kernels (stgcn_domain_planes.hip) - whole plane rows in HBM, LDS as the transposer
   // (a grid of fewer than 256 workgroups - small batches - leaves most CUs idle: the tile kernels split a sample finer; the
   // time-domain variant for odd V reads its slabs one float per lane and measured no faster than the tile kernel)
-  if ((Cin >= 16 || Cout >= 16) && (long long)B * ((Cout + 15) / 16) >= cg_dom_planes_min_wgs() && !(domain == 1 && (V & 1)) &&
-      cg_dom_env("CG_DOM_NO_PLANES") == nullptr) {
+  if ((Cin >= 16 || Cout >= 16) && (long long)B * ((Cout + 15) / 16) >= cg_dom_planes_min_wgs() && !(domain == 1 && (V & 1))) {
     st = cg_domp_fwd_launch(x, adj, W, bias, y, ystats, B, Cin, Cout, T, V, domain, (hipStream_t)stream_);
     if (st != CG_ESHAPE) return st;
   }
-  // wide layers: both products on the matrix cores with the shared staging of stgcn_domain_mfma.hip (CG_DOM_FWD_OLD=1: the
-  // first-generation kernels below, kept for A/B runs)
+  // wide layers: both products on the matrix cores with the shared staging of stgcn_domain_mfma.hip (V > 64 and the shapes it
+  // refuses: the first-generation kernels below)
   // (measured at 64->64, B=256, T=50, V=22: time domain 146 vs 173 us; in the space domain both generations sit at ~280 us,
   // bound by the 4-byte-column accesses of x and y - DESIGN.md section 4 - so the first-generation kernel stays there)
-  if ((Cin >= 16 || Cout >= 16) && domain == 1 && V <= 64 && cg_dom_env("CG_DOM_FWD_OLD") == nullptr) {
+  if ((Cin >= 16 || Cout >= 16) && domain == 1 && V <= 64) {
     st = cg_domm_fwd_launch(x, adj, W, bias, y, ystats, B, Cin, Cout, T, V, domain, (hipStream_t)stream_);
     if (st != CG_ESHAPE) return st;
   }
   // matrix cores pay off in the time domain (164 vs 243 us at C=64, B=256); in the space domain the kernel is bound by
   // its 4-byte-column accesses, the MFMA variant is no faster there and measured 1.7x the HBM write traffic (PMC)
-  const bool mfma = Cin >= 16 && Cout >= 16 && domain == 1 && cg_dom_env("CG_DOM_NO_MFMA") == nullptr;
-  if (mfma) {
+  if (Cin >= 16 && Cout >= 16 && domain == 1) {
     // matrix-core path: its own LDS images; fit the tile to 64 KiB where possible
     while (g.GT > 1 && cg_dom_mfma_lds_bytes(g) > 64 * 1024) { --g.GT; g.PP = g.GT * g.Jp; }
     g.ntiles = (g.NG + g.GT - 1) / g.GT;
     if (cg_dom_mfma_lds_bytes(g) > 160 * 1024 - 256) return CG_ESHAPE;
     const long long total = (long long)B * g.ntiles;
-    if (cg_dom_env("CG_DOM_PER") == nullptr) { long long per = total / 2048; g.per = (int)(per < 1 ? 1 : (per > 16 ? 16 : per)); }
+    const long long per = total / 2048;
+    g.per = (int)(per < 1 ? 1 : (per > 16 ? 16 : per));
     const size_t lds = cg_dom_mfma_lds_bytes(g);
     const long long nwg = (total + g.per - 1) / g.per;
     dim3 grid((unsigned)(((nwg + 7) / 8) * 8)), block(256);
@@ -684,7 +672,7 @@ extern "C" int cg_stgcn_domain_bwd(const float* x, const float* adj, const float
   // wide layers, space domain: plane backward (stgcn_domain_planes.hip)
   // (narrow inputs: the channel-mix-first order makes the graph products as wide as the OUTPUT, the tile kernels keep them
   // as wide as the input - 229 vs 279 us at 10 -> 64; small batches: as in the forward)
-  if (Cin >= 16 && domain == 0 && (long long)B * ((T + 15) / 16) >= cg_dom_planes_min_wgs() && cg_dom_env("CG_DOM_NO_PLANES") == nullptr) {
+  if (Cin >= 16 && domain == 0 && (long long)B * ((T + 15) / 16) >= cg_dom_planes_min_wgs()) {
     st = cg_domp_bwd_launch(x, adj, W, dy, dx, dadj, ws, CG_DOM_REPLICAS, B, Cin, Cout, T, V, domain, stream);
     if (st != CG_ESHAPE) {
       if (st != CG_OK) return st;
@@ -694,7 +682,7 @@ extern "C" int cg_stgcn_domain_bwd(const float* x, const float* adj, const float
     }
   }
   // wide layers, time domain: local plane backward (a chunk of frames per workgroup)
-  if (Cin >= 16 && domain == 1 && (long long)B * ((T + 7) / 8) >= cg_dom_planes_min_wgs() && cg_dom_env("CG_DOM_NO_PLANES") == nullptr) {
+  if (Cin >= 16 && domain == 1 && (long long)B * ((T + 7) / 8) >= cg_dom_planes_min_wgs()) {
     st = cg_domp_bwd_time_launch(x, adj, W, dy, dx, dadj, ws, CG_DOM_REPLICAS, B, Cin, Cout, T, V, stream);
     if (st != CG_ESHAPE) {
       if (st != CG_OK) return st;
@@ -705,7 +693,7 @@ extern "C" int cg_stgcn_domain_bwd(const float* x, const float* adj, const float
   }
   // wide layers: every product on the matrix cores (stgcn_domain_mfma.hip); narrow ones (C <= 10 on both sides: CISTGCN-8,
   // the output block) stay on the VALU kernel below, where a 16-wide MFMA tile would be mostly padding
-  if ((Cin >= 16 || Cout >= 16) && (domain == 1 ? V : T) <= 64 && cg_dom_env("CG_DOM_BWD_VALU") == nullptr) {
+  if ((Cin >= 16 || Cout >= 16) && (domain == 1 ? V : T) <= 64) {
     st = cg_domm_bwd_launch(x, adj, W, dy, dx, dadj, ws, CG_DOM_REPLICAS, B, Cin, Cout, T, V, domain, stream);
     if (st != CG_ESHAPE) {
       if (st != CG_OK) return st;

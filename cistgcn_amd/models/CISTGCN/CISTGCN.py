@@ -161,7 +161,7 @@ def _pointwise(x, conv, stats=False):
     return ops.contract_stats(spec, w, x, conv.bias, bl) if stats else (ops.contract(spec, w, x, conv.bias, bl), None)
 
 
-_PWM_MIN_POSITIONS = int(__import__("os").environ.get("CISTGCN_PWM_MIN_POSITIONS", "32768"))     # B * H * W from which single 1x1 maps take the stacked kernel
+_PWM_MIN_POSITIONS = 32768     # B * H * W from which single 1x1 maps take the stacked kernel
 
 
 def _collapse_rows(x, conv, stats=False):
@@ -229,18 +229,12 @@ class CISTGCN(nn.Module):
         self.in_ch = 10
         self.fused_domain = True     # False: graph product and channel mix as two generic contractions
         self.staged = True           # True: same-depth ops of a block's parallel branches share one launch
-        # True: everything behind the tcn convolutions of a block as phase kernels (ops.dstd_tail); CISTGCN_FUSED_TAIL=0 is a tuning aid
-        self.fused_tail = __import__("os").environ.get("CISTGCN_FUSED_TAIL", "1") != "0"
-        self.fused_adj = __import__("os").environ.get("CISTGCN_FUSED_ADJ", "1") != "0"
-        self.fused_maps = __import__("os").environ.get("CISTGCN_FUSED_MAPS", "1") != "0"
-        self.fused_context = __import__("os").environ.get("CISTGCN_FUSED_CONTEXT", "1") != "0"   # ContextLayer heads 1 / 3 without their activations
-        self.fused_input = __import__("os").environ.get("CISTGCN_FUSED_INPUT", "1") != "0"   # global_norm + block statistics (and their backward with the fan-in sum) as one operator
-        self.fused_defer = __import__("os").environ.get("CISTGCN_FUSED_DEFER", "1") != "0"    # BatchNorm + PReLU of the first tower level applied by the collapsing kernels on load
-        self.fused_cols = __import__("os").environ.get("CISTGCN_FUSED_COLS", "1") != "0"      # (1,V) convolutions of the joint towers through csrc/collapse_rows.hip (cg_collapse_cols_*)
-        self.fused_towers = __import__("os").environ.get("CISTGCN_FUSED_TOWERS", "1") != "0"   # first tower level + BatchNorm + PReLU as one operator (backward without the BatchNorm input gradient)
-        self.fused_gates = __import__("os").environ.get("CISTGCN_FUSED_GATES", "1") != "0"    # the gate paths behind their (1,V) convolutions as one launch
-        self.fused_res_maps = True   # the residual 1x1 convolutions (with bias) of a width-changing block through the stacked kernel too
-        self.stack_min_elements = int(__import__("os").environ.get("CISTGCN_STACK_MIN_ELEMENTS", str(1 << 21)))      # block inputs smaller than this keep one contraction per first-level map
+        # the switches below are for tests, which pin one plan against another (tests/checks.py::build_pair, test_gpu_parity.py)
+        self.fused_tail = True       # everything behind the tcn convolutions of a block as phase kernels (ops.dstd_tail)
+        self.fused_adj = True        # seed, expansor and adjacency of both Map2Adj towers as phase kernels (ops.map2adj_tail)
+        self.fused_maps = True       # the first-level maps of a block (towers, gates, residual maps) and of the context heads stacked
+        self.fused_defer = True      # BatchNorm + PReLU of the first tower level applied by the collapsing kernels on load
+        self.stack_min_elements = 1 << 21      # block inputs smaller than this keep one contraction per first-level map
         # The reference edits the config lists in place (CISTGCN.py:514-517,548); copies are used here
         # so that one `opt` can build several models.
         widths = [self.in_ch] + list(p.input_gcn.model_complexity) + [self.in_ch]
@@ -421,7 +415,7 @@ class CISTGCN(nn.Module):
         if not all(d.interpretable for d in doms):
             return self._block(m, x)
         x_in, x_sums = x if isinstance(x, tuple) else (x, None)       # (tensor, f64 channel sums) from the previous block's tail in train mode
-        fused_in = self.fused_input and ops.block_input_ok(x_in)
+        fused_in = ops.block_input_ok(x_in)
         xn0 = None if fused_in else self._na(x, bn=m.global_norm)
         B, _, T, V = x_in.shape
         has_res = not isinstance(m.dsgn.residual, nn.Identity)
@@ -443,7 +437,7 @@ class CISTGCN(nn.Module):
         # input in one pass per group as well (a group: up to 128 stacked output rows)
         res_convs = ([d.residual[0] for d in doms] if has_res else []) + ([m.residual[0]] if has_bres else [])
         res_w = [c.weight.view(c.out_channels, c.in_channels) for c in res_convs]
-        res_groups = self._map_groups(x_in, res_w) if (big and self.fused_maps and self.fused_res_maps and res_convs) else None
+        res_groups = self._map_groups(x_in, res_w) if (big and self.fused_maps and res_convs) else None
         n_alias = 4 + (1 if stacked else 0) + (1 if rows_gate else 0) + (len(res_groups) if res_groups else 0) + (0 if has_res else 2) + (0 if has_bres else 1)
         if fused_in:
             # global_norm and the block statistics from one pass over the block input; in backward the gradients of all the consumers below,
@@ -494,19 +488,18 @@ class CISTGCN(nn.Module):
         if stacked:
             tb = [b for a in maps for b in (a.time_compress[1], a.joint_compress[1])]
             tp = [b for a in maps for b in (a.time_compress[2], a.joint_compress[2])]
-            if self.fused_towers and ops.tower_maps_ok(x_maps, tower_w, tp):
+            if ops.tower_maps_ok(x_maps, tower_w, tp):
                 # first level of the four towers with its BatchNorm + PReLU as one operator: backward never stores the gradient in front of
                 # the BatchNorm (the pointwise backward undoes BatchNorm and PReLU while loading)
                 # ... and, when every map goes into a whole-sample collapsing kernel, the BatchNorm + PReLU themselves move into that
                 # kernel's load path: the four activated (B, C/2, T, V) maps are never stored (unless branch records are asked for: `in_tap`)
                 def _collapse_ok(k, wmap):
-                    a_, tower = maps[k // 2], (maps[k // 2].time_compress if k % 2 == 0 else maps[k // 2].joint_compress)
-                    c_ = tower[3]
-                    probe = torch.empty(0, device=x_maps.device).new_empty((B, wmap.shape[0], T, V))
-                    wv = c_.weight.view(c_.out_channels, c_.in_channels, -1)
+                    c_ = (maps[k // 2].time_compress if k % 2 == 0 else maps[k // 2].joint_compress)[3]
                     if c_.bias is not None:
                         return False
-                    return ops.collapse_rows_ok(probe, wv) if k % 2 == 0 else (self.fused_cols and ops.collapse_cols_ok(probe, wv))
+                    probe = torch.empty((B, wmap.shape[0], T, V), device="meta")      # the shape of the raw map, nothing allocated
+                    wv = c_.weight.view(c_.out_channels, c_.in_channels, -1)
+                    return ops.collapse_rows_ok(probe, wv) if k % 2 == 0 else ops.collapse_cols_ok(probe, wv)
                 defer = self.fused_defer and big and all(_collapse_ok(k, wmap) for k, wmap in enumerate(tower_w))
                 if defer:
                     towers_done, tower_tr = ops.tower_maps(x_maps, tower_w, tb, tp, tr, defer=True)
@@ -524,7 +517,7 @@ class CISTGCN(nn.Module):
         res_done = None
         if res_groups:
             res_bns = ([d.residual[1] for d in doms] if has_res else []) + ([m.residual[1]] if has_bres else [])
-            if self.fused_towers and all(ops.tower_maps_ok(xg, [res_w[i] for i in grp], [None] * len(grp)) for xg, grp in zip(x_resmaps, res_groups)):
+            if all(ops.tower_maps_ok(xg, [res_w[i] for i in grp], [None] * len(grp)) for xg, grp in zip(x_resmaps, res_groups)):
                 # the residual maps with their BatchNorm as one operator per group, like the towers: backward is one reduction pass and the
                 # pointwise backward undoing the BatchNorm on load (as two operators: 229 us of cg_norm_act_bwd on the 10 -> 64 block)
                 res_done = [None] * len(res_convs)
@@ -583,7 +576,7 @@ class CISTGCN(nn.Module):
             c4 = a.joint_compress[3]
             x4 = t1[2 * i + 1][0] if isinstance(t1[2 * i + 1], tuple) else t1[2 * i + 1]
             w4 = c4.weight.view(c4.out_channels, c4.in_channels, -1)
-            if big and self.fused_cols and c4.bias is None and ops.collapse_cols_ok(x4, w4):
+            if big and c4.bias is None and ops.collapse_cols_ok(x4, w4):
                 y4, st4 = ops.collapse_cols(x4, w4, tr, transform=tower_tr[2 * i + 1] if tower_tr else None)  # whole-sample kernel for the joint axis
                 cols3[i] = (y4.unsqueeze(3), st4)
             else:
@@ -601,7 +594,7 @@ class CISTGCN(nn.Module):
                 o.append(cols3[i] if i in cols3 else rest.pop(0))
         # 4. BatchNorm tails
         Cg = m.conv_s[4].out_channels
-        gate_fused = (self.fused_gates and o[0][0].shape[1] == Cg and o[0][0].numel() == B * Cg and
+        gate_fused = (o[0][0].shape[1] == Cg and o[0][0].numel() == B * Cg and
                       ops.gate_head_ok(B, Cg, stats_s.shape[1], (m.conv_s[7], m.conv_t[7], m.map_s[3], m.map_t[3])))
         tower_calls = []
         for i, a in enumerate(maps):
@@ -723,7 +716,7 @@ class CISTGCN(nn.Module):
         c1, c2, c3 = m.context_conv1, m.context_conv2, m.context_conv3
         tr = self.training
         w13 = [c[0].weight.view(c[0].out_channels, c[0].in_channels) for c in (c1, c3)]
-        if self.fused_context and c1[0].bias is None and c3[0].bias is None and ops.context_heads_ok(x, c1[0].out_channels):
+        if c1[0].bias is None and c3[0].bias is None and ops.context_heads_ok(x, c1[0].out_channels):
             # heads 1 and 3 (max / mean over the positions of a 1 -> hidden_dim map, BatchNorm, PReLU) from the one-channel sequence
             # itself: their (B, hidden_dim, To, 3V) activations are never stored (csrc/context_heads.hip)
             xa, xb = ops.fanout(x, 2)

@@ -103,7 +103,7 @@ class _ZeroPool:
 _arenas = {}
 _zero_pools = {}
 _seeds = {}
-_ARENA_CHECK = bool(int(__import__("os").environ.get("CISTGCN_ARENA_CHECK", "0")))
+_ARENA_CHECK = bool(int(os.environ.get("CISTGCN_ARENA_CHECK", "0")))
 
 
 def _dev(device):
@@ -281,7 +281,7 @@ def _plan(sizes, la, lx, ly, sa, sx, sy, oa, ox, oy, bias_label, device, y_dense
     p.splitk = 1
     p.dense = y_dense
     p.mode, p.ws_floats = 0, 0
-    if y_dense and p.K >= 256 and blocks < 512 and aligned and _KRED and _kred_ok(p, tabs):
+    if y_dense and p.K >= 256 and blocks < 512 and aligned and _kred_ok(p, tabs):
         # weight gradient of a pointwise map: K-reduction kernel (float4 along k straight into the matrix cores,
         # replicated partial sums folded by the last workgroup)
         bt = 16 if max(p.M, p.N) <= 16 else 32
@@ -289,7 +289,7 @@ def _plan(sizes, la, lx, ly, sa, sx, sy, oa, ox, oy, bias_label, device, y_dense
         p.mode = 2
         p.splitk = int(max(1, (p.K + 4063) // 4064, min(512, (p.K + 255) // 256, max(1, _KRED_BLOCKS // tiles))))
         p.ws_floats = int(_lib.lib().cg_contract_kred_ws_floats(p.G, p.M, p.N))
-    elif (y_dense and aligned and _STREAM and p.x_vec and p.K <= 128 and p.N >= _STREAM_MIN_N and _quads(tabs[7])
+    elif (y_dense and aligned and p.x_vec and p.K <= 128 and p.N >= _STREAM_MIN_N and _quads(tabs[7])
           and (tabs[4] % 4 == 0).all() and (tabs[2] % 4 == 0).all()):
         p.mode = 1        # pointwise map over a long contiguous position axis: streaming kernel (A panel in LDS, X via float4)
     elif y_dense and p.K >= 256 and blocks < 512:
@@ -301,15 +301,13 @@ def _plan(sizes, la, lx, ly, sa, sx, sy, oa, ox, oy, bias_label, device, y_dense
     return p
 
 
-_KRED = bool(int(__import__("os").environ.get("CISTGCN_KRED", "1")))     # tuning aid: 0 = always the tiled split-K path
-_STREAM = bool(int(__import__("os").environ.get("CISTGCN_STREAM", "1")))  # tuning aid: 0 = tiled path for pointwise maps
 # below ~6e4 positions a launch is latency bound either way and splitting a batch into two kernels costs a graph node
-_STREAM_MIN_N = int(__import__("os").environ.get("CISTGCN_STREAM_MIN_N", "65536"))
-_KRED_BLOCKS = int(__import__("os").environ.get("CISTGCN_KRED_BLOCKS", "128"))
-_KRED_MAX = int(__import__("os").environ.get("CISTGCN_KRED_MAX", "64"))
+_STREAM_MIN_N = 65536
+_KRED_BLOCKS = 128
+_KRED_MAX = 64
 # measured on MI355X (A/B on one box): below ~1e5 reduction elements the tiled split-K plan is as fast or faster
 # (B=16 step +2.5 % with K-reduction everywhere), above it the K-reduction kernel wins (B=256, C=64 step -3.3 %)
-_KRED_MIN_K = int(__import__("os").environ.get("CISTGCN_KRED_MIN_K", "65536"))
+_KRED_MIN_K = 65536
 
 
 def _quads(tab):
@@ -547,15 +545,10 @@ class _ContractMany(torch.autograd.Function):
         return (None,) + tuple(res)
 
 
-_CHAIN = bool(int(__import__("os").environ.get("CISTGCN_CHAIN", "1")))        # tuning aid: 0 = separate outputs + one sum
-
-
 def _chain_lists(cands, builders):
     """Split each candidate list (builder indices whose outputs are to be summed) into runs that share the streaming
     geometry; runs of one stay unchained."""
     out = []
-    if not _CHAIN:
-        return out
     for idxs in cands:
         byg = {}
         for i in idxs:
@@ -930,12 +923,11 @@ class _Fanout(torch.autograd.Function):
 
 
 _SUM_MAX = 8
-_FANOUT = bool(int(__import__("os").environ.get("CISTGCN_FANOUT", "1")))      # tuning aid: 0 = let autograd accumulate
 
 
 def fanout(x, n):
     """n autograd-independent aliases of x (see _Fanout); n <= 1 returns (x,)"""
-    if n <= 1 or not _FANOUT or not (torch.is_grad_enabled() and x.requires_grad):
+    if n <= 1 or not (torch.is_grad_enabled() and x.requires_grad):
         return (x,) * max(n, 1)
     return _Fanout.apply(x, n)
 
@@ -1119,14 +1111,13 @@ def dilated_convs(x, convs):
     B, C, H, W = x.shape
     O = convs[0].out_channels
     # (one workgroup per sample: below ~64 samples the chip is mostly idle and the generic contraction is faster)
-    if (_FPN_KERNELS and B >= _FPN_MIN_BATCH and x.stride(3) == 1 and all(c.out_channels == O and c.bias is not None for c in convs)
+    if (B >= _FPN_MIN_BATCH and x.stride(3) == 1 and all(c.out_channels == O and c.bias is not None for c in convs)
             and _lib.lib().cg_fpn_conv_supported(B, C, O, H, W)):
         return _FpnConvs.apply(x, dils, *wb)
     return _DilatedConvs.apply(x, dils, *wb)
 
 
-_FPN_KERNELS = __import__("os").environ.get("CISTGCN_FPN_KERNELS", "1") != "0"     # 0: the generic contraction (tuning aid)
-_FPN_MIN_BATCH = int(__import__("os").environ.get("CISTGCN_FPN_MIN_BATCH", "64"))
+_FPN_MIN_BATCH = 64
 
 
 class _FpnConvs(torch.autograd.Function):
@@ -2145,7 +2136,7 @@ class _TowerMaps(torch.autograd.Function):
         stream = _stream(x)
         # pass 1: channel sums of the gradient in front of the BatchNorm, slope gradients, dgamma / dbeta
         arr = (NormAct * n)()
-        reds, smalls, have_red = [], [], []
+        reds, smalls = [], []
         for i in range(n):
             a, bn = arr[i], cfg["bn"][i]
             M = ws[i].shape[0]
@@ -2158,24 +2149,13 @@ class _TowerMaps(torch.autograd.Function):
             nal = alphas[i].numel() if ctx.has_alpha[i] else 0
             if nal:
                 a.alpha, a.alpha_n = alphas[i].data_ptr(), nal
-            given = ctx.deferred[i].get("red") if getattr(ctx, "deferred", None) else None
-            red = given if given is not None else _arena(dev).take(2 * M + (_lib.ALPHA_SLOTS if nal <= 1 else nal))
-            have_red.append(given is not None)
+            red = _arena(dev).take(2 * M + (_lib.ALPHA_SLOTS if nal <= 1 else nal))
             small = torch.empty(3, M, dtype=f32, device=dev)
             a.red, a.dgamma, a.dbeta = red.data_ptr(), small[0].data_ptr(), small[1].data_ptr()
             if nal:
                 a.dalpha = small[2].data_ptr()
             reds.append(red); smalls.append(small)
-        if all(have_red):
-            _lib.call("cg_norm_act_params_many", arr, n, stream)        # the consumers' backward kernels summed already: parameter gradients only
-        else:
-            if any(have_red):                                           # mixed: redo all of them here (fresh words for the ones already summed)
-                for i in range(n):
-                    if have_red[i]:
-                        nal = alphas[i].numel() if ctx.has_alpha[i] else 0
-                        reds[i] = _arena(dev).take(2 * ws[i].shape[0] + (_lib.ALPHA_SLOTS if nal <= 1 else nal))
-                        arr[i].red = reds[i].data_ptr()
-            _lib.call("cg_norm_act_bwd_reduce_many", arr, n, stream)
+        _lib.call("cg_norm_act_bwd_reduce_many", arr, n, stream)
         # pass 2: dx and dW_i (db_i) with BatchNorm / PReLU undone on load
         t = _PointwiseMaps._block(x, ws, [None] * n)
         dx = torch.empty_like(x)
@@ -2256,19 +2236,9 @@ def split_channels(y, sizes):
     return _SplitChannels.apply(tuple(int(s) for s in sizes), y)
 
 
-_ROWS_KERNELS = __import__("os").environ.get("CISTGCN_ROWS_KERNELS", "1") != "0"     # 0: the generic contraction (tuning aid)
-
-
-# BatchNorm / PReLU backward sums of a deferred tower map from the collapsing backward kernel (`in_red`) instead of cg_norm_act_bwd_reduce_many.
-# OFF by default: measured at the headline shape the two backward kernels grow from 48 / 55 to 71 / 82 us per call (228 / 286 VGPRs: the raw
-# x of the result positions travels a sample ahead, nine f64 sums per lane), more than the 65 us reduction pass per block they replace.
-# `transform["fold_reduce"] = True` selects it per map (tests/checks.py::check_tower_collapse does for one shape).
-_FOLD_REDUCE = os.environ.get("CISTGCN_FOLD_REDUCE", "0") == "1"
-
-
 def collapse_rows_ok(x, w):
     """True when `collapse_rows` takes the (T,1) convolution `w` (O,C,T) of x (B,C,T,V)."""
-    if not _ROWS_KERNELS or x.dim() != 4 or not x.is_contiguous() or w.dim() != 3:
+    if x.dim() != 4 or not x.is_contiguous() or w.dim() != 3:
         return False
     B, C, T, V = x.shape
     return w.shape[1] == C and w.shape[2] == T and V <= 32 and w.shape[0] <= 64 and (C * T) % 4 == 0
@@ -2323,11 +2293,6 @@ class _CollapseRows(torch.autograd.Function):
         dy = dy if dy.is_contiguous() else _copy(dy)
         B, C, T, V = x.shape
         t = _CollapseRows._block(x, w, ctx.tr)
-        if ctx.tr is not None and ctx.tr.get("fold_reduce", _FOLD_REDUCE):
-            # the reduction pass of the BatchNorm / PReLU backward (sums of g, g * xhat, slope gradient) is done here, where dx' is produced
-            red = _arena(x.device).take(2 * C + _lib.ALPHA_SLOTS)
-            t.in_red = red.data_ptr()
-            ctx.tr["red"] = red
         dx = torch.empty_like(x)
         dw = torch.empty_like(w)
         zb, _z = _zeros(int(_lib.lib().cg_collapse_rows_ws_floats(C, T, w.shape[0])), x.device)
@@ -2344,7 +2309,7 @@ def collapse_rows(x, w, want_stats=False, transform=None):
 
 def collapse_cols_ok(x, w):
     """True when `collapse_cols` takes the (1,V) convolution `w` (O,C,V) of x (B,C,T,V)."""
-    if not _ROWS_KERNELS or x.dim() != 4 or not x.is_contiguous() or w.dim() != 3:
+    if x.dim() != 4 or not x.is_contiguous() or w.dim() != 3:
         return False
     B, C, T, V = x.shape
     return w.shape[1] == C and w.shape[2] == V and T <= 64 and w.shape[0] <= 64 and (C * V) % 4 == 0 and C * T * V < 2 ** 31
@@ -2379,11 +2344,6 @@ class _CollapseCols(torch.autograd.Function):
         dy = dy if dy.is_contiguous() else _copy(dy)
         B, C, T, V = x.shape
         t = _CollapseRows._block(x, w, ctx.tr)
-        if ctx.tr is not None and ctx.tr.get("fold_reduce", _FOLD_REDUCE):
-            # the reduction pass of the BatchNorm / PReLU backward (sums of g, g * xhat, slope gradient) is done here, where dx' is produced
-            red = _arena(x.device).take(2 * C + _lib.ALPHA_SLOTS)
-            t.in_red = red.data_ptr()
-            ctx.tr["red"] = red
         dx = torch.empty_like(x)
         dw = torch.empty_like(w)
         zb, _z = _zeros(int(_lib.lib().cg_collapse_cols_ws_floats(C, V, w.shape[0])), x.device)

@@ -5,7 +5,6 @@ The reference has no distributed code at all (train.py:214 pins one GPU); batche
 except for per-replica BatchNorm statistics, so data parallelism = every rank runs the same step
 on its shard and the flat gradient buffer is all-reduced (sum) and scaled by 1/world.
 """
-import os
 import ctypes
 
 import numpy as np
@@ -461,9 +460,6 @@ class DataParallelStep(_StepBase):
         "tried", "groups"}."""
         import torch.distributed as dist
         dev = self.x.device
-        if os.environ.get("CISTGCN_SIDE_STREAM_PROBE", "1") == "0":      # tuning aid: take the next pool stream unmeasured
-            self._side, self.overlap_probe = torch.cuda.Stream(device=dev), {"independent": None, "collective": False, "tried": 0, "groups": 0}
-            return self.overlap_probe
         main = torch.cuda.current_stream(dev)
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         torch.cuda._sleep(200000)

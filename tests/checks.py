@@ -1146,9 +1146,6 @@ def check_tower_collapse(device, shapes=((3, 10, (8, 8, 8, 8), 6, 8, 5), (2, 64,
             xd = _leaf(x0, device)
             ops.begin_step(device)
             ys, trs = ops.tower_maps(xd, [m[0].weight.view(m[0].out_channels, C) for m in net], [m[1] for m in net], [m[2] for m in net], train, defer=True)
-            if C in (64, 12):                          # the opt-in variant on two shapes: the BatchNorm / PReLU backward sums from the collapsing backward kernels
-                for tr_ in trs:
-                    tr_["fold_reduce"] = True
             outs = []
             for k, m in enumerate(net):
                 w = m[3].weight.view(O, m[3].in_channels, -1)

@@ -1,12 +1,20 @@
 #!/usr/bin/env python3
 """GPU box: A/B of the fused ST-GCN stage generations in ONE process (interleaved rounds, HIP events):
-plane kernels (stgcn_domain_planes.hip) against the tile kernels (CG_DOM_NO_PLANES=1).  Needs CISTGCN_ABLATION=1 (set here)."""
+plane kernels (stgcn_domain_planes.hip) against the tile kernels, forced by moving the plane kernels' grid threshold out of reach
+(cg_stgcn_domain_planes_min_workgroups, as tests/checks.py::check_stgcn_domain does).  Needs CISTGCN_ABLATION=1 (set here)."""
 import os, sys
 os.environ["CISTGCN_ABLATION"] = "1"
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import torch
 from cistgcn_amd import _lib, ops
+
+PLANES_MIN = _lib.lib().cg_stgcn_domain_planes_min_workgroups(-1)      # the shipped threshold
+
+
+def planes(on):
+    """on: the shipped dispatch (plane kernels where the grid fills the chip); off: the tile kernels for every launch"""
+    _lib.lib().cg_stgcn_domain_planes_min_workgroups(PLANES_MIN if on else 1 << 62)
 
 
 def timeit(fn, reps=20):
@@ -25,11 +33,11 @@ def ab(fn, rounds=5):
     """median over interleaved rounds of (new, old)"""
     new, old = [], []
     for _ in range(rounds):
-        os.environ.pop("CG_DOM_NO_PLANES", None)
+        planes(True)
         new.append(timeit(fn))
-        os.environ["CG_DOM_NO_PLANES"] = "1"
+        planes(False)
         old.append(timeit(fn))
-    os.environ.pop("CG_DOM_NO_PLANES", None)
+    planes(True)
     new.sort(); old.sort()
     return new[len(new) // 2], old[len(old) // 2]
 
@@ -54,12 +62,11 @@ for (B, ci, co, T, V) in shapes:
         bwd = lambda: _lib.call("cg_stgcn_domain_bwd", p(x), p(adj), p(w), p(dy), p(dx), p(dadj), p(dw), p(db), p(ws), B, ci, co, T, V, dom, 0, st)
         # results of both generations
         res = {}
-        for name, env in (("new", None), ("old", "1")):
-            if env: os.environ["CG_DOM_NO_PLANES"] = env
-            else: os.environ.pop("CG_DOM_NO_PLANES", None)
+        for name, on in (("new", True), ("old", False)):
+            planes(on)
             fwd(); bwd(); torch.cuda.synchronize()
             res[name] = [t.clone() for t in (y, dx, dadj, dw, db)]
-        os.environ.pop("CG_DOM_NO_PLANES", None)
+        planes(True)
         err = [float((a - o).abs().max() / o.abs().max().clamp_min(1e-30)) for a, o in zip(res["new"], res["old"])]
         fn, fo = ab(fwd)
         bn, bo = ab(bwd)
