@@ -228,6 +228,14 @@ _SIGNATURES = {
     "cg_map2adj_tail_part_floats": [c_int, c_int, c_int],
     "cg_map2adj_tail_red_doubles": [c_int],
     "cg_augment_sequences": [P, P, P, P, P, P, P, P, P, P, c_int, c_int, c_int, c_int, P],
+    "cg_map2adj_tail_geometry": [c_int, c_int, c_int, POINTER(c_int)],
+    "cg_dstd_tail_geometry": [c_int, c_int, c_int, c_int, POINTER(c_int)],
+    "cg_pointwise_maps_geometry": [c_int, c_int, c_int, c_int, POINTER(c_int), c_int, POINTER(c_int)],
+    "cg_collapse_geometry": [c_int, c_int, c_int, c_int, c_int, c_int, POINTER(c_int)],
+    "cg_fpn_conv_geometry": [c_int, c_int, c_int, c_int, c_int, POINTER(c_int)],
+    "cg_stgcn_domain_geometry": [c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, POINTER(c_int)],
+    "cg_block_input_geometry": [c_int, c_int, c_int, c_int, POINTER(c_int)],
+    "cg_norm_act_rows_per_block": [POINTER(View4)],
     "cg_adam_flat": [P, P, P, P, LL, c_float, c_float, c_float, c_float, c_float, c_float, c_float, LL, P],
 }
 EXPORTS = tuple(sorted(_SIGNATURES))

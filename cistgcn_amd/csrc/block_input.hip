@@ -318,6 +318,19 @@ extern "C" int cg_block_input_supported(int B, int C, int T, int V) {
   return cg_bin_geometry(&t, &g) == CG_OK ? 1 : 0;
 }
 
+static unsigned cg_bin_grid(const CgBlockInput* t, const CgBinGeom& g) { return (unsigned)(t->B * g.cps); }
+// include/cistgcn_hip.h : host-only, spans of planes per sample and the grid of the streaming kernels (no launch)
+extern "C" int cg_block_input_geometry(int B, int C, int T, int V, int* out) {
+  if (!out) return CG_EARG;
+  CgBlockInput t;
+  t.B = B; t.C = C; t.T = T; t.V = V;
+  CgBinGeom g;
+  const int st = cg_bin_geometry(&t, &g);
+  if (st != CG_OK) return st;
+  out[0] = g.NPL; out[1] = g.cps; out[2] = (int)cg_bin_grid(&t, g);
+  return CG_OK;
+}
+
 // include/cistgcn_hip.h : cg_block_input_fwd / cg_block_input_bwd
 extern "C" int cg_block_input_fwd(const CgBlockInput* t, void* stream_) {
   CgBinGeom g;
@@ -327,7 +340,7 @@ extern "C" int cg_block_input_fwd(const CgBlockInput* t, void* stream_) {
   if (t->train ? !t->bn.stats : (!t->bn.running_mean || !t->bn.running_var)) return CG_EARG;
   hipStream_t stream = (hipStream_t)stream_;
   const size_t lds = ((size_t)g.L + 4 * g.NPL) * sizeof(float);
-  const dim3 grid((unsigned)(t->B * g.cps)), block(CG_BIN_THREADS);
+  const dim3 grid(cg_bin_grid(t, g)), block(CG_BIN_THREADS);
   const int vw = cg_bin_vw(g, {t->x, t->xn});
   if (vw == 4) hipLaunchKernelGGL(cg_bin_fwd_kernel<4>, grid, block, lds, stream, *t, g);
   else if (vw == 2) hipLaunchKernelGGL(cg_bin_fwd_kernel<2>, grid, block, lds, stream, *t, g);
@@ -358,7 +371,7 @@ extern "C" int cg_block_input_bwd(const CgBlockInput* t, void* stream_) {
     st = cg_launch_status();
     if (st != CG_OK) return st;
   } else a.pq = nullptr;
-  const dim3 grid((unsigned)(t->B * g.cps));
+  const dim3 grid(cg_bin_grid(t, g));
   const size_t lds = ((size_t)2 * g.NPL * t->T + 4 * g.NPL + 2) * sizeof(float) + (size_t)2 * g.NPL * sizeof(double);
   int vw = cg_bin_vw(g, {t->x, t->gsum, t->g[0], t->g[1], t->g[2], t->g[3], t->g[4], t->g[5], t->g[6], t->g[7]});
   if (vw == 4) hipLaunchKernelGGL(cg_bin_bwd_sum_kernel<4>, grid, block, lds, stream, a, g);

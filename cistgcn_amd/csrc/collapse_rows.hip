@@ -617,6 +617,19 @@ static int cg_cols_nt(int T) { return T <= 16 ? 1 : T <= 32 ? 2 : 4; }
 extern "C" int cg_collapse_cols_supported(int C, int T, int V, int O) { return T >= 1 && T <= 64 && O >= 1 && O <= 64 && (((long long)C * V) & 3) == 0 ? 1 : 0; }
 extern "C" long long cg_collapse_cols_ws_floats(int C, int V, int O) { return (long long)CG_ROWS_REPLICAS * O * C * V; }
 
+// include/cistgcn_hip.h : host-only, the backward grid of cg_collapse_rows_bwd (cols == 0) / cg_collapse_cols_bwd (no launch)
+extern "C" int cg_collapse_geometry(int B, int C, int T, int V, int O, int cols, int* out) {
+  if (!out) return CG_EARG;
+  static const float dummy = 0.f;               // the geometry refuses null operands; it never reads them
+  CgRowsConv t = {};
+  t.B = B; t.C = C; t.T = T; t.V = V; t.O = O; t.x = &dummy; t.W = &dummy;
+  CgRowsGeom g;
+  const int st = cols ? cg_cols_geometry(&t, &g) : cg_rows_geometry(&t, &g);
+  if (st != CG_OK) return st;
+  out[0] = g.kranges; out[1] = g.slices; out[2] = g.per;
+  return CG_OK;
+}
+
 #define CG_COLS_DISPATCH(OT_, NT_, LAUNCH)                         \
   switch (4 * ((OT_) - 1) + ((NT_) == 1 ? 0 : (NT_) == 2 ? 1 : 2)) { \
     case 0: LAUNCH(1, 1) break; case 1: LAUNCH(1, 2) break; case 2: LAUNCH(1, 4) break;       \

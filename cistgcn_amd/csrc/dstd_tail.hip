@@ -1033,25 +1033,51 @@ __global__ void cg_tail_fold_kernel(const float* __restrict__ ws, int replicas, 
 // ---- host side ---------------------------------------------------------------------------------------------------
 #define CG_TAIL_REPLICAS 16
 
+static int cg_tail_shape_ok(int B, int C, int T, int V) { return B > 0 && C > 0 && T > 0 && V > 0 && C <= 64 && B <= 65535; }
+// grid of the row phases: (channels, groups of `rb` samples)
+static dim3 cg_tail_row_grid(int B, int C, int rb) { return dim3((unsigned)C, (unsigned)((B + rb - 1) / rb), 1); }
+
 static int cg_tail_check(const CgDstdTail* t) {
   if (!t) return CG_EARG;
-  if (t->B <= 0 || t->C <= 0 || t->T <= 0 || t->V <= 0 || t->C > 64) return CG_ESHAPE;
+  if (!cg_tail_shape_ok(t->B, t->C, t->T, t->V)) return CG_ESHAPE;
   for (int i = 0; i < 2; ++i)
     if (!t->y[i] || !t->r[i] || !t->w[i] || !t->alpha_d[i] || !t->alpha_p[i] || !t->bn_t[i].gamma || !t->bn_p[i].gamma || !t->bn_t[i].save ||
         !t->bn_p[i].save) return CG_EARG;
   if (!t->Wc || !t->bn_c.gamma || !t->bn_c.save || !t->alpha_c || !t->h0) return CG_EARG;
   if (t->train && t->drop_p > 0.f && !t->seed) return CG_EARG;
-  if (t->B > 65535) return CG_ESHAPE;
   return CG_OK;
 }
 
 extern "C" long long cg_dstd_tail_ws_floats(int C) { return (long long)CG_TAIL_REPLICAS * C * 2 * C; }
+
+// ranges of the matrix phases (F2: tiles of CG_TAIL_PT positions, K3: CG_TAIL_PT3): the B * tps tiles of the batch in sample-major order,
+// `per` consecutive ones per workgroup, at most 512 workgroups
+struct CgTailRanges { int tps, total, per, nwg; };
+static CgTailRanges cg_tail_ranges(int B, int P, int PT) {
+  CgTailRanges r;
+  r.tps = (P + PT - 1) / PT; r.total = B * r.tps;
+  r.per = (r.total + 511) / 512; r.nwg = (r.total + r.per - 1) / r.per;
+  return r;
+}
 
 static size_t cg_tail_gemm_lds(int C, bool bwd) {
   const int CM = (C + 15) & ~15, C2M = (2 * C + 15) & ~15, WS = C2M + 4;
   size_t f = (size_t)C2M * (bwd ? CG_TAIL_PS3 : CG_TAIL_PS) + (size_t)CM * WS + (size_t)8 * C2M;
   if (bwd) f += (size_t)CM * CG_TAIL_PS3 + (size_t)8 * CM;
   return f * sizeof(float) + (bwd ? (size_t)(2 * C2M + 2) : (size_t)2 * CM) * sizeof(double) + 16;
+}
+
+// include/cistgcn_hip.h : host-only, what the launchers below choose (no launch)
+extern "C" int cg_dstd_tail_geometry(int B, int C, int T, int V, int* out) {
+  if (!out) return CG_EARG;
+  if (!cg_tail_shape_ok(B, C, T, V)) return CG_ESHAPE;
+  const int P = T * V;
+  const int rb = cg_tail_rows(B, C, P);
+  out[0] = rb; out[1] = (int)cg_tail_row_grid(B, C, rb).y;
+  const CgTailRanges f2 = cg_tail_ranges(B, P, CG_TAIL_PT), k3 = cg_tail_ranges(B, P, CG_TAIL_PT3);
+  out[2] = CG_TAIL_PT; out[3] = f2.tps; out[4] = f2.total; out[5] = f2.per; out[6] = f2.nwg;
+  out[7] = CG_TAIL_PT3; out[8] = k3.tps; out[9] = k3.total; out[10] = k3.per; out[11] = k3.nwg;
+  return CG_OK;
 }
 
 // include/cistgcn_hip.h : cg_dstd_tail_fwd (phases 1..4) / cg_dstd_tail_bwd (phases 1..5)
@@ -1061,15 +1087,15 @@ extern "C" int cg_dstd_tail_fwd(const CgDstdTail* t, int phase, void* stream_) {
   hipStream_t stream = (hipStream_t)stream_;
   const int P = t->T * t->V;
   const int rb = cg_tail_rows(t->B, t->C, P);
-  const dim3 rows((unsigned)t->C, (unsigned)((t->B + rb - 1) / rb), 1);
+  const dim3 rows = cg_tail_row_grid(t->B, t->C, rb);
   if (phase == 1) {
     if (!t->train) return CG_OK;                      // eval: running statistics, nothing to reduce
     if (!t->bn_t[0].stats || !t->bn_t[1].stats || !t->bn_p[0].stats || !t->bn_p[1].stats) return CG_EARG;
     hipLaunchKernelGGL(cg_tail_f1_kernel, dim3(rows.x, rows.y, 2), dim3(256), 0, stream, *t, rb);
   } else if (phase == 2) {
     if (t->train && (!t->bn_p[0].stats || !t->bn_p[1].stats || !t->bn_c.stats)) return CG_EARG;
-    const int tps = (P + CG_TAIL_PT - 1) / CG_TAIL_PT, total = t->B * tps;
-    const int per = (total + 511) / 512, nwg = (total + per - 1) / per;
+    const CgTailRanges rg = cg_tail_ranges(t->B, P, CG_TAIL_PT);
+    const int tps = rg.tps, total = rg.total, per = rg.per, nwg = rg.nwg;
     const size_t lds = cg_tail_gemm_lds(t->C, false);
     const int mt = (t->C + 15) / 16, nt2 = (2 * t->C + 15) / 16;
 #define CG_TAIL_F2_LAUNCH(M, N)                                                                                               \
@@ -1101,7 +1127,7 @@ extern "C" int cg_dstd_tail_bwd(const CgDstdTail* t, int phase, void* stream_) {
   hipStream_t stream = (hipStream_t)stream_;
   const int P = t->T * t->V, C = t->C;
   const int rb = cg_tail_rows(t->B, C, P);
-  const dim3 rows((unsigned)C, (unsigned)((t->B + rb - 1) / rb), 1);
+  const dim3 rows = cg_tail_row_grid(t->B, C, rb);
   if (phase == 1) {
     if (!t->dgate) return CG_EARG;
     hipLaunchKernelGGL(cg_tail_k1_kernel, rows, dim3(256), 0, stream, *t, rb);
@@ -1110,8 +1136,8 @@ extern "C" int cg_dstd_tail_bwd(const CgDstdTail* t, int phase, void* stream_) {
     hipLaunchKernelGGL(cg_tail_k2_kernel, rows, dim3(256), 0, stream, *t, rb);
   } else if (phase == 3) {
     if (!t->dpooled || !t->red_c || !t->gp[0] || !t->gp[1] || !t->red_p[0] || !t->red_p[1] || !t->dWc_ws || !t->dWc) return CG_EARG;
-    const int tps = (P + CG_TAIL_PT3 - 1) / CG_TAIL_PT3, total = t->B * tps;
-    const int per = (total + 511) / 512, nwg = (total + per - 1) / per;
+    const CgTailRanges rg = cg_tail_ranges(t->B, P, CG_TAIL_PT3);
+    const int tps = rg.tps, total = rg.total, per = rg.per, nwg = rg.nwg;
     const size_t lds = cg_tail_gemm_lds(C, true);
     const int mt = (C + 15) / 16, nt2 = (2 * C + 15) / 16;
 #define CG_TAIL_K3_LAUNCH(M, N)                                                                                               \

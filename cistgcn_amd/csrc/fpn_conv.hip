@@ -335,6 +335,19 @@ static size_t cg_fpn_lds_fwd(const CgFpnConv* t, const CgFpnGeom& g) { return ((
 static size_t cg_fpn_lds_dx(const CgFpnConv* t, const CgFpnGeom& g) { return ((size_t)t->O * g.IMG + (size_t)g.CM * g.KS2 + g.KP2 + g.PM) * 4; }
 static size_t cg_fpn_lds_dw(const CgFpnConv* t, const CgFpnGeom& g) { return ((size_t)t->C * g.IMG + (size_t)g.OM * (g.PM + 4) + g.KP + g.PM) * 4; }
 
+static int cg_fpn_dw_nwg(int B, const CgFpnGeom& g) { return (B + g.per - 1) / g.per; }
+// include/cistgcn_hip.h : host-only, samples per workgroup and workgroups per dilation of the weight-gradient kernel (no launch)
+extern "C" int cg_fpn_conv_geometry(int B, int C, int O, int H, int W, int* out) {
+  if (!out) return CG_EARG;
+  CgFpnConv t = {};
+  t.B = B; t.C = C; t.O = O; t.H = H; t.W = W; t.n = 1; t.dil[0] = 1;
+  CgFpnGeom g;
+  const int st = cg_fpn_geometry(&t, &g);
+  if (st != CG_OK) return st;
+  out[0] = g.per; out[1] = cg_fpn_dw_nwg(B, g);
+  return CG_OK;
+}
+
 // 1 when cg_fpn_conv_* takes the shape (else the caller uses the generic contraction)
 extern "C" int cg_fpn_conv_supported(int B, int C, int O, int H, int W) {
   CgFpnConv t = {};
@@ -384,7 +397,7 @@ extern "C" int cg_fpn_conv_bwd(const CgFpnConv* t, void* stream_) {
   if (lds > 160 * 1024) return CG_ESHAPE;
   hipError_t e = cg_lds_limit((const void*)cg_fpn_dw_kernel, lds);
   if (e != hipSuccess) return (int)e;
-  const int nwg = (t->B + a.g.per - 1) / a.g.per;
+  const int nwg = cg_fpn_dw_nwg(t->B, a.g);
   hipLaunchKernelGGL(cg_fpn_dw_kernel, dim3((unsigned)nwg, (unsigned)t->n), dim3(CG_FPN_THREADS), lds, stream, a);
   st = cg_launch_status();
   if (st != CG_OK) return st;

@@ -878,11 +878,12 @@ static CgAdjGeom cg_adj_geometry(int B, int Kc, int J) {
 }
 static int cg_adj_tile(int Kc) { const int KcM = cg_adj_kcm(Kc); return KcM > 32 ? 64 : KcM > 16 ? 128 : 256; }
 
+static int cg_adj_shape_ok(int B, int Kc, int J) { return B > 0 && Kc > 0 && J > 0 && Kc <= 64 && J <= 64; }
 static int cg_adj_check(const CgAdjTail* it, int n) {
   if (!it || n <= 0 || n > 2) return CG_EARG;
   for (int i = 0; i < n; ++i) {
     const CgAdjTail& t = it[i];
-    if (t.B <= 0 || t.Kc <= 0 || t.J <= 0 || t.Kc > 64 || t.J > 64 || (t.domain != 0 && t.domain != 1) || t.B != it[0].B) return CG_ESHAPE;
+    if (!cg_adj_shape_ok(t.B, t.Kc, t.J) || (t.domain != 0 && t.domain != 1) || t.B != it[0].B) return CG_ESHAPE;
     if (!t.s || !t.q || !t.W0 || !t.W4 || !t.alpha || !t.bn.gamma || !t.bn.beta || !t.bn.save || !t.e) return CG_EARG;
     if (t.train && t.drop_p > 0.f && !t.seed) return CG_EARG;
   }
@@ -915,6 +916,15 @@ extern "C" long long cg_map2adj_tail_ws_floats(int Kc) { return (long long)2 * C
 extern "C" long long cg_map2adj_tail_red_doubles(int Kc) { return (long long)CG_ADJ_REPLICAS * (2 * Kc + 1); }
 // floats of the per-chunk dS / dQ scratch `part` (no zeroing needed)
 extern "C" long long cg_map2adj_tail_part_floats(int B, int Kc, int J) { return (long long)B * cg_adj_chunks(B, Kc, J) * 2 * Kc * J; }
+
+// include/cistgcn_hip.h : host-only, what the launchers below choose for one tower (no launch)
+extern "C" int cg_map2adj_tail_geometry(int B, int Kc, int J, int* out) {
+  if (!out) return CG_EARG;
+  if (!cg_adj_shape_ok(B, Kc, J)) return CG_ESHAPE;
+  const CgAdjGeom g = cg_adj_geometry(B, Kc, J);
+  out[0] = g.PT; out[1] = g.ntiles; out[2] = g.tpw; out[3] = g.nch;
+  return CG_OK;
+}
 
 // include/cistgcn_hip.h : cg_map2adj_tail_fwd (phases 1, 2) / cg_map2adj_tail_bwd (phases 1, 2)
 extern "C" int cg_map2adj_tail_fwd(const CgAdjTail* items, int n, int phase, void* stream_) {

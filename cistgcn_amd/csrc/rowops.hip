@@ -42,6 +42,9 @@ static int cg_rows_per_block(const CgView4& v) {
   return (int)rb;
 }
 
+// include/cistgcn_hip.h : host-only, rows of one channel per workgroup of the row kernels for this view (no launch)
+extern "C" int cg_norm_act_rows_per_block(const CgView4* xv) { return xv ? cg_rows_per_block(*xv) : CG_EARG; }
+
 #define CG_ROW_MAX_BATCH 6     // problems per launch of the row kernels (kernel-argument budget)
 // Vector width of the contiguous-row paths: 4 (rows 16-byte aligned, P % 4 == 0) or 2 (rows 8-byte aligned, P % 2 == 0: the
 // (T,V) planes of the 25-joint skeletons, P = 1250, and the (25, 66) planes of the output block).  The width is uniform per

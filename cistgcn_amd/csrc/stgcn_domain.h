@@ -3,6 +3,11 @@
 #pragma once
 #include "cg_common.h"
 
+// workgroups of a launch that hands `per` consecutive tiles to each, and its grid (whole groups of eight workgroups, one per XCD:
+// the kernels return at once in the workgroups past the work)
+static inline long long cg_dom_nwg(long long total, int per) { return (total + per - 1) / per; }
+static inline unsigned cg_dom_grid(long long nwg) { return (unsigned)(((nwg + 7) / 8) * 8); }
+
 // geometry of the matrix-core kernels (see the header comment of stgcn_domain_mfma.hip)
 struct CgDomM {
   int B, Cin, Cout, T, V;

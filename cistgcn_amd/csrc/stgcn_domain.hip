@@ -595,6 +595,35 @@ static int cg_dom_geom(CgDomainGeom& g, int B, int Cin, int Cout, int T, int V, 
   return CG_OK;
 }
 
+// whether a launch tries the plane generation first (a shape its launcher refuses falls through to the older kernels): wide layers at
+// batch sizes that fill the chip with one workgroup per (sample, chunk of 16 output channels | 16 frames | 8 frames)
+static bool cg_dom_planes_first(int B, int Cin, int Cout, int T, int V, int domain, bool bwd) {
+  if (!bwd) return (Cin >= 16 || Cout >= 16) && (long long)B * ((Cout + 15) / 16) >= cg_dom_planes_min_wgs() && !(domain == 1 && (V & 1));
+  if (domain == 0) return Cin >= 16 && (long long)B * ((T + 15) / 16) >= cg_dom_planes_min_wgs();
+  return Cin >= 16 && (long long)B * ((T + 7) / 8) >= cg_dom_planes_min_wgs();
+}
+
+// include/cistgcn_hip.h : host-only, tiles per workgroup of the tile kernels (kind 0) / the matrix-core kernels (kind 1) (no launch)
+extern "C" int cg_stgcn_domain_geometry(int B, int Cin, int Cout, int T, int V, int domain, int bwd, int kind, int* out) {
+  if (!out || (domain != 0 && domain != 1) || (kind != 0 && kind != 1)) return CG_EARG;
+  long long total; int per, ntiles;
+  if (kind == 0) {
+    CgDomainGeom g;
+    const int st = cg_dom_geom(g, B, Cin, Cout, T, V, domain, bwd != 0);
+    if (st != CG_OK) return st;
+    ntiles = g.ntiles; total = (long long)B * g.ntiles; per = g.per;
+  } else {
+    CgDomM g;
+    const int st = cg_domm_geom(g, B, Cin, Cout, T, V, domain, bwd != 0);
+    if (st != CG_OK) return st;
+    ntiles = g.ntiles; total = g.total; per = g.per;
+  }
+  const long long nwg = cg_dom_nwg(total, per);
+  out[0] = ntiles; out[1] = (int)total; out[2] = per; out[3] = (int)nwg; out[4] = (int)cg_dom_grid(nwg);
+  out[5] = cg_dom_planes_first(B, Cin, Cout, T, V, domain, bwd != 0) ? 1 : 0;
+  return CG_OK;
+}
+
 extern "C" int cg_stgcn_domain_fwd(const float* x, const float* adj, const float* W, const float* bias, float* y, double* ystats,
                                    int B, int Cin, int Cout, int T, int V, int domain, void* stream_) {
   if (!x || !adj || !W || !y) return CG_EARG;
@@ -604,7 +633,7 @@ extern "C" int cg_stgcn_domain_fwd(const float* x, const float* adj, const float
   // wide layers, third generation: plane kernels (stgcn_domain_planes.hip) - whole plane rows in HBM, LDS as the transposer
   // (a grid of fewer than 256 workgroups - small batches - leaves most CUs idle: the tile kernels split a sample finer; the
   // time-domain variant for odd V reads its slabs one float per lane and measured no faster than the tile kernel)
-  if ((Cin >= 16 || Cout >= 16) && (long long)B * ((Cout + 15) / 16) >= cg_dom_planes_min_wgs() && !(domain == 1 && (V & 1))) {
+  if (cg_dom_planes_first(B, Cin, Cout, T, V, domain, false)) {
     st = cg_domp_fwd_launch(x, adj, W, bias, y, ystats, B, Cin, Cout, T, V, domain, (hipStream_t)stream_);
     if (st != CG_ESHAPE) return st;
   }
@@ -627,8 +656,8 @@ extern "C" int cg_stgcn_domain_fwd(const float* x, const float* adj, const float
     const long long per = total / 2048;
     g.per = (int)(per < 1 ? 1 : (per > 16 ? 16 : per));
     const size_t lds = cg_dom_mfma_lds_bytes(g);
-    const long long nwg = (total + g.per - 1) / g.per;
-    dim3 grid((unsigned)(((nwg + 7) / 8) * 8)), block(256);
+    const long long nwg = cg_dom_nwg(total, g.per);
+    dim3 grid(cg_dom_grid(nwg)), block(256);
     if (lds > 48 * 1024) {
       const void* fn = domain == 0 ? (const void*)cg_stgcn_domain_fwd_mfma_kernel<0> : (const void*)cg_stgcn_domain_fwd_mfma_kernel<1>;
       hipError_t e = cg_lds_limit(fn, lds);
@@ -639,8 +668,8 @@ extern "C" int cg_stgcn_domain_fwd(const float* x, const float* adj, const float
     return cg_launch_status();
   }
   const size_t lds = cg_dom_lds_bytes(g, false);
-  const long long nwg = ((long long)B * g.ntiles + g.per - 1) / g.per;
-  dim3 grid((unsigned)(((nwg + 7) / 8) * 8)), block(256);
+  const long long nwg = cg_dom_nwg((long long)B * g.ntiles, g.per);
+  dim3 grid(cg_dom_grid(nwg)), block(256);
   if (lds > 48 * 1024) {
     const void* fn = domain == 0 ? (const void*)cg_stgcn_domain_fwd_kernel<0> : (const void*)cg_stgcn_domain_fwd_kernel<1>;
     hipError_t e = cg_lds_limit(fn, lds);
@@ -672,7 +701,7 @@ extern "C" int cg_stgcn_domain_bwd(const float* x, const float* adj, const float
   // wide layers, space domain: plane backward (stgcn_domain_planes.hip)
   // (narrow inputs: the channel-mix-first order makes the graph products as wide as the OUTPUT, the tile kernels keep them
   // as wide as the input - 229 vs 279 us at 10 -> 64; small batches: as in the forward)
-  if (Cin >= 16 && domain == 0 && (long long)B * ((T + 15) / 16) >= cg_dom_planes_min_wgs()) {
+  if (domain == 0 && cg_dom_planes_first(B, Cin, Cout, T, V, domain, true)) {
     st = cg_domp_bwd_launch(x, adj, W, dy, dx, dadj, ws, CG_DOM_REPLICAS, B, Cin, Cout, T, V, domain, stream);
     if (st != CG_ESHAPE) {
       if (st != CG_OK) return st;
@@ -682,7 +711,7 @@ extern "C" int cg_stgcn_domain_bwd(const float* x, const float* adj, const float
     }
   }
   // wide layers, time domain: local plane backward (a chunk of frames per workgroup)
-  if (Cin >= 16 && domain == 1 && (long long)B * ((T + 7) / 8) >= cg_dom_planes_min_wgs()) {
+  if (domain == 1 && cg_dom_planes_first(B, Cin, Cout, T, V, domain, true)) {
     st = cg_domp_bwd_time_launch(x, adj, W, dy, dx, dadj, ws, CG_DOM_REPLICAS, B, Cin, Cout, T, V, stream);
     if (st != CG_ESHAPE) {
       if (st != CG_OK) return st;
@@ -703,8 +732,8 @@ extern "C" int cg_stgcn_domain_bwd(const float* x, const float* adj, const float
     }
   }
   const size_t lds = cg_dom_lds_bytes(g, true);
-  const long long nwg = ((long long)B * g.ntiles + g.per - 1) / g.per;
-  dim3 grid((unsigned)(((nwg + 7) / 8) * 8)), block(256);
+  const long long nwg = cg_dom_nwg((long long)B * g.ntiles, g.per);
+  dim3 grid(cg_dom_grid(nwg)), block(256);
   if (lds > 48 * 1024) {
     const void* fn = domain == 0 ? (const void*)cg_stgcn_domain_bwd_kernel<0> : (const void*)cg_stgcn_domain_bwd_kernel<1>;
     e = cg_lds_limit(fn, lds);

@@ -525,8 +525,8 @@ int cg_domm_bwd_launch(const float* x, const float* adj, const float* W, const f
   const int tilesW = (g.CoM / 16) * (g.CiM / 16);
   if (tilesW > 4 * 4) return CG_ESHAPE;          // 4 waves x 4 register tiles (Cin, Cout <= 64); wider layers: VALU kernel
   const size_t lds = cg_domm_lds_bytes(g, true);
-  const long long nwg = ((long long)g.total + g.per - 1) / g.per;
-  dim3 grid((unsigned)(((nwg + 7) / 8) * 8)), block(CG_DOMM_THREADS);
+  const long long nwg = cg_dom_nwg(g.total, g.per);
+  dim3 grid(cg_dom_grid(nwg)), block(CG_DOMM_THREADS);
   const int maxw = (tilesW + 3) / 4;
 #define CG_DOMM_LAUNCH(D, M)                                                                                              \
   do {                                                                                                                    \
@@ -551,8 +551,8 @@ int cg_domm_fwd_launch(const float* x, const float* adj, const float* W, const f
   int st = cg_domm_geom(g, B, Cin, Cout, T, V, domain, false);
   if (st != CG_OK) return st;
   const size_t lds = cg_domm_lds_bytes(g, false);
-  const long long nwg = ((long long)g.total + g.per - 1) / g.per;
-  dim3 grid((unsigned)(((nwg + 7) / 8) * 8)), block(CG_DOMM_THREADS);
+  const long long nwg = cg_dom_nwg(g.total, g.per);
+  dim3 grid(cg_dom_grid(nwg)), block(CG_DOMM_THREADS);
   const void* fn = domain == 0 ? (const void*)cg_stgcn_domain_fwd_mfma2_kernel<0> : (const void*)cg_stgcn_domain_fwd_mfma2_kernel<1>;
   hipError_t e = cg_lds_limit(fn, lds);
   if (e != hipSuccess) return (int)e;

@@ -496,6 +496,22 @@ static int cg_pwm_geometry(const CgPwMaps* t, bool bwd, CgPwGeom* g) {
   else if ((G_).NT == 4 && (G_).CT == 4) LAUNCH(4, 4)                                                                                \
   else LAUNCH(0, 0)
 
+static int cg_pwm_nwg(const CgPwGeom& g) { return (g.total + g.per - 1) / g.per; }
+
+// include/cistgcn_hip.h : host-only, what cg_pointwise_maps_fwd (bwd == 0) / _bwd choose for n maps of M[i] rows (no launch)
+extern "C" int cg_pointwise_maps_geometry(int B, int Cin, int P, int n, const int* M, int bwd, int* out) {
+  if (!out || !M || n <= 0 || n > CG_PWM_MAXN) return CG_EARG;
+  static const float dummy = 0.f;               // the geometry refuses null operands; it never reads them
+  CgPwMaps t = {};
+  t.B = B; t.Cin = Cin; t.P = P; t.n = n; t.x = &dummy;
+  for (int i = 0; i < n; ++i) { t.M[i] = M[i]; t.W[i] = &dummy; }
+  CgPwGeom g;
+  const int st = cg_pwm_geometry(&t, bwd != 0, &g);
+  if (st != CG_OK) return st;
+  out[0] = g.PT; out[1] = g.tps; out[2] = g.total; out[3] = g.per; out[4] = cg_pwm_nwg(g);
+  return CG_OK;
+}
+
 extern "C" long long cg_pointwise_maps_ws_floats(int Cin) { return (long long)CG_PWM_REPLICAS * CG_PWM_MAXROWS * (Cin + 1); }      // + the bias-gradient rows
 
 // include/cistgcn_hip.h : cg_pointwise_maps_fwd / cg_pointwise_maps_bwd
@@ -509,7 +525,7 @@ extern "C" int cg_pointwise_maps_fwd(const CgPwMaps* t, void* stream_) {
     if ((t->stats[i] != nullptr) != (t->stats[0] != nullptr)) return CG_EARG;
   }
   const size_t lds = ((size_t)a.g.CinM * a.g.PS + (size_t)a.g.MM * a.g.WS + 2 + (size_t)5 * a.g.MM) * sizeof(float);
-  const int nwg = (a.g.total + a.g.per - 1) / a.g.per;
+  const int nwg = cg_pwm_nwg(a.g);
 #define CG_PWM_FWD_LAUNCH(N, C)                                                                                         \
   {                                                                                                                    \
     hipError_t e = cg_lds_limit((const void*)cg_pwm_fwd_kernel<N, C>, lds);                                            \
@@ -533,7 +549,7 @@ extern "C" int cg_pointwise_maps_bwd(const CgPwMaps* t, void* stream_) {
     if (t->yraw[i] && (!t->bn_save[i] || !t->bn_gamma[i] || !t->bn_beta[i] || !t->prelu[i] || (t->bn_train && !t->bn_red[i]))) return CG_EARG;
   }
   const size_t lds = ((size_t)(a.g.MM + a.g.CinM) * a.g.PS + (size_t)a.g.MM * a.g.WS) * sizeof(float);
-  const int nwg = (a.g.total + a.g.per - 1) / a.g.per;
+  const int nwg = cg_pwm_nwg(a.g);
   hipStream_t stream = (hipStream_t)stream_;
 #define CG_PWM_BWD_LAUNCH(N, C)                                                                                         \
   {                                                                                                                    \

@@ -435,6 +435,36 @@ int cg_context_heads_fwd(const CgCtxHeads* t, void* stream);
 int cg_context_heads_bwd(const CgCtxHeads* t, void* stream);
 long long cg_context_heads_red_doubles(int C);
 
+/* ---- launch geometry queries (host only: no launch, no device access) ---------------------------------------------
+ * What the launchers above would choose for a shape, answered by the very functions they call.  Most kernels hand a workgroup a
+ * contiguous range of tiles / samples once the batch is large; tests ask here whether a shape really enters those loops.
+ * Return value as everywhere (0 ok, -1 bad argument, -2 unsupported shape); `out` receives the ints listed.
+ *   cg_map2adj_tail_geometry   one tower: out[4] = { positions per tile, tiles per sample, tiles per workgroup, workgroups per sample }
+ *                              (workgroup ch of a sample walks tiles ch * tpw .. min(tiles, (ch + 1) * tpw) - 1; towers sharing a launch get
+ *                              the larger workgroup count, the surplus workgroups return at once)
+ *   cg_dstd_tail_geometry      out[12] = { samples per workgroup of the row phases, row workgroups per channel,
+ *                              F2: positions per tile, tiles per sample, tiles, tiles per workgroup, workgroups,  K3: the same five }
+ *                              (tiles in sample-major order; workgroup i walks tiles i * per .. min(total, (i + 1) * per) - 1)
+ *   cg_pointwise_maps_geometry forward (bwd == 0) or backward: out[5] = { positions per tile, tiles per sample, tiles, tiles per workgroup,
+ *                              workgroups }, ranges as above
+ *   cg_collapse_geometry       backward of cg_collapse_rows (cols == 0) / cg_collapse_cols: out[3] = { K ranges, sample slices (grid y), samples
+ *                              per slice }
+ *   cg_fpn_conv_geometry       weight-gradient kernel: out[2] = { samples per workgroup, workgroups per dilation }
+ *   cg_stgcn_domain_geometry   kind 0: tile kernels, kind 1: matrix-core kernels (stgcn_domain_mfma.hip); forward (bwd == 0) or backward:
+ *                              out[6] = { tiles per sample, tiles, tiles per workgroup, workgroups, grid (workgroups rounded up to eight),
+ *                              1 when this launch tries the plane kernels first (then the five numbers before describe the fall-back) }
+ *   cg_block_input_geometry    out[3] = { planes (channels) per span, spans per sample, grid of the streaming kernels = B * spans } (a workgroup
+ *                              owns one span of one sample; the last span of a sample is short when C is no multiple of the span)
+ *   cg_norm_act_rows_per_block samples of one channel per workgroup of the row kernels (cg_norm_act_*, cg_chan_stats) for the view */
+int cg_map2adj_tail_geometry(int B, int Kc, int J, int* out);
+int cg_dstd_tail_geometry(int B, int C, int T, int V, int* out);
+int cg_pointwise_maps_geometry(int B, int Cin, int P, int n, const int* M, int bwd, int* out);
+int cg_collapse_geometry(int B, int C, int T, int V, int O, int cols, int* out);
+int cg_fpn_conv_geometry(int B, int C, int O, int H, int W, int* out);
+int cg_stgcn_domain_geometry(int B, int Cin, int Cout, int T, int V, int domain, int bwd, int kind, int* out);
+int cg_block_input_geometry(int B, int C, int T, int V, int* out);
+int cg_norm_act_rows_per_block(const CgView4* xv);
+
 /* ---- evaluation harness counterpart, environment/test.py:97-132 ----------------------
  * y[r,k,:] = x[r,idx[k],:] : `inputs[:, :, dim_used]` (32 -> 22 joints); x (rows,Jin,3), y (rows,Jout,3) contiguous */
 int cg_gather_joints(const float* x, float* y, const int32_t* idx, long long rows, int Jin, int Jout, void* stream);

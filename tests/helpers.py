@@ -62,6 +62,18 @@ def tol_ok(a, ref, rel=1e-4, floor=1.0):
     return err <= bound, err, bound
 
 
+# the comparison of this process that came closest to its bound since `reset_worst()`: [error / bound, what, error, bound]
+WORST = [0.0, "", 0.0, 0.0]
+
+
+def reset_worst():
+    WORST[:] = [0.0, "", 0.0, 0.0]
+
+
+def worst_line():
+    return "worst error / bound %.3f (%s: %.3e against %.3e)" % tuple(WORST)
+
+
 def assert_close(a, ref, what, rel=1e-4, floor=1.0):
     if isinstance(a, torch.Tensor):
         a = a.detach().cpu().numpy()
@@ -69,6 +81,8 @@ def assert_close(a, ref, what, rel=1e-4, floor=1.0):
         ref = ref.detach().cpu().numpy()
     ok, err, bound = tol_ok(a, ref, rel, floor)
     assert ok, "%s: max err %.3e > bound %.3e" % (what, err, bound)
+    if bound > 0.0 and err / bound > WORST[0]:
+        WORST[:] = [err / bound, what, err, bound]
 
 
 def grad_summary(g):

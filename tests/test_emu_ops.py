@@ -9,6 +9,8 @@ import pytest
 
 import checks
 import emu
+import helpers
+import loop_shapes as L
 
 
 @pytest.fixture(scope="module", autouse=True)
@@ -30,6 +32,82 @@ def test_operator(check):
         check("cpu", shapes=((3, 5, 4, 6, 3), (2, 10, 10, 22, 7), (4, 64, 5, 22, 8), (2, 6, 5, 5, 2), (3, 3, 22, 25, 4), (9, 32, 50, 25, 6)))
     else:
         check("cpu")
+
+
+def _loops_map2adj_tail():
+    L.assert_map2adj_tail_loops()
+    checks.check_map2adj_tail("cpu", shapes=L.MAP2ADJ_TAIL, replay=True)
+
+
+def _loops_dstd_tail():
+    L.assert_dstd_tail_loops()
+    checks.check_dstd_tail("cpu", shapes=L.DSTD_TAIL, replay=True)
+
+
+def _loops_tower_maps():
+    L.assert_pointwise_maps_loops(L.TOWER_MAPS, name="tower_maps")
+    checks.check_tower_maps("cpu", shapes=L.TOWER_MAPS, replay=True)
+
+
+def _loops_pointwise_maps():
+    L.assert_pointwise_maps_loops(L.POINTWISE_MAPS)
+    checks.check_pointwise_maps("cpu", shapes=L.POINTWISE_MAPS)
+
+
+def _loops_tower_collapse():
+    L.assert_pointwise_maps_loops(L.TOWER_COLLAPSE, deep=False, name="tower_collapse")
+    for (B, C, Ms, T, V, O) in L.TOWER_COLLAPSE:          # the collapsing convolutions of the deferred maps: M_i input channels each
+        L.assert_collapse_loops(((B, Ms[0], T, V, O),), cols=False, name="tower_collapse rows")
+        L.assert_collapse_loops(((B, Ms[1], T, V, O),), cols=True, name="tower_collapse cols")
+    checks.check_tower_collapse("cpu", shapes=L.TOWER_COLLAPSE, replay=True)
+
+
+def _loops_collapse_rows():
+    assert L.assert_collapse_loops(L.COLLAPSE_ROWS, cols=False), "collapse_rows: geometry gives no slice three samples"
+    checks.check_collapse_rows("cpu", shapes=L.COLLAPSE_ROWS)
+
+
+def _loops_collapse_cols():
+    assert L.assert_collapse_loops(L.COLLAPSE_COLS, cols=True), "collapse_cols: geometry gives no slice three samples"
+    checks.check_collapse_cols("cpu", shapes=L.COLLAPSE_COLS)
+
+
+def _loops_dilated_convs():
+    L.assert_dilated_convs_loops()
+    checks.check_dilated_convs("cpu", shapes=L.DILATED_CONVS)
+
+
+def _loops_block_input():
+    L.assert_block_input_loops()
+    checks.check_block_input("cpu", shapes=L.BLOCK_INPUT)
+
+
+def _loops_norm_act():
+    L.assert_norm_act_rows_loop()
+    checks.check_norm_act_rows("cpu", L.NORM_ACT_ROWS)
+
+
+@pytest.mark.parametrize("family", [_loops_map2adj_tail, _loops_dstd_tail, _loops_tower_maps, _loops_pointwise_maps, _loops_tower_collapse,
+                                    _loops_collapse_rows, _loops_collapse_cols, _loops_dilated_convs, _loops_block_input, _loops_norm_act], ids=lambda f: f.__name__[len("_loops_"):])
+def test_operator_loop_shapes(family):
+    """the operator checks on shapes whose launch geometry - asked from the library (tests/loop_shapes.py) - gives a workgroup several tiles or
+    samples, a short last range and ranges that cross samples; the default lists above stay at one tile per workgroup everywhere"""
+    helpers.reset_worst()
+    family()
+    print("%s: %s" % (family.__name__[len("_loops_"):], helpers.worst_line()))
+
+
+def test_stgcn_domain_loop_shapes():
+    """tile and matrix-core kernels of the fused ST-GCN stage with several tiles per workgroup (the plane generation pinned off: it would take
+    these batch sizes where it has the (T, V) family), and the plane kernels with a batch that does not fill its last group of eight samples"""
+    helpers.reset_worst()
+    L.assert_stgcn_domain_loops(L.STGCN_TILE, kind=0)
+    checks.check_stgcn_domain("cpu", shapes=L.STGCN_TILE, planes=None)
+    L.assert_stgcn_domain_loops(L.STGCN_MFMA, kind=1)
+    checks.check_stgcn_domain("cpu", shapes=L.STGCN_MFMA, planes=None)
+    assert all(s[0] % 8 != 0 and s[0] > 64 and s[4] % 4 != 0 and s[3] % 8 != 0 for s in L.STGCN_PLANES)
+    checks.check_stgcn_domain("cpu", shapes=L.STGCN_PLANES, planes=True)
+    print("stgcn_domain: %s" % helpers.worst_line())
 
 
 def test_stgcn_domain_small():

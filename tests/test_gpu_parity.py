@@ -7,6 +7,8 @@ import pytest
 import torch
 
 import checks
+import helpers
+import loop_shapes as L
 from helpers import CASES
 from oracle import cistgcn_ref as O
 
@@ -47,6 +49,169 @@ def test_stgcn_domain_plane_kernels():
     instantiated (T, V) family, against einsum on the CPU: forward, channel sums, dx, dAdj, dW, db"""
     checks.check_stgcn_domain("cuda", shapes=checks.PLANE_SHAPES, planes=True)
     checks.check_stgcn_domain("cuda", shapes=((300, 64, 64, 50, 22),))          # default switch, a full chip of workgroups
+
+
+# ---------------------------------------------------------------------------------------------
+# the multi-tile loops of the phase kernels at operator level (tests/loop_shapes.py)
+# ---------------------------------------------------------------------------------------------
+def _loops_map2adj_tail():
+    L.assert_map2adj_tail_loops()
+    checks.check_map2adj_tail("cuda", shapes=L.MAP2ADJ_TAIL, replay=True)
+
+
+def _loops_dstd_tail():
+    L.assert_dstd_tail_loops()
+    checks.check_dstd_tail("cuda", shapes=L.DSTD_TAIL, replay=True)
+
+
+def _loops_tower_maps():
+    L.assert_pointwise_maps_loops(L.TOWER_MAPS + L.TOWER_MAPS_WIDE, name="tower_maps")
+    checks.check_tower_maps("cuda", shapes=L.TOWER_MAPS + L.TOWER_MAPS_WIDE, replay=True)
+
+
+def _loops_pointwise_maps():
+    L.assert_pointwise_maps_loops(L.POINTWISE_MAPS + L.TOWER_MAPS_WIDE)
+    checks.check_pointwise_maps("cuda", shapes=L.POINTWISE_MAPS + L.TOWER_MAPS_WIDE)
+
+
+def _loops_tower_collapse():
+    L.assert_pointwise_maps_loops(L.TOWER_COLLAPSE, deep=False, name="tower_collapse")
+    for (B, C, Ms, T, V, O) in L.TOWER_COLLAPSE:          # the collapsing convolutions of the deferred maps: M_i input channels each
+        L.assert_collapse_loops(((B, Ms[0], T, V, O),), cols=False, name="tower_collapse rows")
+        L.assert_collapse_loops(((B, Ms[1], T, V, O),), cols=True, name="tower_collapse cols")
+    checks.check_tower_collapse("cuda", shapes=L.TOWER_COLLAPSE, replay=True)
+
+
+def _loops_collapse_rows():
+    assert L.assert_collapse_loops(L.COLLAPSE_ROWS, cols=False), "collapse_rows: geometry gives no slice three samples"
+    checks.check_collapse_rows("cuda", shapes=L.COLLAPSE_ROWS)
+
+
+def _loops_collapse_cols():
+    assert L.assert_collapse_loops(L.COLLAPSE_COLS, cols=True), "collapse_cols: geometry gives no slice three samples"
+    checks.check_collapse_cols("cuda", shapes=L.COLLAPSE_COLS)
+
+
+def _loops_dilated_convs():
+    L.assert_dilated_convs_loops()
+    checks.check_dilated_convs("cuda", shapes=L.DILATED_CONVS)
+
+
+def _loops_block_input():
+    L.assert_block_input_loops()
+    checks.check_block_input("cuda", shapes=L.BLOCK_INPUT)
+
+
+def _loops_norm_act():
+    L.assert_norm_act_rows_loop()
+    checks.check_norm_act_rows("cuda", L.NORM_ACT_ROWS)
+
+
+def _loops_stgcn_domain():
+    L.assert_stgcn_domain_loops(L.STGCN_TILE, kind=0)
+    checks.check_stgcn_domain("cuda", shapes=L.STGCN_TILE, planes=None)
+    L.assert_stgcn_domain_loops(L.STGCN_MFMA, kind=1)
+    checks.check_stgcn_domain("cuda", shapes=L.STGCN_MFMA, planes=None)
+    assert all(s[0] % 8 != 0 and s[0] > 64 and s[4] % 4 != 0 and s[3] % 8 != 0 for s in L.STGCN_PLANES)
+    checks.check_stgcn_domain("cuda", shapes=L.STGCN_PLANES, planes=True)
+
+
+@pytest.mark.timeout(600)
+@pytest.mark.parametrize("family", [_loops_map2adj_tail, _loops_dstd_tail, _loops_tower_maps, _loops_pointwise_maps, _loops_tower_collapse,
+                                    _loops_collapse_rows, _loops_collapse_cols, _loops_dilated_convs, _loops_block_input, _loops_norm_act, _loops_stgcn_domain],
+                         ids=lambda f: f.__name__[len("_loops_"):])
+def test_operator_loop_shapes(family):
+    """the operator checks on the shape lists of tests/loop_shapes.py: the launch geometry, asked from the library, gives a workgroup several
+    tiles or samples, a short last range and ranges that cross samples - asserted before any number is compared"""
+    helpers.reset_worst()
+    family()
+    print("%s: %s" % (family.__name__[len("_loops_"):], helpers.worst_line()))
+
+
+# (C, T, V, B) of the layers the benchmark runs (BASELINE configs[2] and configs[4]) at odd batch sizes on both sides of the ones the model
+# tests use (256, 128)
+LAYER_SHAPES = [(64, 50, 22, 255), (64, 50, 22, 257), (32, 50, 25, 129)]
+
+
+def _layer_cases(C, T, V, B):
+    """family -> (check, its arguments, the C entry points that must run)"""
+    M = (C // 2,) * 4                   # the four Map2Adj towers of a block: cin // 2 channels each
+    return {
+        "dstd_tail": (checks.check_dstd_tail, dict(replay=True, shapes=((B, C, T, V),)), ("cg_dstd_tail_fwd", "cg_dstd_tail_bwd")),
+        "map2adj_tail": (checks.check_map2adj_tail, dict(replay=True, shapes=((B, T, V),)), ("cg_map2adj_tail_fwd", "cg_map2adj_tail_bwd")),
+        "tower_maps": (checks.check_tower_maps, dict(replay=True, shapes=((B, C, M, T, V),)), ("cg_pointwise_maps_fwd", "cg_pointwise_maps_bwd", "cg_norm_act_bwd_reduce_many")),
+        "pointwise_maps": (checks.check_pointwise_maps, dict(shapes=((B, C, M, T, V),)), ("cg_pointwise_maps_fwd", "cg_pointwise_maps_bwd")),
+        "tower_collapse": (checks.check_tower_collapse, dict(replay=True, shapes=((B, C, M, T, V, C // 2),)),
+                           ("cg_pointwise_maps_fwd", "cg_collapse_rows_fwd", "cg_collapse_cols_fwd", "cg_collapse_rows_bwd", "cg_collapse_cols_bwd", "cg_pointwise_maps_bwd")),
+        "collapse_rows": (checks.check_collapse_rows, dict(shapes=((B, C // 2, T, V, C // 2),)), ("cg_collapse_rows_fwd", "cg_collapse_rows_bwd")),
+        "collapse_cols": (checks.check_collapse_cols, dict(shapes=((B, C // 2, T, V, C // 2),)), ("cg_collapse_cols_fwd", "cg_collapse_cols_bwd")),
+        # the time extrapolator sees (batch, frames, 10 lifted channels, joints): T -> 25 frames, then 25 -> 25
+        "dilated_convs": (checks.check_dilated_convs, dict(shapes=((B, T, 25, 10, V), (B, 25, 25, 10, V))), ("cg_fpn_conv_fwd", "cg_fpn_conv_bwd")),
+        "stgcn_domain": (checks.check_stgcn_domain, dict(shapes=((B, C, C, T, V),)), ("cg_stgcn_domain_fwd", "cg_stgcn_domain_bwd")),
+        "norm_act": (checks.check_norm_act_rows, dict(shapes=((B, C, T, V),)), ("cg_norm_act_fwd_many", "cg_norm_act_bwd_many")),
+        "block_input": (checks.check_block_input, dict(shapes=((B, C, T, V, 8),)), ("cg_block_input_fwd", "cg_block_input_bwd")),
+    }
+
+
+@pytest.mark.timeout(900)
+@pytest.mark.parametrize("family", sorted(_layer_cases(64, 50, 22, 257)))
+@pytest.mark.parametrize("cfg", LAYER_SHAPES, ids=str)
+def test_operator_at_layer_shapes(cfg, family):
+    """every operator family at the layer shapes the benchmark runs, odd batch sizes, against the reference its check uses at the default
+    shapes, at the same bounds: fp64 stock PyTorch on the CPU for dstd_tail, map2adj_tail, tower_maps, tower_collapse, block_input; fp32
+    stock PyTorch on the CPU for norm_act, dilated_convs, stgcn_domain; the generic contraction on the device for pointwise_maps,
+    collapse_rows and collapse_cols (their kernels meet fp64 at these shapes inside tower_maps / tower_collapse).  The entry points that
+    must have run are counted.  These tensors have up to 18 million elements: the references take the PReLU branches of the HIP run and
+    the few elements whose backward took the other branch are accounted for one by one (checks.BranchLog)."""
+    check, kwargs, entries = _layer_cases(*cfg)[family]
+    C, T, V, B = cfg
+    if family == "dstd_tail":
+        print("geometry %s" % (L.dstd_tail_geometry(B, C, T, V),))
+    elif family == "map2adj_tail":
+        L.assert_map2adj_tail_loops(((B, T, V),), whole_list=False)
+    helpers.reset_worst()
+    with L.counted_calls() as launches:
+        check("cuda", **kwargs)
+    for entry in entries:
+        assert launches.get(entry, 0) > 0, "%s %s: %s did not run (%s)" % (family, cfg, entry, launches)
+    print("%s %s: %s; launches %s" % (family, cfg, helpers.worst_line(), {k: launches[k] for k in entries}))
+
+
+@pytest.mark.timeout(600)
+@pytest.mark.parametrize("B", [63, 64, 65])
+def test_dilated_convs_across_the_batch_threshold(B):
+    """ops.dilated_convs through its own dispatch (ops._FPN_MIN_BATCH = 64, not patched): the generic contraction below the threshold,
+    the whole-sample kernels of csrc/fpn_conv.hip from it on - same numbers on both sides"""
+    from cistgcn_amd import ops
+    assert ops._FPN_MIN_BATCH == 64
+    helpers.reset_worst()
+    with L.counted_calls() as launches:
+        checks._check_dilated_convs("cuda", B, 25, 25, 10, 22)
+    fpn = launches.get("cg_fpn_conv_fwd", 0), launches.get("cg_fpn_conv_bwd", 0)
+    if B < 64:
+        assert fpn == (0, 0) and launches.get("cg_contract_many", 0) > 0, "B = %d ran %s" % (B, launches)
+    else:
+        assert fpn[0] > 0 and fpn[1] > 0, "B = %d ran %s" % (B, launches)
+    print("dilated_convs B=%d: %s; launches %s" % (B, helpers.worst_line(), launches))
+
+
+@pytest.mark.timeout(600)
+@pytest.mark.parametrize("B", [36, 37, 63, 64, 65])
+def test_stgcn_domain_across_the_plane_switch(B):
+    """the fused ST-GCN stage at 64 -> 64 channels, (T, V) = (50, 22), with the kernel-generation switch left at its default of 256
+    workgroups: the forward and the space-domain backward change generation between B = 63 and 64 (4 chunks per sample), the time-domain
+    backward between B = 36 and 37 (7 chunks of frames per sample).  Both generations compute the same function through the same entry
+    points, so the side each launch is on is asked from the library (cg_stgcn_domain_geometry, answered by the predicate the launchers use)."""
+    from cistgcn_amd import _lib
+    assert _lib.lib().cg_stgcn_domain_planes_min_workgroups(-1) == 256
+    first = {(dom, bwd): L._geom("cg_stgcn_domain_geometry", B, 64, 64, 50, 22, dom, bwd, 0, n=6)[5] for dom in (0, 1) for bwd in (0, 1)}
+    assert first == {(0, 0): int(B >= 64), (1, 0): int(B >= 64), (0, 1): int(B >= 64), (1, 1): int(B >= 37)}, "B = %d: plane kernels first in %s" % (B, first)
+    helpers.reset_worst()
+    with L.counted_calls() as launches:
+        checks.check_stgcn_domain("cuda", shapes=((B, 64, 64, 50, 22),))
+    assert launches.get("cg_stgcn_domain_fwd", 0) > 0 and launches.get("cg_stgcn_domain_bwd", 0) > 0, launches
+    assert _lib.lib().cg_stgcn_domain_planes_min_workgroups(-1) == 256
+    print("stgcn_domain B=%d: %s" % (B, helpers.worst_line()))
 
 
 @pytest.mark.parametrize("name", CASES)
@@ -198,6 +363,20 @@ def test_full_size_train_matches_oracle(dropout):
     if dropout > 0.0:
         assert r["dropout_sites"] == 91
     print("full-size train parity (dropout %.1f): %s" % (dropout, r))
+
+
+@pytest.mark.timeout(1500)
+@pytest.mark.parametrize("fp64", [_host_can_run_the_fp64_oracle_at_full_size()], ids=lambda v: "fp64-oracle" if v else "fp32-oracle(host-memory-below-90GB)")
+def test_amass25_shape_at_the_benched_batch_matches_oracle(fp64):
+    """BASELINE configs[4]'s per-GPU workload (CISTGCN-32, T = 50, V = 25) at the batch size the benchmark times as `other_workloads`
+    (256), train mode with dropout 0.1, against the oracle on the masks and PReLU branches of the HIP run: the V = 25 plane kernels take
+    several tiles per workgroup only at this size (test_amass25_shape_at_size_matches_oracle stops at B = 64).  Same arguments as that
+    test; the oracle's activations are about a third of the C = 64 full-size case, the host-memory probe is the same (the test id names
+    the oracle's precision)."""
+    r = checks.check_model_branch_replay("cuda", 32, 50, 25, 256, "train", grad_floor=0.25, max_flip_frac=1e-4, rel_bound=REL_BOUND, oracle_fp64=fp64,
+                                         attr_rel=2e-4, rel_min_size=1, dropout=0.1)
+    assert r["dropout_sites"] == 91
+    print("configs[4] shape at B=256 (%s oracle): %s" % ("fp64" if fp64 else "fp32", r))
 
 
 @pytest.mark.timeout(900)
