@@ -155,6 +155,14 @@ class CtxHeads(ctypes.Structure):
                 ("dw", c_void_p * 2), ("dgamma", c_void_p * 2), ("dbeta", c_void_p * 2), ("dalpha", c_void_p * 2)]
 
 
+class AttackStep(ctypes.Structure):
+    _fields_ = [("B", c_int), ("T", c_int), ("V", c_int), ("mode", c_int), ("iterations", c_int), ("patience", c_int),
+                ("epsilon", c_float), ("mu", c_float),
+                ("x0", c_void_p), ("x", c_void_p), ("grad", c_void_p), ("g", c_void_p), ("mask", c_void_p), ("loss", c_void_p),
+                ("best", c_void_p), ("stall", c_void_p), ("active", c_void_p), ("w", c_void_p), ("queries", c_void_p), ("n_active", c_void_p),
+                ("steps", c_void_p), ("frozen_at", c_void_p)]
+
+
 P = c_void_p
 LL = c_longlong
 _SIGNATURES = {
@@ -236,6 +244,10 @@ _SIGNATURES = {
     "cg_stgcn_domain_geometry": [c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, POINTER(c_int)],
     "cg_block_input_geometry": [c_int, c_int, c_int, c_int, POINTER(c_int)],
     "cg_norm_act_rows_per_block": [POINTER(View4)],
+    "cg_mpjpe_sample_fwd": [P, P, P, c_int, c_int, P],
+    "cg_mpjpe_sample_bwd": [P, P, P, P, c_int, c_int, P],
+    "cg_attack_step": [POINTER(AttackStep), P],
+    "cg_attack_step_max_floats": [],
     "cg_adam_flat": [P, P, P, P, LL, c_float, c_float, c_float, c_float, c_float, c_float, c_float, LL, P],
 }
 EXPORTS = tuple(sorted(_SIGNATURES))

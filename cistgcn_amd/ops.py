@@ -1384,6 +1384,107 @@ def mpjpe(pred, target):
     return _Mpjpe.apply(pred, target)
 
 
+class _MpjpePerSample(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, pred, target):
+        _chk(pred), _chk(target)
+        if pred.dim() != 4 or pred.shape != target.shape or pred.shape[-1] != 3:
+            raise AssertionError("mpjpe_per_sample: predicted %s vs target %s, expected (B,To,V,3)" % (tuple(pred.shape), tuple(target.shape)))
+        pred = pred if pred.is_contiguous() else _copy(pred)
+        target = target if target.is_contiguous() else _copy(target)
+        B = pred.shape[0]
+        loss = torch.empty(B, dtype=torch.float32, device=pred.device)
+        _lib.call("cg_mpjpe_sample_fwd", _ptr(pred), _ptr(target), _ptr(loss), B, pred.numel() // (3 * B), _stream(pred))
+        ctx.save_for_backward(pred, target)
+        return loss
+
+    @staticmethod
+    def backward(ctx, w):
+        pred, target = ctx.saved_tensors
+        B = pred.shape[0]
+        _chk(w, "upstream gradient")
+        if w.numel() != B:
+            raise ValueError("mpjpe_per_sample: upstream gradient of %d elements for %d samples" % (w.numel(), B))
+        w = w if w.is_contiguous() else w.contiguous()
+        d = torch.empty_like(pred)
+        _lib.call("cg_mpjpe_sample_bwd", _ptr(pred), _ptr(target), _ptr(w), _ptr(d), B, pred.numel() // (3 * B), _stream(pred))
+        return d, None
+
+
+def mpjpe_per_sample(pred, target):
+    """One mean per-joint position error per sample: `losses.mpjpe(pred, target, reduce_axis=[1, 2])` (losses/losses.py:50-61 as the
+    attacks call it, adversarial_attacks.py:175-178).  (B,To,V,3) x 2 -> (B,).  No atomics: two calls give the same bits.  The backward
+    takes a (B,) upstream gradient, which the attack loop keeps on the device (1/B for a sample that is still optimised, 0 else)."""
+    return _MpjpePerSample.apply(pred, target)
+
+
+ATTACK_MODES = {"fgsm": 0, "ifgsm": 1, "mifgsm": 2}
+
+
+class AttackState:
+    """Device-resident bookkeeping of an iterative attack (adversarial_attacks.py:512-515, :529-538): per sample the highest loss so
+    far (`best`), the iterations without improvement (`stall`), whether it is still optimised (`active`), the upstream weight of its
+    loss in the next backward (`w`: 1/B or 0) and the model calls spent on it (`queries`); `n_active` counts the active samples."""
+
+    def __init__(self, batch, device):
+        self.B = int(batch)
+        self.best = torch.empty(self.B, dtype=torch.float32, device=device)
+        self.stall = torch.empty(self.B, dtype=torch.int32, device=device)
+        self.active = torch.empty(self.B, dtype=torch.int32, device=device)
+        self.w = torch.empty(self.B, dtype=torch.float32, device=device)
+        self.queries = torch.empty(self.B, dtype=torch.int32, device=device)
+        self.n_active = torch.empty(1, dtype=torch.int32, device=device)
+        self.steps = torch.empty(self.B, dtype=torch.int32, device=device)          # steps taken, counted per sample by its workgroup
+        self.frozen_at = torch.empty(self.B, dtype=torch.int32, device=device)      # step at whose end the sample froze
+        self.reset()
+
+    def reset(self):
+        """Re-arm for the next batch (in place: a captured iteration keeps reading the same buffers)."""
+        with torch.no_grad():
+            self.best.zero_(); self.stall.zero_(); self.queries.zero_(); self.steps.zero_()
+            self.frozen_at.fill_(2 ** 31 - 1)
+            self.active.fill_(1); self.n_active.fill_(self.B)
+            self.w.copy_((torch.ones(self.B, dtype=torch.float32) / self.B).to(self.w.device))
+        return self
+
+
+def attack_step(mode, x, x0, grad, epsilon, iterations=1, mu=0.0, mask=None, g=None, loss=None, state=None, patience=5):
+    """One step of FGSM / I-FGSM / MI-FGSM on the whole batch in one launch (include/cistgcn_hip.h, cg_attack_step): `x` (B,T,V,3)
+    holds the current iterate and is overwritten by the adversarial one; `x0` is the clean input, `grad` the gradient of the weighted
+    per-sample losses at `x`.  `mask` (T,V) of 0/1 restricts the joints and frames that move, `g` is MI-FGSM's momentum (updated in
+    place), `loss` (B,) and `state` (`AttackState`, updated in place) drive the early stop of the iterative modes.  No autograd, no
+    host synchronisation."""
+    m = ATTACK_MODES.get(mode)
+    if m is None:
+        raise ValueError("attack_step: unknown mode %r (expected one of %s)" % (mode, sorted(ATTACK_MODES)))
+    for t, name in ((x, "x"), (x0, "x0"), (grad, "grad")):
+        _chk(t, name)
+        if t.dim() != 4 or t.shape != x.shape or t.shape[-1] != 3 or not t.is_contiguous():
+            raise ValueError("attack_step: %s must be a contiguous (B,T,V,3) tensor like x, got %s" % (name, tuple(t.shape)))
+    B, T, V, _ = x.shape
+    a = _lib.AttackStep()
+    a.B, a.T, a.V, a.mode, a.iterations, a.patience = B, T, V, m, int(iterations), int(patience)
+    a.epsilon, a.mu = float(epsilon), float(mu)
+    a.x0, a.x, a.grad = _ptr(x0), _ptr(x), _ptr(grad)
+    if mask is not None:
+        _chk(mask, "mask")
+        if tuple(mask.shape) != (T, V) or not mask.is_contiguous():
+            raise ValueError("attack_step: mask must be a contiguous (T,V) tensor, got %s" % (tuple(mask.shape),))
+        a.mask = _ptr(mask)
+    if m == 2:
+        if g is None or g.shape != x.shape or g.dtype != torch.float32 or not g.is_contiguous():
+            raise ValueError("attack_step: MI-FGSM needs its momentum g, float32 and shaped like x")
+        a.g = _ptr(g)
+    if m != 0:
+        if loss is None or state is None or loss.numel() != B or state.B != B or loss.dtype != torch.float32 or not loss.is_contiguous():
+            raise ValueError("attack_step: the iterative modes need loss (B,) and an AttackState of the same batch")
+        a.loss, a.best, a.stall, a.active = _ptr(loss), _ptr(state.best), _ptr(state.stall), _ptr(state.active)
+        a.w, a.queries, a.n_active = _ptr(state.w), _ptr(state.queries), _ptr(state.n_active)
+        a.steps, a.frozen_at = _ptr(state.steps), _ptr(state.frozen_at)
+    _lib.call("cg_attack_step", ctypes.byref(a), _stream(x))
+    return x
+
+
 # ----------------------------------------------------------------------------------------------
 # fused ST-GCN stage
 # ----------------------------------------------------------------------------------------------

@@ -391,6 +391,84 @@ class GraphedForward:
         return self.pred
 
 
+class GraphedAttack:
+    """One iteration of an iterative input attack (`environment.attacks.IFGSM` / `MIFGSM`) as a HIP graph: eval-mode forward,
+    `ops.mpjpe_per_sample`, backward to the input with the device-resident per-sample weights as root gradient, `ops.attack_step`.
+    The batch keeps its shape whatever samples are frozen (see environment/attacks.py), the bookkeeping lives in device memory and the
+    step kernel writes the weights of the next backward, so `run()` is `iterations` graph launches without a host round trip.
+
+    Same rules as `GraphedStep`: static input buffers (`x0`, `x_i`, `target`), warm-up on a side stream, buffers and the dropout seed
+    restored, the interpretation attributes dropped, and `step()` raises if a parameter has moved since the capture.  The model is
+    captured in eval mode and gets its mode back; replays do not depend on the mode the model is in later."""
+
+    def __init__(self, model, x, target, attack, warmup=2):
+        from .environment import attacks
+        if attack.mode not in ("ifgsm", "mifgsm"):
+            raise ValueError("GraphedAttack captures an iterative attack (IFGSM / MIFGSM), got %s" % type(attack).__name__)
+        self.model, self.attack = model, attack
+        self.x0, self.target = attacks._Attack._prepare(x, target)
+        self.x0, self.target = self.x0.clone(), self.target.clone()
+        self.x_i = self.x0.clone().requires_grad_(True)
+        self.state = ops.AttackState(self.x0.shape[0], self.x0.device)
+        self.mask, self.g = attack.mask(self.x0), attack.new_momentum(self.x0)
+        self.params = [p for p in model.parameters()]
+        was_training = model.training
+        model.eval()
+        snap = _buffers_snapshot(model, self.x0.device)
+        try:
+            side = torch.cuda.Stream()
+            side.wait_stream(torch.cuda.current_stream())
+            with torch.cuda.stream(side):
+                for _ in range(warmup):
+                    self._iteration()
+            torch.cuda.current_stream().wait_stream(side)
+            torch.cuda.synchronize()
+            _drop_graph_attributes(model)
+            self.graph = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(self.graph):
+                self._iteration()
+            _drop_graph_attributes(model)
+        finally:
+            model.train(was_training)
+        _buffers_restore(model, self.x0.device, snap)
+        self._param_ptrs = [p.data_ptr() for p in self.params]
+        self.reset()
+
+    def _iteration(self):
+        from .environment.attacks import loss_and_input_grad
+        loss, grad = loss_and_input_grad(self.model, self.x_i, self.target, self.state.w)
+        self.attack.step(self.x_i.detach(), self.x0, grad, loss, self.state, self.mask, self.g)
+
+    def reset(self, x=None, target=None):
+        """Re-arm for the next batch (same shapes) without re-capturing: new clean input / target if given, the iterate back at the
+        clean input, momentum and bookkeeping cleared."""
+        with torch.no_grad():
+            if x is not None:
+                self.x0.copy_(x)
+            if target is not None:
+                self.target.copy_(target)
+            self.x_i.detach().copy_(self.x0)
+            if self.g is not None:
+                _lib.call("cg_zero", ops._ptr(self.g), self.g.numel() * 4, ops._stream(self.g))
+        self.state.reset()
+        return self
+
+    def step(self):
+        """One replay = one attack iteration on the static buffers."""
+        if any(p.data_ptr() != q for p, q in zip(self.params, self._param_ptrs)):
+            raise RuntimeError("the parameters moved after this attack was captured (FlatAdam / model.to() / load with assign): "
+                               "the HIP graph still reads the old buffers")
+        self.graph.replay()
+
+    def run(self):
+        """`iterations` replays from the current state; the same dictionary as `attack.apply` (views of the static buffers: copy what
+        has to outlive the next `reset`).  An iteration that starts with every sample frozen changes nothing, as the reference has left
+        its loop by then, so no early exit (and no look at the device) is needed."""
+        for _ in range(self.attack.iterations):
+            self.step()
+        return {"adv_inputs": self.x_i.detach(), "queries": self.state.queries, "loss": self.state.best}
+
+
 class EagerStep(_StepBase):
     """Same step without graph capture (debugging / first-iteration reference)."""
 

@@ -506,6 +506,39 @@ int cg_multi_copy(void* ptrs, const long long* flat_off, const int32_t* chunk_te
  * p[i] *= s: the 1/world of the gradient mean when no optimizer kernel follows to absorb it (cg_adam_flat's grad_scale). */
 int cg_scale(float* p, long long n, float s, void* stream);
 
+/* ---- input-space attacks (csrc/attack.hip) ----------------------------------------------------------
+ * environment/adversarial_attacks.py of the reference.  An attack iteration is: eval-mode forward, one loss per sample
+ * (`losses.mpjpe(..., reduce_axis=[1, 2])`, :175-178 with losses/losses.py:50-61), backward to the input poses, one step.
+ * The reference re-slices the batch to the samples that are still optimised (`[op_mask]`, :518-521); here the batch keeps its
+ * shape and a frozen sample has upstream weight 0, which gives the same signs and the same L1-normalised directions.
+ * Per-sample MPJPE: pred / target contiguous (B,N,3), N = To*V; loss (B,), no atomics (bit-reproducible);
+ * backward dpred[b] = w[b] * (pred - target) / (N * ||pred - target||), 0 where the norm is 0. */
+int cg_mpjpe_sample_fwd(const float* pred, const float* tgt, float* loss, int B, int N, void* stream);
+int cg_mpjpe_sample_bwd(const float* pred, const float* tgt, const float* w, float* dpred, int B, int N, void* stream);
+/* One attack step, one workgroup per sample, everything of an iteration except the model call:
+ *   mode 0 FGSM   (compute_gradient :401-417):  x = x + mask * eps_b * sign(grad); no reset, no bookkeeping
+ *   mode 1 I-FGSM (:469-496):                   x = x + mask * (eps_b / iterations) * sign(grad)
+ *   mode 2 MI-FGSM (:581-610):                  g = mu * g + grad / ||grad||_1 (per sample); x = x + mask * (eps_b / iterations) * sign(g)
+ * with eps_b = epsilon * |max y - min y| of the CURRENT iterate (`_get_bound_per_sample`, typ_eval "len_y", :348-350).  Only samples
+ * that are active at the start of the step move; then EVERY sample whose max |x - x0| exceeds eps_b has the elements outside
+ * [x0 - eps_b, x0 + eps_b) reset to x0 (:486-493).  Bookkeeping of the active samples with loss[b] of this iteration (:517,
+ * :529-538): queries += 1; best = loss if loss > best, else stall += 1; a sample with stall >= patience (5 in the reference) is
+ * frozen: active = 0, w = 0, n_active -= 1; w = 1/B otherwise (the root gradient of the next backward).
+ * A step that starts with every sample frozen changes nothing: the reference has left its loop by then (:540-541).  steps[b]
+ * counts the steps of sample b and frozen_at[b] (INT_MAX while active) is the step at whose end it froze, so that every workgroup
+ * can tell "active at the start of this step" apart from "frozen by another workgroup of this launch".
+ * Deviation: an active sample whose gradient is all zero keeps g and x in MI-FGSM (the reference writes NaN there).
+ * x is updated in place (x_i in, x_adv out); mask (T,V) of 0/1 or NULL; g only for mode 2; the bookkeeping pointers only for
+ * modes 1 and 2.  T*V*3 <= cg_attack_step_max_floats() (the sample, x0 and the direction stay in LDS). */
+typedef struct CgAttackStep {
+  int B, T, V, mode, iterations, patience;
+  float epsilon, mu;
+  const float* x0; float* x; const float* grad; float* g; const float* mask; const float* loss;
+  float* best; int* stall; int* active; float* w; int* queries; int* n_active; int* steps; int* frozen_at;
+} CgAttackStep;
+int cg_attack_step(const CgAttackStep* a, void* stream);
+long long cg_attack_step_max_floats(void);
+
 #ifdef __cplusplus
 }
 #endif
