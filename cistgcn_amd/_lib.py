@@ -163,6 +163,12 @@ class AttackStep(ctypes.Structure):
                 ("steps", c_void_p), ("frozen_at", c_void_p)]
 
 
+class EvalMetricsArgs(ctypes.Structure):      # CgEvalMetrics
+    _fields_ = [("B", c_int), ("To", c_int), ("J", c_int), ("Nb", c_int), ("frames", c_int), ("pad", c_int),
+                ("pred", c_void_p), ("target", c_void_p), ("speeds", c_void_p), ("bones", c_void_p),
+                ("out", c_void_p * 9), ("ws", c_void_p)]
+
+
 P = c_void_p
 LL = c_longlong
 _SIGNATURES = {
@@ -248,6 +254,8 @@ _SIGNATURES = {
     "cg_mpjpe_sample_bwd": [P, P, P, P, c_int, c_int, P],
     "cg_attack_step": [POINTER(AttackStep), P],
     "cg_attack_step_max_floats": [],
+    "cg_eval_metrics": [POINTER(EvalMetricsArgs), P],
+    "cg_eval_metrics_ws_doubles": [c_int, c_int, c_int],
     "cg_adam_flat": [P, P, P, P, LL, c_float, c_float, c_float, c_float, c_float, c_float, c_float, LL, P],
 }
 EXPORTS = tuple(sorted(_SIGNATURES))

@@ -1,0 +1,328 @@
+// Evaluation metrics of a batch (environment/test.py::Metrics.compute :65-94 of the reference with losses/losses.py: mpjpe :50-61,
+// weighted_mpjpe :64-76, pa_mpjpe :79-144, n_mpjpe :147-160, mean_velocity_error :163-177, bone_length_error :199-215,
+// weighted_bone_length_error :218-238) - nine metrics of pred / target (B,To,J,3) in one pass, without a host round trip:
+//   cg_em_batch_max_kernel   max over the batch of (sn[b,t,j] + w_t), the denominator of `w_joints_t` (test.py:67-70)
+//   cg_eval_metrics_kernel   one wavefront per (b,t) frame, one lane per joint: every sum over the joints of a frame (centroids,
+//                            norms, the 3x3 correlation of the Procrustes fit, the scale of n_mpjpe) is a wave reduction, no barrier
+//   cg_em_frames_kernel      `frames` mode only: the per-(b,t) sums over joints are added over b in a fixed order
+// A frame is at most 64 joints x 3 floats; what a lane holds is widened to fp64 once and rounded to fp32 once, at the store, so the
+// distance to an fp64 evaluation is the final rounding.  Nothing is accumulated with floating-point atomics: two calls give the same
+// bits.  Neither pred, target nor speeds is written (the reference divides `speeds` in place, test.py:67).
+#include "cg_common.h"
+
+#include <math.h>
+
+#define CG_EM_THREADS 256
+#define CG_EM_WAVES (CG_EM_THREADS / CG_WAVE)
+#define CG_EM_PRE_THREADS 1024
+#define CG_EM_PRE_WAVES (CG_EM_PRE_THREADS / CG_WAVE)
+#define CG_EM_METRICS 9
+#define CG_EM_SUMS 7
+
+// order of CgEvalMetrics.out (mirrored by include/cistgcn_hip.h and cistgcn_amd/ops.py)
+enum { CG_EM_MPJPE = 0, CG_EM_PA, CG_EM_N, CG_EM_MVE, CG_EM_W, CG_EM_BONE, CG_EM_WBONE, CG_EM_WJ, CG_EM_WJT };
+// the per-frame sums `frames` mode keeps: w_mpjpe and w_bone_l are w_t times the sums of mpjpe and bone_l
+enum { CG_EM_S_E = 0, CG_EM_S_PA, CG_EM_S_N, CG_EM_S_MVE, CG_EM_S_BONE, CG_EM_S_WJ, CG_EM_S_WJT };
+
+struct CgEvalMetrics {      // mirrored by include/cistgcn_hip.h and cistgcn_amd/_lib.py
+  int B, To, J, Nb, frames, pad;
+  const float* pred;        // (B,To,J,3)
+  const float* target;      // (B,To,J,3)
+  const float* speeds;      // (B,To,J)
+  const int32_t* bones;     // (Nb,2) joint pairs
+  float* out[CG_EM_METRICS];      // frames: (To,) each, (To-1,) for mve; else (B,To,J), (B,To-1,J) for mve, (B,To,Nb) for the bone metrics
+  double* ws;               // cg_eval_metrics_ws_doubles(B,To,J): [To*J] batch maxima | [CG_EM_SUMS][B][To] per-frame sums
+};
+
+// w_t = (t + 1) / To in fp32, as `arange(1, To + 1) / To` gives it (test.py:301-302)
+__device__ __forceinline__ double cg_em_wt(int t, int To) { return (double)((float)(t + 1) / (float)To); }
+
+// sum over the wavefront of N values at once, result in every lane (a butterfly: every lane adds the same pairs, so all lanes hold
+// the same bits); the N exchanges of a level are independent
+template <int N>
+__device__ __forceinline__ void cg_em_wave_sum(double (&v)[N]) {
+#pragma unroll
+  for (int off = CG_WAVE / 2; off > 0; off >>= 1) {
+#pragma unroll
+    for (int i = 0; i < N; ++i) v[i] += __shfl_xor(v[i], off, CG_WAVE);
+  }
+}
+
+__device__ __forceinline__ float cg_em_wave_max(float v) {
+#pragma unroll
+  for (int off = CG_WAVE / 2; off > 0; off >>= 1) v = fmaxf(v, __shfl_xor(v, off, CG_WAVE));
+  return v;
+}
+
+// sn + w_t of one joint: sn = speeds / (max over the joints of the frame + 1e-6) (test.py:67-69)
+__device__ __forceinline__ double cg_em_sn(float s, float frame_max) { return (double)s / ((double)frame_max + 1e-6); }
+
+// ---------------------------------------------------------------------------------------------
+// bmax[t,j] = max_b (sn[b,t,j] + w_t): one workgroup per frame index t, its waves stride over the samples
+// ---------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(CG_EM_PRE_THREADS) void cg_em_batch_max_kernel(const float* __restrict__ speeds, double* __restrict__ bmax, int B,
+                                                                            int To, int J) {
+  __shared__ double red[CG_EM_PRE_WAVES][CG_WAVE];
+  const int lane = threadIdx.x & (CG_WAVE - 1), wave = threadIdx.x / CG_WAVE;
+  for (int t = blockIdx.x; t < To; t += gridDim.x) {
+    const double wt = cg_em_wt(t, To);
+    double m = -INFINITY;
+    for (int b = wave; b < B; b += CG_EM_PRE_WAVES) {       // wave-uniform trip count: the shuffle below has all 64 lanes
+      const float s = lane < J ? speeds[((long long)b * To + t) * J + lane] : -INFINITY;
+      const float mx = cg_em_wave_max(s);
+      m = fmax(m, cg_em_sn(s, mx) + wt);
+    }
+    red[wave][lane] = m;
+    __syncthreads();
+    if (wave == 0 && lane < J) {
+      for (int w = 1; w < CG_EM_PRE_WAVES; ++w) m = fmax(m, red[w][lane]);
+      bmax[(long long)t * J + lane] = m;
+    }
+    __syncthreads();
+  }
+}
+
+// ---------------------------------------------------------------------------------------------
+// 3x3 Procrustes rotation.  H = U diag(s) V^T; the reference forms R = V' U^T with the last ROW of V scaled by sigma = sign det(V U^T)
+// (losses.py:106-119), i.e. R = diag(1,1,sigma) V U^T, and V U^T is the transposed polar factor of H: it does not depend on the signs
+// or the order a particular SVD gives its vectors.  V and s^2 come from cyclic Jacobi rotations of H^T H in fp64, u_i = H v_i / s_i for
+// the two larger singular values and u_3 = +-(u_1 x u_2), on the side of H v_3 (so a flat pose, s_3 = 0, still has a rotation).
+// Every lane of the wave runs this on the same numbers.
+// ---------------------------------------------------------------------------------------------
+#define CG_EM_ROTATE(p, q, r)                                                              \
+  if (A[p][q] != 0.0) {                                                                    \
+    const double theta = (A[q][q] - A[p][p]) / (2.0 * A[p][q]);                            \
+    const double tt = (theta < 0.0 ? -1.0 : 1.0) / (fabs(theta) + sqrt(theta * theta + 1.0)); \
+    const double c = 1.0 / sqrt(tt * tt + 1.0), s = tt * c;                                \
+    const double apq = A[p][q], arp = A[r][p], arq = A[r][q];                              \
+    A[p][p] -= tt * apq;                                                                   \
+    A[q][q] += tt * apq;                                                                   \
+    A[p][q] = A[q][p] = 0.0;                                                               \
+    A[r][p] = A[p][r] = c * arp - s * arq;                                                 \
+    A[r][q] = A[q][r] = s * arp + c * arq;                                                 \
+    for (int k = 0; k < 3; ++k) {                                                          \
+      const double vp = V[k][p], vq = V[k][q];                                             \
+      V[k][p] = c * vp - s * vq;                                                           \
+      V[k][q] = s * vp + c * vq;                                                           \
+    }                                                                                      \
+  }
+
+#define CG_EM_SWAP_COLS(i, j)                                                              \
+  {                                                                                        \
+    const double l = lam[i]; lam[i] = lam[j]; lam[j] = l;                                  \
+    for (int k = 0; k < 3; ++k) { const double v = V[k][i]; V[k][i] = V[k][j]; V[k][j] = v; } \
+  }
+
+// R0 = V U^T and the singular values of H (sv[2] the smallest)
+__device__ __forceinline__ void cg_em_polar(const double (&H)[3][3], double (&R0)[3][3], double (&sv)[3]) {
+  double A[3][3], V[3][3] = {{1.0, 0.0, 0.0}, {0.0, 1.0, 0.0}, {0.0, 0.0, 1.0}};
+#pragma unroll
+  for (int i = 0; i < 3; ++i)
+#pragma unroll
+    for (int j = 0; j < 3; ++j) A[i][j] = H[0][i] * H[0][j] + H[1][i] * H[1][j] + H[2][i] * H[2][j];
+  for (int sweep = 0; sweep < 8; ++sweep) {       // quadratic convergence: 3x3 is at fp64 rounding after 5 sweeps
+    CG_EM_ROTATE(0, 1, 2)
+    CG_EM_ROTATE(0, 2, 1)
+    CG_EM_ROTATE(1, 2, 0)
+  }
+  double lam[3] = {A[0][0], A[1][1], A[2][2]};
+  if (lam[0] < lam[2]) CG_EM_SWAP_COLS(0, 2)
+  if (lam[1] < lam[2]) CG_EM_SWAP_COLS(1, 2)
+  double U[3][3];      // U[c][m]: component c of u_m
+#pragma unroll
+  for (int m = 0; m < 3; ++m) {
+    sv[m] = sqrt(fmax(lam[m], 0.0));
+#pragma unroll
+    for (int c = 0; c < 3; ++c) U[c][m] = H[c][0] * V[0][m] + H[c][1] * V[1][m] + H[c][2] * V[2][m];      // H v_m, scaled below
+  }
+#pragma unroll
+  for (int c = 0; c < 3; ++c) { U[c][0] /= sv[0]; U[c][1] /= sv[1]; }
+  const double x0 = U[1][0] * U[2][1] - U[2][0] * U[1][1], x1 = U[2][0] * U[0][1] - U[0][0] * U[2][1], x2 = U[0][0] * U[1][1] - U[1][0] * U[0][1];
+  const double side = x0 * U[0][2] + x1 * U[1][2] + x2 * U[2][2] < 0.0 ? -1.0 : 1.0;
+  U[0][2] = side * x0; U[1][2] = side * x1; U[2][2] = side * x2;
+#pragma unroll
+  for (int r = 0; r < 3; ++r)
+#pragma unroll
+    for (int c = 0; c < 3; ++c) R0[r][c] = V[r][0] * U[c][0] + V[r][1] * U[c][1] + V[r][2] * U[c][2];
+}
+
+__device__ __forceinline__ double cg_em_norm3(double a, double b, double c) { return sqrt(a * a + b * b + c * c); }
+
+// ---------------------------------------------------------------------------------------------
+// the main pass: wave w of workgroup g takes frames g * CG_EM_WAVES + w, + gridDim.x * CG_EM_WAVES, ...
+// ---------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(CG_EM_THREADS) void cg_eval_metrics_kernel(CgEvalMetrics a) {
+  const int lane = threadIdx.x & (CG_WAVE - 1), wave = threadIdx.x / CG_WAVE;
+  const int J = a.J, To = a.To, Nb = a.Nb;
+  const long long F = (long long)a.B * To;
+  const bool on = lane < J;
+  const double* bmax = a.ws;
+  double* part = a.ws + (long long)To * J;
+  for (long long f = (long long)blockIdx.x * CG_EM_WAVES + wave; f < F; f += (long long)gridDim.x * CG_EM_WAVES) {      // wave-uniform
+    const int t = (int)(f % To);
+    const long long b = f / To;
+    const double wt = cg_em_wt(t, To);
+    const bool vel = t < To - 1;
+    const float* pf = a.pred + f * J * 3;
+    const float* xf = a.target + f * J * 3;
+    double P[3] = {0.0, 0.0, 0.0}, X[3] = {0.0, 0.0, 0.0}, mve = 0.0;
+    float sp = -INFINITY;
+    if (on) {
+#pragma unroll
+      for (int c = 0; c < 3; ++c) { P[c] = (double)pf[lane * 3 + c]; X[c] = (double)xf[lane * 3 + c]; }
+      sp = a.speeds[f * J + lane];
+      if (vel) {
+        double d[3];
+#pragma unroll
+        for (int c = 0; c < 3; ++c) d[c] = ((double)pf[(J + lane) * 3 + c] - P[c]) - ((double)xf[(J + lane) * 3 + c] - X[c]);
+        mve = cg_em_norm3(d[0], d[1], d[2]);
+      }
+    }
+    const double e = cg_em_norm3(P[0] - X[0], P[1] - X[1], P[2] - X[2]);
+
+    // sums over the joints, first round: centroids and the two means of n_mpjpe (lanes past J hold zeros)
+    double r1[8] = {X[0], X[1], X[2], P[0], P[1], P[2], X[0] * P[0] + X[1] * P[1] + X[2] * P[2], P[0] * P[0] + P[1] * P[1] + P[2] * P[2]};
+    cg_em_wave_sum(r1);
+    const double scale = (r1[6] / J) / (r1[7] / J);
+    const double en = cg_em_norm3(scale * P[0] - X[0], scale * P[1] - X[1], scale * P[2] - X[2]);
+
+    // second round: the centred poses, the reference's replacement of small target coordinates, norms and X0^T Y0
+    double muX[3], muY[3], X0[3], Y0[3];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      muX[c] = r1[c] / J;
+      muY[c] = r1[3 + c] / J;
+      X0[c] = on ? X[c] - muX[c] : 0.0;
+      Y0[c] = on ? P[c] - muY[c] : 0.0;
+      if (on && X0[c] * X0[c] < 1e-6) X0[c] = 1e-3;      // losses.py:94, kept as it is
+    }
+    double r2[11];
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+      for (int j = 0; j < 3; ++j) r2[3 * i + j] = X0[i] * Y0[j];
+    r2[9] = X0[0] * X0[0] + X0[1] * X0[1] + X0[2] * X0[2];
+    r2[10] = Y0[0] * Y0[0] + Y0[1] * Y0[1] + Y0[2] * Y0[2];
+    cg_em_wave_sum(r2);
+    const double normX = fmax(sqrt(r2[9]), 1e-3), normY = sqrt(r2[10]);
+    double H[3][3], R[3][3], sv[3];
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+      for (int j = 0; j < 3; ++j) H[i][j] = r2[3 * i + j] / (normX * normY);      // 0 / 0 = NaN when every predicted joint coincides
+    cg_em_polar(H, R, sv);
+    const double det = R[0][0] * (R[1][1] * R[2][2] - R[1][2] * R[2][1]) - R[0][1] * (R[1][0] * R[2][2] - R[1][2] * R[2][0]) +
+                       R[0][2] * (R[1][0] * R[2][1] - R[1][1] * R[2][0]);
+    const double sigma = det > 0.0 ? 1.0 : (det < 0.0 ? -1.0 : det);      // torch.sign: 0 stays 0, NaN stays NaN
+    double al = (sv[0] + sv[1] + sigma * sv[2]) * normX / normY, tr[3];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) R[2][c] *= sigma;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) tr[c] = muX[c] - al * (muY[0] * R[0][c] + muY[1] * R[1][c] + muY[2] * R[2][c]);
+    // losses.py:130-132, element by element: NaN in the scale -> 1, in the rotation -> 0, in the translation -> 0
+    if (al != al) al = 1.0;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      if (tr[c] != tr[c]) tr[c] = 0.0;
+#pragma unroll
+      for (int r = 0; r < 3; ++r)
+        if (R[r][c] != R[r][c]) R[r][c] = 0.0;
+    }
+    double dpa[3];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) dpa[c] = al * (P[0] * R[0][c] + P[1] * R[1][c] + P[2] * R[2][c]) + tr[c] - X[c];
+    const double epa = cg_em_norm3(dpa[0], dpa[1], dpa[2]);
+
+    // the speed weights
+    const float smax = cg_em_wave_max(sp);
+    double wj = 0.0, wjt = 0.0;
+    if (on) {
+      const double sn = cg_em_sn(sp, smax);
+      wj = sn * e;
+      wjt = (sn + wt) / bmax[(long long)t * J + lane] * e;
+    }
+
+    // bones: lane k takes bones k, k + 64, ...
+    double bsum = 0.0;
+    for (int k = lane; k < Nb; k += CG_WAVE) {
+      const int i = a.bones[2 * k], j = a.bones[2 * k + 1];
+      double v = 0.0;
+      if ((unsigned)i < (unsigned)J && (unsigned)j < (unsigned)J) {      // the operator refuses other indices; never read past the frame
+        const double lp = cg_em_norm3((double)pf[3 * i] - (double)pf[3 * j], (double)pf[3 * i + 1] - (double)pf[3 * j + 1], (double)pf[3 * i + 2] - (double)pf[3 * j + 2]);
+        const double lx = cg_em_norm3((double)xf[3 * i] - (double)xf[3 * j], (double)xf[3 * i + 1] - (double)xf[3 * j + 1], (double)xf[3 * i + 2] - (double)xf[3 * j + 2]);
+        v = fabs(lp - lx);
+      }
+      if (!a.frames) {
+        a.out[CG_EM_BONE][f * Nb + k] = (float)v;
+        a.out[CG_EM_WBONE][f * Nb + k] = (float)(wt * v);
+      }
+      bsum += v;
+    }
+
+    if (a.frames) {
+      double r3[CG_EM_SUMS] = {on ? e : 0.0, on ? epa : 0.0, on ? en : 0.0, mve, bsum, wj, wjt};
+      cg_em_wave_sum(r3);
+      if (lane < CG_EM_SUMS) {
+        double v = r3[0];
+#pragma unroll
+        for (int m = 1; m < CG_EM_SUMS; ++m) v = lane == m ? r3[m] : v;
+        part[((long long)lane * a.B + b) * To + t] = v;
+      }
+    } else if (on) {
+      const long long o = f * J + lane;
+      a.out[CG_EM_MPJPE][o] = (float)e;
+      a.out[CG_EM_PA][o] = (float)epa;
+      a.out[CG_EM_N][o] = (float)en;
+      a.out[CG_EM_W][o] = (float)(wt * e);
+      a.out[CG_EM_WJ][o] = (float)wj;
+      a.out[CG_EM_WJT][o] = (float)wjt;
+      if (vel) a.out[CG_EM_MVE][(b * (To - 1) + t) * J + lane] = (float)mve;
+    }
+  }
+}
+
+// out[q][t] = mean over samples and joints (bones): one wave per (q,t); lane l adds samples l, l + 64, ... in order, then the
+// lanes are added in the fixed tree of cg_wave_sum
+__global__ __launch_bounds__(CG_EM_THREADS) void cg_em_frames_kernel(CgEvalMetrics a) {
+  const int lane = threadIdx.x & (CG_WAVE - 1), wave = threadIdx.x / CG_WAVE;
+  const int To = a.To, B = a.B;
+  const double* part = a.ws + (long long)To * a.J;
+  const long long U = (long long)CG_EM_METRICS * To;
+  for (long long u = (long long)blockIdx.x * CG_EM_WAVES + wave; u < U; u += (long long)gridDim.x * CG_EM_WAVES) {
+    const int q = (int)(u / To), t = (int)(u % To);
+    if (q == CG_EM_MVE && t == To - 1) continue;      // wave-uniform
+    const int m = q == CG_EM_MPJPE || q == CG_EM_W ? CG_EM_S_E : q == CG_EM_PA ? CG_EM_S_PA : q == CG_EM_N ? CG_EM_S_N : q == CG_EM_MVE ? CG_EM_S_MVE
+                : q == CG_EM_BONE || q == CG_EM_WBONE ? CG_EM_S_BONE : q == CG_EM_WJ ? CG_EM_S_WJ : CG_EM_S_WJT;
+    double s = 0.0;
+    for (int b = lane; b < B; b += CG_WAVE) s += part[((long long)m * B + b) * To + t];
+    s = cg_wave_sum(s);
+    if (lane == 0) {
+      const bool bone = q == CG_EM_BONE || q == CG_EM_WBONE;
+      double v = s / ((double)B * (double)(bone ? a.Nb : a.J));
+      if (q == CG_EM_W || q == CG_EM_WBONE) v *= cg_em_wt(t, To);
+      a.out[q][t] = (float)v;
+    }
+  }
+}
+
+extern "C" long long cg_eval_metrics_ws_doubles(int B, int To, int J) {
+  if (B < 1 || To < 2 || J < 1 || J > CG_WAVE) return 0;
+  return (long long)To * J + (long long)CG_EM_SUMS * B * To;
+}
+
+extern "C" int cg_eval_metrics(const CgEvalMetrics* a, void* stream_) {
+  if (!a || !a->pred || !a->target || !a->speeds || !a->bones || !a->ws) return CG_EARG;
+  for (int q = 0; q < CG_EM_METRICS; ++q)
+    if (!a->out[q]) return CG_EARG;
+  if (a->B < 1 || a->To < 2 || a->J < 1 || a->J > CG_WAVE || a->Nb < 1) return CG_ESHAPE;
+  hipStream_t stream = (hipStream_t)stream_;
+  const long long F = (long long)a->B * a->To;
+  hipLaunchKernelGGL(cg_em_batch_max_kernel, dim3((unsigned)min(a->To, 4096)), dim3(CG_EM_PRE_THREADS), 0, stream, a->speeds, a->ws, a->B, a->To, a->J);
+  const long long groups = (F + CG_EM_WAVES - 1) / CG_EM_WAVES;
+  hipLaunchKernelGGL(cg_eval_metrics_kernel, dim3((unsigned)min(groups, 16384LL)), dim3(CG_EM_THREADS), 0, stream, *a);
+  if (a->frames) {
+    const long long fg = ((long long)CG_EM_METRICS * a->To + CG_EM_WAVES - 1) / CG_EM_WAVES;
+    hipLaunchKernelGGL(cg_em_frames_kernel, dim3((unsigned)min(fg, 4096LL)), dim3(CG_EM_THREADS), 0, stream, *a);
+  }
+  return cg_launch_status();
+}

@@ -4,4 +4,5 @@ as the reference's `human_motion_prediction.environment` for the functions mirro
 from .attacks import FGSM, IFGSM, MIFGSM, NOATTACK, NoAttack  # noqa: F401
 from .checkpoint import load_params_from_model_path, make_checkpoint, save_ckpt  # noqa: F401
 from .evaluation import capture_interpretation, mpjpe_ms_table, save_interpretation  # noqa: F401
+from .evaluation import EvalMetrics  # noqa: F401
 from .input_pipeline import DeviceAugmentation, DevicePrefetcher  # noqa: F401

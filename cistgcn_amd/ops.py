@@ -1352,6 +1352,52 @@ def eval_scatter_mpjpe(pred, target, dim_used, dim_repeat_32=(), dim_repeat_22=(
     return out, err
 
 
+# order of CgEvalMetrics.out (include/cistgcn_hip.h)
+EVAL_METRICS = ("mpjpe", "pa_mpjpe", "n_mpjpe", "mve", "w_mpjpe", "bone_l", "w_bone_l", "w_joints", "w_joints_t")
+
+
+def eval_metrics(pred, target, speeds, bones, reduce="frames"):
+    """The metrics of `Metrics.compute` (test.py:65-94; `mae` excepted) for one batch in one call: a dict of the names in
+    `EVAL_METRICS`.  pred / target (B,To,J,3), speeds (B,To,J) (`target_gvel[..., 0]`), bones: the (i,j) joint pairs of the skeleton.
+    reduce="frames": one value per frame, the mean over samples and joints ((To,), (To-1,) for `mve`), the reference's
+    `reduce_axis=(0, 2)`; reduce=None: per joint ((B,To,J), (B,To-1,J) for `mve`, (B,To,Nb) for `bone_l` / `w_bone_l`), its
+    `compute_joint_error`.  No input is written, nothing is read back, two calls give the same bits."""
+    if reduce not in ("frames", None):
+        raise ValueError("eval_metrics: reduce must be \"frames\" or None, got %r" % (reduce,))
+    _chk(pred, "pred"), _chk(target, "target"), _chk(speeds, "speeds")
+    if pred.dim() != 4 or pred.shape != target.shape or pred.shape[3] != 3:
+        raise ValueError("eval_metrics: expected pred and target of one shape (B,To,J,3), got %s and %s" % (tuple(pred.shape), tuple(target.shape)))
+    B, To, J, _ = pred.shape
+    if tuple(speeds.shape) != (B, To, J):
+        raise ValueError("eval_metrics: speeds must be (B,To,J) = %s, got %s" % ((B, To, J), tuple(speeds.shape)))
+    if B < 1 or J < 1 or J > 64 or To < 2:
+        raise ValueError("eval_metrics: needs B >= 1, 1 <= J <= 64 and To >= 2, got B=%d To=%d J=%d" % (B, To, J))
+    pairs = [(int(i), int(j)) for i, j in bones]
+    if not pairs:
+        raise ValueError("eval_metrics: no bones")
+    flat = [v for p in pairs for v in p]
+    if min(flat) < 0 or max(flat) >= J:
+        raise IndexError("eval_metrics: bone joint index out of range for %d joints" % J)
+    Nb = len(pairs)
+    pred = pred if pred.is_contiguous() else _copy(pred)
+    target = target if target.is_contiguous() else _copy(target)
+    speeds = speeds if speeds.is_contiguous() else _copy(speeds)
+    dev = pred.device
+    if reduce == "frames":
+        shapes = {k: (To - 1,) if k == "mve" else (To,) for k in EVAL_METRICS}
+    else:
+        shapes = {k: (B, To - 1, J) if k == "mve" else (B, To, Nb) if k in ("bone_l", "w_bone_l") else (B, To, J) for k in EVAL_METRICS}
+    out = {k: torch.empty(shapes[k], dtype=torch.float32, device=dev) for k in EVAL_METRICS}
+    ws = torch.empty(int(_lib.lib().cg_eval_metrics_ws_doubles(B, To, J)), dtype=torch.float64, device=dev)
+    a = _lib.EvalMetricsArgs()
+    a.B, a.To, a.J, a.Nb, a.frames = B, To, J, Nb, int(reduce == "frames")
+    a.pred, a.target, a.speeds, a.bones, a.ws = _ptr(pred), _ptr(target), _ptr(speeds), _ptr(_index_tensor(flat, dev)), _ptr(ws)
+    for q, k in enumerate(EVAL_METRICS):
+        a.out[q] = out[k].data_ptr()
+    _lib.call("cg_eval_metrics", ctypes.byref(a), _stream(pred))
+    return out
+
+
 def cumsum_time(x):
     """cumulative sum over axis 1 of a 4-D (possibly strided) tensor"""
     return _Cumsum.apply(x)

@@ -539,6 +539,34 @@ typedef struct CgAttackStep {
 int cg_attack_step(const CgAttackStep* a, void* stream);
 long long cg_attack_step_max_floats(void);
 
+/* ---- evaluation metrics (csrc/eval_metrics.hip) ------------------------------------------------------
+ * What environment/test.py::Metrics.compute (:65-94) reports per batch, except `mae`, in one pass on the device: out[] in the order
+ *   0 mpjpe      losses.mpjpe (losses/losses.py:50-61)                    e = |P - X|
+ *   1 pa_mpjpe   losses.pa_mpjpe (:79-144)                                |a P R + t - X| after the per-frame Procrustes fit, with the
+ *                                                                         reference's replacement of centred target coordinates whose
+ *                                                                         square is < 1e-6 by 1e-3 (:94), R = diag(1,1,sign det) V U^T
+ *                                                                         (:106-119) and its NaN rule a -> 1, R -> 0, t -> 0 (:130-132)
+ *   2 n_mpjpe    losses.n_mpjpe (:147-160)                                |c P - X|, c = mean_j(X.P) / mean_j(P.P) of the frame
+ *   3 mve        losses.mean_velocity_error (:163-177)                    |(P[t+1] - P[t]) - (X[t+1] - X[t])|, To - 1 frames
+ *   4 w_mpjpe    losses.weighted_mpjpe with temporal_w (:64-76, test.py:68,81)         w_t e, w_t = (t + 1) / To (test.py:301-302)
+ *   5 bone_l     losses.bone_length_error (:199-215)                      | |P_i - P_j| - |X_i - X_j| | per bone (i,j)
+ *   6 w_bone_l   losses.weighted_bone_length_error (:218-238)             w_t bone_l
+ *   7 w_joints   losses.weighted_mpjpe with speeds (test.py:67,89)        sn e, sn = speeds / (max_j speeds + 1e-6)
+ *   8 w_joints_t losses.weighted_mpjpe with speed_temporal_w (test.py:69-70,91)        (sn + w_t) / max_b(sn + w_t) e
+ * frames = 1 (reduce_axis (0,2), test.py:289): every out[q] is (To,), the mean over samples and joints (bones), (To-1,) for mve;
+ * frames = 0 (compute_joint_error, test.py:303-304): (B,To,J), (B,To-1,J) for mve, (B,To,Nb) for the bone metrics.
+ * pred / target (B,To,J,3), speeds (B,To,J) contiguous and never written; bones (Nb,2) joint indices in [0,J);
+ * J <= 64, To >= 2, Nb >= 1, B >= 1, else CG_ESHAPE.  ws: cg_eval_metrics_ws_doubles(B,To,J) doubles (0 for an unsupported shape).
+ * No floating-point atomics (the sums over the batch are added in a fixed order): two calls give the same bits. */
+typedef struct CgEvalMetrics {
+  int B, To, J, Nb, frames, pad;
+  const float* pred; const float* target; const float* speeds; const int32_t* bones;
+  float* out[9];
+  double* ws;
+} CgEvalMetrics;
+int cg_eval_metrics(const CgEvalMetrics* a, void* stream);
+long long cg_eval_metrics_ws_doubles(int B, int To, int J);
+
 #ifdef __cplusplus
 }
 #endif
