@@ -192,6 +192,14 @@ __device__ __forceinline__ void cg_tail_act_load(const CgDstdTail& t, int b, int
   }
 }
 
+// pre-activation of prelu1 / prelu2 from z = w * x: gamma * zhat + beta with zhat = (z - mean) * rstd rounded on its own - the very
+// expression the backward (K3) forms from the zhat it stages.  With (z - mean) * (gamma * rstd) + beta here the two differ by an ulp of
+// beta, and an element that close to 0 took one PReLU branch forward and the other one backward.
+__device__ __forceinline__ float cg_tail_pre_p(float z, float mean, float rstd, float gamma, float beta) {
+  const float zhat = (z - mean) * rstd;
+  return gamma * zhat + beta;
+}
+
 template <int PT>
 __device__ __forceinline__ void cg_tail_act_finish(const CgTailHot& t, const float* sK, unsigned long long seed, int b, int p0, int np,
                                                    const float4 yq[PT / 8], const float4 rq[PT / 8], const float wq[PT / 8], float* img, int what) {
@@ -209,14 +217,14 @@ __device__ __forceinline__ void cg_tail_act_finish(const CgTailHot& t, const flo
       const float yv[4] = {yq[q].x, yq[q].y, yq[q].z, yq[q].w}, rv[4] = {rq[q].x, rq[q].y, rq[q].z, rq[q].w};
       float keep[4];
       cg_tail_keep4(t, i, seed, (unsigned long long)off, keep);
-      const float wv = wq[q], ap = t.alpha_p[i], scale_p = k1.z * k1.y;
+      const float wv = wq[q], ap = t.alpha_p[i];
       float xv[4];
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         const float u = ((yv[j] - k0.x) * k0.y + k0.z) * keep[j] + rv[j];
         xv[j] = cg_prelu(u, k0.w);
         const float z = wv * xv[j];
-        val[j] = what == 0 ? cg_prelu((z - k1.x) * scale_p + k1.w, ap) : (z - k1.x) * k1.y;
+        val[j] = what == 0 ? cg_prelu(cg_tail_pre_p(z, k1.x, k1.y, k1.z, k1.w), ap) : (z - k1.x) * k1.y;
       }
       if (what == 0) {
         if (t.tap_a[i]) *reinterpret_cast<float4*>(t.tap_a[i] + off) = make_float4(val[0], val[1], val[2], val[3]);
@@ -248,14 +256,14 @@ __device__ __forceinline__ void cg_tail_stage_act(const CgDstdTail& t, const flo
         const float yv[4] = {y4.x, y4.y, y4.z, y4.w}, rv[4] = {r4.x, r4.y, r4.z, r4.w};
         float keep[4];
         cg_tail_keep4(t, i, seed, (unsigned long long)off, keep);
-        const float wv = t.w[i][(long long)b * C + c], ap = t.alpha_p[i][0], scale_p = k1.z * k1.y;
+        const float wv = t.w[i][(long long)b * C + c], ap = t.alpha_p[i][0];
         float xv[4];
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
           const float u = ((yv[j] - k0.x) * k0.y + k0.z) * keep[j] + rv[j];
           xv[j] = cg_prelu(u, k0.w);
           const float z = wv * xv[j];
-          val[j] = what == 0 ? cg_prelu((z - k1.x) * scale_p + k1.w, ap) : (z - k1.x) * k1.y;
+          val[j] = what == 0 ? cg_prelu(cg_tail_pre_p(z, k1.x, k1.y, k1.z, k1.w), ap) : (z - k1.x) * k1.y;
         }
         if (what == 0) {
           if (t.tap_a[i]) *reinterpret_cast<float4*>(t.tap_a[i] + off) = make_float4(val[0], val[1], val[2], val[3]);
@@ -277,7 +285,7 @@ __device__ __forceinline__ void cg_tail_stage_act(const CgDstdTail& t, const flo
       const float u = ((t.y[i][off] - k[0]) * k[1] + k[2]) * keep + t.r[i][off];
       const float z = t.w[i][(long long)b * C + c] * cg_prelu(u, k[3]);
       if (what == 0) {
-        val = cg_prelu((z - k[4]) * (k[6] * k[5]) + k[7], t.alpha_p[i][0]);
+        val = cg_prelu(cg_tail_pre_p(z, k[4], k[5], k[6], k[7]), t.alpha_p[i][0]);
         if (t.tap_a[i]) t.tap_a[i][off] = val;
         if (!t.train && t.tap_x[i]) t.tap_x[i][off] = cg_prelu(u, k[3]);       // eval: F1 does not run
       }

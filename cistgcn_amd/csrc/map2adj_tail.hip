@@ -305,11 +305,17 @@ __device__ __forceinline__ void cg_adj_m2_body(const CgAdjTail& t, const CgAdjGe
     __syncthreads();
     cg_adj_commit<KCM, VEC>(Kc, np, [&](int c, int pp, bool ok, int off) {
       const float4 k4 = *reinterpret_cast<const float4*>(sK + 8 * c);           // mean, rstd, scale, beta
+      const float gam = sK[8 * c + 6];
       const long long idx = ((long long)b * Kc + c) * Pn + p0 + pp;
       float keep[4], v[4];
       cg_adj_keeps<VEC>(drop_p, salt, drop && ok, seed, idx, keep);
+      // gamma * e_hat + beta with e_hat = (e - mean) * rstd rounded on its own: the expression the backward forms from the e_hat it stages
+      // ((e - mean) * scale + beta differs from it by an ulp of beta: an element that close to 0 took the other PReLU branch backward)
 #pragma unroll
-      for (int j = 0; j < N; ++j) v[j] = ok ? cg_prelu(((ebuf[off + j] - k4.x) * k4.z + k4.w) * keep[j], alpha) : 0.f;
+      for (int j = 0; j < N; ++j) {
+        const float ehat = (ebuf[off + j] - k4.x) * k4.y;
+        v[j] = ok ? cg_prelu((gam * ehat + k4.w) * keep[j], alpha) : 0.f;
+      }
       cg_adj_put<KCM, VEC>(sH, c, pp, v);
       if (tap && ok) {
         if (VEC) *reinterpret_cast<float4*>(tap + idx) = make_float4(v[0], v[1], v[2], v[3]);

@@ -931,12 +931,15 @@ def _interpretation_attrs(model):
 
 
 def check_model_branch_replay(device, C, T, V, B, mode="train", seed=0, scale=350.0, grad_floor=1.0, max_flip_frac=2e-5,
-                              x=None, tgt=None, net=None, ora=None, rel_bound=None, oracle_fp64=False, attr_rel=1e-3, rel_min_size=16, **cfg_kw):
+                              x=None, tgt=None, net=None, ora=None, rel_bound=None, oracle_fp64=False, attr_rel=1e-3, rel_min_size=16, after_device_run=None,
+                              **cfg_kw):
     """Flip-aware parity of EVERY parameter gradient (north_star tolerance 1e-4): the HIP model runs first and records
     the branch each PReLU element took (`net.act_trace`); the oracle then differentiates the same piecewise-linear
     function (helpers.BranchReplay), so no kink allowance is needed: pred, loss, dL/dx and all parameter gradients are
     held to max|a-b| <= 1e-4 * max(floor, max|ref|).  The branches the oracle would have taken on its own are compared
-    too: they may differ from the HIP ones only on a vanishing fraction of elements whose pre-activation is rounding-sized."""
+    too: they may differ from the HIP ones only on a vanishing fraction of elements whose pre-activation is rounding-sized.
+    `after_device_run` (a callable) runs behind the forward + backward of the HIP model, before the oracle runs and before any number is
+    compared (check_model_plan asserts the launch plan there)."""
     from helpers import BranchReplay, assert_grads_strict
     g = _gen(2000 + seed)
     To = cfg_kw.get("To", 25)
@@ -967,6 +970,8 @@ def check_model_branch_replay(device, C, T, V, B, mode="train", seed=0, scale=35
         seed = int(ops.seed_state(device)[0].item())       # the word the kernels of this forward drew their masks from
     finally:
         net.act_trace, net.drop_trace = None, None
+    if after_device_run is not None:
+        after_device_run()
     dropping = mode == "train" and net.dropout > 0.0
     from helpers import DropReplay
     ora32 = ora
@@ -1021,6 +1026,171 @@ def check_model_branch_replay(device, C, T, V, B, mode="train", seed=0, scale=35
         ora32.load_state_dict({k: (v.float() if v.dtype.is_floating_point else v) for k, v in so.items()})
     return {"flips": rep.flips, "elements": rep.elements, "worst_flip": rep.worst, "worst_grad": worst, "relative_error": rel_report,
             "worst_attr": worst_attr, "dropout_sites": drp.sites if dropping else 0, "dropped": drp.dropped if dropping else 0}
+
+
+def check_model_plan(device, entry, mode, stack_all=False, **cfg_kw):
+    """One entry of tests/plan_shapes.py: the model at a shape that puts a launch-plan predicate on the side the reference's YAML shapes
+    never reach.  The plan first - how often each fused entry point ran in the forward, against the hand-written counts of the entry,
+    asserted behind the HIP run and before the oracle runs -, then the numbers: check_model_branch_replay against the fp64 oracle on the
+    PReLU branches (and dropout masks) of the HIP run, at the project's bound 1e-4 * max(floor, max|ref|) with floor 0.25 in eval mode and
+    1 in train mode, attributes and running statistics at its defaults.  `cfg_kw` adds make_cfg keywords (dropout=0.1)."""
+    import helpers
+    import loop_shapes
+    import plan_shapes
+    C, T, V, B = entry["shape"]
+    assert B >= 6, "batch statistics over fewer than six samples miss the bound on every plan"
+    if entry["stage_geometry"]:
+        for line in plan_shapes.stage_kernels(entry):
+            print(line)
+    saved = {k: getattr(ops, k) for k in entry["patch"]}
+    helpers.reset_worst()
+    try:
+        for k, v in entry["patch"].items():
+            setattr(ops, k, v)
+        with loop_shapes.counted_calls() as launches:
+            try:
+                r = check_model_branch_replay(device, C, T, V, B, mode, grad_floor=0.25 if mode == "eval" else 1.0, oracle_fp64=True, stack_all=stack_all,
+                                              after_device_run=lambda: plan_shapes.assert_plan(entry, stack_all, dict(launches)),
+                                              **dict(entry["cfg"], **cfg_kw))
+            except RuntimeError as e:
+                if "cistgcn_hip:" not in str(e):
+                    raise
+                # a predicate lets through what the library refuses (a limit moved on one side only)
+                raise AssertionError("launch plan of %s (stack_all=%s): the model called an entry point with a shape it refuses (%s); launches up to there %s"
+                                     % (entry["name"], stack_all, e, {k: v for k, v in launches.items() if k in plan_shapes.ALWAYS + plan_shapes.STACKED})) from e
+    finally:
+        for k, v in saved.items():
+            setattr(ops, k, v)
+    print("plan %s %s stack_all=%s: %s; worst gradient at %.3f of its bound (%s); %s" % (entry["name"], mode, stack_all, helpers.worst_line(), r["worst_grad"][0], r["worst_grad"][1], r))
+    return r
+
+
+# every shape predicate the launch plan asks, at its limit and one step past it: (family, operator check, its shape AT the limit)
+LIMIT_SHAPES = (
+    ("collapse_rows V = 32, O = 64", "check_collapse_rows", (2, 6, 4, 32, 64)),
+    ("collapse_cols T = 64, O = 64", "check_collapse_cols", (2, 6, 64, 4, 64)),
+    ("gate_head C = 64, S = 192", "check_gate_head", (5, 64, 192, 2)),
+    ("context_heads hidden = 64", "check_context_heads", (3, 5, 12, 64)),
+    ("context_heads H * W = 16384", "check_context_heads", (2, 128, 128, 4)),
+    ("map2adj_tail T = 64", "check_map2adj_tail", (2, 64, 6)),          # these three with replay=True (limit_kwargs): at (2, 64, 6) one pre-activation of
+    ("map2adj_tail V = 64", "check_map2adj_tail", (2, 6, 64)),          # the 49 152 lies within rounding of 0 and the fp64 reference, left to its own
+    ("dstd_tail C = 64", "check_dstd_tail", (2, 64, 3, 5)),             # branches, takes the other one (a kink term of 0.7 in ds; see BranchLog)
+    ("pointwise_maps C = 128, 32 tiles of 16 x 16", "check_pointwise_maps", (2, 128, (32, 32), 3, 4)),
+    ("pointwise_maps 128 stacked rows", "check_pointwise_maps", (2, 10, (64, 64), 3, 4)),
+    ("tower_maps C = 128", "check_tower_maps", (2, 128, (32, 32), 3, 4)),
+    ("stgcn_domain Cin = Cout = 128", "check_stgcn_domain", (2, 128, 128, 3, 4)),
+    ("dilated_convs H * W = 256", "check_dilated_convs", (2, 5, 4, 16, 16)),
+)
+
+
+def limit_kwargs(check):
+    """keywords of the operator check `check` for a LIMIT_SHAPES entry"""
+    return {"replay": True} if check in ("check_map2adj_tail", "check_dstd_tail", "check_tower_maps") else {}
+
+
+def check_predicate_limits():
+    """Host side only (no launch): every `*_ok` / `*_supported` predicate of the launch plan says yes AT its limit (the shapes of
+    LIMIT_SHAPES, which the operator checks then run) and no one step past it.  Nothing here calls an entry point with a shape it refuses."""
+    import ctypes
+    from types import SimpleNamespace as NS
+    from cistgcn_amd import _lib
+    from cistgcn_amd.models.CISTGCN.CISTGCN import CISTGCN
+    lib = _lib.lib()
+    meta = lambda *shape: torch.empty(shape, device="meta")
+    rows = lambda C, T, V, O: ops.collapse_rows_ok(meta(2, C, T, V), meta(O, C, T))
+    cols = lambda C, T, V, O: ops.collapse_cols_ok(meta(2, C, T, V), meta(O, C, V))
+    assert rows(6, 4, 32, 64) and not rows(6, 4, 33, 64) and not rows(6, 4, 32, 65) and not rows(5, 5, 32, 64), "collapse_rows_ok: V <= 32, O <= 64, C * T % 4 == 0"
+    assert not ops.collapse_rows_ok(meta(2, 4, 6, 8).permute(0, 1, 3, 2), meta(5, 4, 8)), "collapse_rows_ok: contiguous input"
+    assert cols(6, 64, 4, 64) and not cols(6, 65, 4, 64) and not cols(6, 64, 4, 65) and not cols(5, 64, 5, 64), "collapse_cols_ok: T <= 64, O <= 64, C * V % 4 == 0"
+    for (C, T, V, O) in ((6, 64, 4, 64), (6, 65, 4, 64), (6, 64, 4, 65), (5, 64, 5, 64)):
+        assert bool(lib.cg_collapse_cols_supported(C, T, V, O)) == cols(C, T, V, O), "collapse_cols_ok and cg_collapse_cols_supported disagree at %s" % ((C, T, V, O),)
+    one, three = [nn.PReLU()] * 4, [nn.PReLU()] * 3 + [nn.PReLU(3)]
+    assert ops.gate_head_ok(5, 64, 192, one) and not ops.gate_head_ok(5, 65, 192, one) and not ops.gate_head_ok(5, 64, 193, one) and not ops.gate_head_ok(5, 64, 192, three), \
+        "gate_head_ok: C <= 64, S <= 192, shared slopes"
+    assert ops.context_heads_ok(meta(2, 1, 128, 128), 64) and not ops.context_heads_ok(meta(2, 1, 128, 128), 65) and not ops.context_heads_ok(meta(2, 1, 1, 16385), 64) \
+        and not ops.context_heads_ok(meta(2, 2, 4, 4), 8), "context_heads_ok: hidden <= 64, H * W <= 16384, one input channel"
+    pw = lambda C, Ms, H, W: ops.pointwise_maps_ok(meta(2, C, H, W), [meta(M, C) for M in Ms])
+    assert pw(128, (32, 32), 3, 4) and not pw(129, (32, 32), 3, 4) and not pw(128, (32, 32, 16), 3, 4), "pointwise_maps_ok: C <= 128, (rows / 16) * ceil(C / 16) <= 32"
+    assert pw(10, (64, 64), 3, 4) and not pw(10, (64, 64, 1), 3, 4) and not pw(10, (65,), 3, 4) and not pw(10, (8,), 3, 3) and not pw(10, (8,) * 5, 3, 4), \
+        "pointwise_maps_ok: 128 stacked rows, 64 rows per map, H * W even, four maps"
+    tw = lambda prelus: ops.tower_maps_ok(meta(2, 10, 3, 4), [meta(8, 10)] * len(prelus), prelus)
+    assert tw([nn.PReLU(), None]) and not tw([nn.PReLU(), nn.PReLU(8)]), "tower_maps_ok: shared slopes"
+    stage = lambda cin, cout: CISTGCN._fused_stage_ok(NS(fused_domain=True), nn.Conv2d(cin, cout, 1))
+    assert stage(128, 128) and not stage(129, 128) and not stage(128, 129), "_fused_stage_ok: Cin, Cout <= 128"
+    geom = lambda cin, cout, T, V, dom: lib.cg_stgcn_domain_geometry(8, cin, cout, T, V, dom, 1, 0, (ctypes.c_int * 6)())
+    assert geom(128, 128, 10, 22, 0) == 0 and geom(129, 128, 10, 22, 0) != 0 and geom(128, 129, 10, 22, 1) != 0, "cg_stgcn_domain_geometry: Cin, Cout <= 128"
+    fpn = lambda H, W: bool(lib.cg_fpn_conv_supported(8, 5, 4, H, W))
+    assert fpn(16, 16) and fpn(10, 25) and not fpn(10, 26) and not fpn(1, 257) and not fpn(9, 9) and not fpn(5, 5), "cg_fpn_conv_supported: H * W <= 256, H * W % 4 in (0, 2)"
+    assert ops.block_input_ok(meta(2, 10, 10, 22)) and not ops.block_input_ok(meta(2, 10, 22, 10).permute(0, 1, 3, 2)), "block_input_ok: contiguous input"
+
+
+def check_family_at_limit(device, case):
+    """one entry of LIMIT_SHAPES: the operator-level check of the family AT the limit of its predicate, small batch"""
+    import helpers
+    what, check, shape = case
+    helpers.reset_worst()
+    globals()[check](device, shapes=(shape,), **limit_kwargs(check))
+    print("%s: %s %s: %s" % (what, check, shape, helpers.worst_line()))
+
+
+def check_dstd_tail_kink_branches(device):
+    """The fused tail takes, in its backward, the PReLU branch its own forward took - also at pre-activations within an ulp of 0.
+    Deterministic, eval mode: for eight channels with different BatchNorm constants, the 1024 positions of sample 0 carry z = the fp32
+    neighbours (one ulp apart) of the zero z* = mean - beta / (gamma * rstd) of the prelu1 pre-activation gamma * (z - mean) * rstd + beta,
+    so in every channel the pre-activation walks through 0 in steps of an ulp (y = 0, w = 1 and unit tcn constants make z = r, the
+    residual input, bit for bit).  The reference (fp64 stock PyTorch) takes the branches read off the forward's PReLU outputs and nothing is
+    explained away as a kink term: with two different roundings of the pre-activation in forward ((z - mean) * (gamma * rstd) + beta) and
+    backward (gamma * zhat + beta) the elements between their two zero crossings got the slope forward and the factor 1 backward - dr off
+    by (1 - alpha) * |dx| at those elements (0.23 against a bound of 6e-5 on the CPU shim).  At model level one such element among a million moved the most
+    sensitive gradients of a train step (`map_t.0.weight` of the block and of the blocks in front of it) by ten times their bound in about
+    one run of thirty, the elements changing with the order of the fp32 atomics."""
+    from cistgcn_amd.models.layers.SE import SELayer2d
+    B, C, T, V = 2, 8, 32, 32
+    P = T * V
+    g = _gen(77)
+    bns = [nn.BatchNorm2d(C) for _ in range(5)]
+    al = [nn.PReLU() for _ in range(5)]
+    conv, se = nn.Conv2d(2 * C, C, 1, bias=False), SELayer2d(C, reduction=8)
+    with torch.no_grad():
+        for bn in bns[:2]:                       # tcn BatchNorms: y = 0 -> exactly 0 (mean 0, beta 0)
+            bn.weight.fill_(1.0); bn.bias.zero_(); bn.running_mean.zero_(); bn.running_var.fill_(1.0)
+        for bn in bns[2:]:
+            bn.weight.copy_(1 + 0.3 * torch.rand(C, generator=g)); bn.running_mean.copy_(0.1 + 0.3 * torch.rand(C, generator=g))
+            bn.running_var.copy_(0.5 + torch.rand(C, generator=g)); bn.bias.copy_(-0.2 - 0.4 * torch.rand(C, generator=g))
+        for i, a in enumerate(al):
+            a.weight.fill_(0.1 + 0.07 * i)
+        conv.weight.copy_(0.3 * torch.randn(conv.weight.shape, generator=g))
+        se.w1.copy_(0.5 * torch.randn(se.w1.shape, generator=g)); se.w2.copy_(0.5 * torch.randn(se.w2.shape, generator=g))
+    mods = nn.ModuleList(bns + al + [conv, se]).to(device).eval()
+    bp = bns[2]
+    rstd = 1.0 / torch.sqrt(bp.running_var.detach().cpu().double() + bp.eps)
+    zstar = (bp.running_mean.detach().cpu().double() - bp.bias.detach().cpu().double() / (bp.weight.detach().cpu().double() * rstd)).float()
+    assert bool((zstar > 0.1).all())
+    r1 = 0.5 + torch.rand(B, C, T, V, generator=g)
+    for c in range(C):
+        z0 = np.float32(zstar[c].item())
+        r1[0, c] = torch.from_numpy((z0 + np.spacing(z0) * np.arange(-P // 2, P // 2, dtype=np.float32)).astype(np.float32)).view(T, V)
+    data = [torch.zeros(B, C, T, V), torch.zeros(B, C, T, V), r1, 0.5 + torch.rand(B, C, T, V, generator=g), torch.ones(B, C), torch.ones(B, C), _rand(g, B, C, T, V)]
+    gout = _rand(g, B, C, T, V).to(device)
+    rparams, rbufs = _ref_state(mods)
+    leaves = [_leaf(t, device) for t in data]
+    ops.begin_step(device)
+    taps = []
+    out, _ = ops.dstd_tail(leaves[:2], [None, None], leaves[2:4], (leaves[4], leaves[5]), list(mods[:5]), list(mods[5:10]), mods[10].weight, mods[11], leaves[6], False, taps=taps)
+    out.backward(gout)
+    a1 = taps[2].detach().cpu()[0]                        # prelu1 outputs of sample 0: both branches occur in every channel, one crossing each
+    assert all(bool((a1[c] > 0).any()) and bool((a1[c] <= 0).any()) for c in range(C)), "the pre-activations do not cross 0"
+    rleaves = [_leaf(t.double(), "cpu") for t in data]
+    log = BranchLog()
+    rout = _dstd_tail_ref(rleaves, rparams, rbufs, False, 0.0, (0, 0), 0, log, taps)
+    rout.backward(gout.detach().cpu().double())
+    log.settle("dstd_tail kink branches")
+    assert_close(out, rout, "dstd_tail kink branches out", rel=2e-5)
+    for k in (2, 0):
+        ref = rleaves[k].grad
+        assert_close(leaves[k].grad, ref, "dstd_tail kink branches: gradient of %s on the forward's branches" % ("r1" if k == 2 else "y1"), rel=5e-5, floor=float(ref.abs().max()))
+    print("dstd_tail kink branches: %d of %d pre-activations of the reference within rounding of 0 on the other side than the kernel's forward; backward on the forward's branches everywhere"
+          % (log.flips, B * C * P * 5))
 
 
 # ---------------------------------------------------------------------------------------------

@@ -9,6 +9,7 @@ import torch
 
 import checks
 import emu
+import plan_shapes
 from helpers import CASES
 
 
@@ -83,6 +84,27 @@ def test_golden_case_on_the_branches_of_the_hip_run(name):
 def test_non_interpretable_layers_at_model_level(mode):
     interp, interp_o = (False, True, False, True, False), (False,)
     checks.check_model_branch_replay("cpu", 8, 10, 22, 6, mode, grad_floor=0.25 if mode == "eval" else 1.0, interp=interp, interp_o=interp_o)
+
+
+@pytest.mark.parametrize("stack_all", [False, True], ids=["by-size", "stack-all"])
+@pytest.mark.parametrize("mode", ["eval", "train"])
+@pytest.mark.parametrize("name", [e["name"] for e in plan_shapes.PLANS])
+def test_model_launch_plans_outside_the_fused_limits(name, mode, stack_all):
+    """tests/plan_shapes.py: shapes the reference accepts and its YAML files never use (75 input frames, 40 output frames, 70 joints,
+    hidden_dim 96, 72 / 130 channels, non-uniform widths ...) put each shape predicate of the staged block on its other side.  The plan
+    is asserted first (forward launches per fused entry point against the hand-written counts), then every number against the fp64
+    oracle on the kernels' branches at 1e-4 * max(floor, max|ref|), floor 0.25 (eval) / 1 (train)."""
+    checks.check_model_plan("cpu", plan_shapes.BY_NAME[name], mode, stack_all=stack_all)
+
+
+@pytest.mark.parametrize("name", plan_shapes.DROPOUT_PLANS)
+def test_model_launch_plans_with_dropout(name):
+    """train mode with dropout 0.1 on two fallback plans: the generic adjacency chain (T = 70) and the row-kernel chain behind the tcn
+    convolutions with the unfused gate path (C = 72) number their dropout sites like the fused kernels, so the oracle draws the very
+    masks of the HIP run at all 14 * blocks + 7 sites (asserted inside check_model_branch_replay)"""
+    entry = plan_shapes.BY_NAME[name]
+    r = checks.check_model_plan("cpu", entry, "train", dropout=0.1)
+    assert r["dropout_sites"] == 14 * 3 + 7, r["dropout_sites"]              # blocks = 1: two input blocks and the output block
 
 
 @pytest.mark.skipif(os.environ.get("HIPEMU_SANITIZE", "0") == "1", reason="torch's tracer ends an interpreter that runs under libasan")

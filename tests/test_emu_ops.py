@@ -97,6 +97,24 @@ def test_operator_loop_shapes(family):
     print("%s: %s" % (family.__name__[len("_loops_"):], helpers.worst_line()))
 
 
+def test_tail_backward_takes_the_branches_of_its_forward():
+    """fused DSTD tail, pre-activations of prelu1 walking through 0 in steps of one ulp: the backward takes the forward's branch at every
+    element (forward and backward once rounded the pre-activation differently)"""
+    checks.check_dstd_tail_kink_branches("cpu")
+
+
+def test_plan_predicates_at_their_limits():
+    """host side only: every `*_ok` / `*_supported` predicate of the model's launch plan says yes at its limit and no one step past it"""
+    checks.check_predicate_limits()
+
+
+@pytest.mark.parametrize("case", checks.LIMIT_SHAPES, ids=lambda c: c[0].replace(" ", "").replace(",", "-"))
+def test_family_at_the_limit_of_its_predicate(case):
+    """the operator check of a family on the last shape its predicate takes (V = 32, T = 64, O = 64, C = 64 / 128, S = 192, H * W = 256 /
+    16384 ...); one step past it the model takes the fallback, which tests/plan_shapes.py holds at model level"""
+    checks.check_family_at_limit("cpu", case)
+
+
 def test_stgcn_domain_loop_shapes():
     """tile and matrix-core kernels of the fused ST-GCN stage with several tiles per workgroup (the plane generation pinned off: it would take
     these batch sizes where it has the (T, V) family), and the plane kernels with a batch that does not fill its last group of eight samples"""

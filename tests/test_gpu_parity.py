@@ -9,6 +9,7 @@ import torch
 import checks
 import helpers
 import loop_shapes as L
+import plan_shapes
 from helpers import CASES
 from oracle import cistgcn_ref as O
 
@@ -214,6 +215,25 @@ def test_stgcn_domain_across_the_plane_switch(B):
     print("stgcn_domain B=%d: %s" % (B, helpers.worst_line()))
 
 
+def test_tail_backward_takes_the_branches_of_its_forward():
+    """fused DSTD tail, pre-activations of prelu1 walking through 0 in steps of one ulp: the backward takes the forward's branch at every
+    element (forward and backward once rounded the pre-activation differently)"""
+    checks.check_dstd_tail_kink_branches("cuda")
+
+
+def test_plan_predicates_at_their_limits():
+    """host side only, against the shipped library: every `*_ok` / `*_supported` predicate of the model's launch plan says yes at its limit
+    and no one step past it"""
+    checks.check_predicate_limits()
+
+
+@pytest.mark.parametrize("case", checks.LIMIT_SHAPES, ids=lambda c: c[0].replace(" ", "").replace(",", "-"))
+def test_family_at_the_limit_of_its_predicate(case):
+    """the operator check of a family on the last shape its predicate takes; one step past it the model takes the fallback
+    (test_model_launch_plans_outside_the_fused_limits)"""
+    checks.check_family_at_limit("cuda", case)
+
+
 @pytest.mark.parametrize("name", CASES)
 @pytest.mark.parametrize("mode", ["eval", "train"])
 def test_model_matches_reference_golden(name, mode):
@@ -265,6 +285,25 @@ def test_every_gradient_within_1e4_on_the_same_branches(cfg, mode):
     C, T, V, B = cfg
     r = checks.check_model_branch_replay("cuda", C, T, V, B, mode, grad_floor=0.25 if mode == "eval" else 1.0, rel_bound=REL_BOUND)
     print("branch replay %s %s: %s" % (cfg, mode, r))
+
+
+@pytest.mark.parametrize("stack_all", [False, True], ids=["by-size", "stack-all"])
+@pytest.mark.parametrize("mode", ["eval", "train"])
+@pytest.mark.parametrize("name", [e["name"] for e in plan_shapes.PLANS])
+def test_model_launch_plans_outside_the_fused_limits(name, mode, stack_all):
+    """tests/plan_shapes.py on the MI355X: every shape predicate of the staged block on the side the reference's YAML shapes never reach
+    (T > 64, V > 32 / > 64, output_n 40 / 70, C * T % 4, odd T * V, hidden_dim 96, C = 72 / 130, gate S > 192, non-uniform widths, the
+    dilated convolutions across cg_fpn_conv_supported).  Plan first (forward launches per fused entry point against the hand-written
+    counts), numbers second: fp64 oracle on the kernels' branches, 1e-4 * max(floor, max|ref|), floor 0.25 (eval) / 1 (train), B = 8."""
+    checks.check_model_plan("cuda", plan_shapes.BY_NAME[name], mode, stack_all=stack_all)
+
+
+@pytest.mark.parametrize("name", plan_shapes.DROPOUT_PLANS)
+def test_model_launch_plans_with_dropout(name):
+    """train mode with dropout 0.1 on the generic adjacency chain (T = 70) and on the row-kernel chain with the unfused gate path (C = 72):
+    the site numbering of the fallback paths lines up with the masks the kernels draw (14 sites per block + 7 in the ContextLayer)"""
+    r = checks.check_model_plan("cuda", plan_shapes.BY_NAME[name], "train", dropout=0.1)
+    assert r["dropout_sites"] == 14 * 3 + 7, r["dropout_sites"]
 
 
 @pytest.mark.parametrize("cfg", [(8, 10, 22, 8), (32, 50, 25, 64)], ids=str)
