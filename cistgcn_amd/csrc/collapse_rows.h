@@ -10,7 +10,7 @@ struct CgRowsConv {
   float* y; double* stats;          // stats: optional [CG_STAT_REPLICAS][O][2] f64 sums of y, zero on entry
   // backward
   const float* dy; float* dx; float* dW;
-  float* ws;                        // cg_collapse_rows_ws_floats(C, T, O) zeroed floats
+  float* ws;                        // cg_collapse_rows_ws_floats(C, T, O) floats of scratch (per-slice dW partials; need not be zeroed)
   // optional transform of the input on load (in_on != 0): x' = PReLU(BatchNorm2d(x)) with the BatchNorm `in_bn` over the C input channels
   // and the shared slope in_alpha[0] - the first level of a Map2Adj tower (CISTGCN.py:138-141 / :156-158) folded into the load path
   // of its collapsing convolution, so that the activated tensor is never stored.  Forward: in_bn.stats holds the f64 channel sums

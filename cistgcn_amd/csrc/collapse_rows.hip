@@ -15,7 +15,6 @@ HIP_DYNAMIC_SHARED(unsigned char, cg_dyn_lds)
 #define CG_ROWS_FWD_THREADS 512
 #define CG_ROWS_BWD_THREADS 256
 #define CG_ROWS_KB 64            // rows of W per backward workgroup
-#define CG_ROWS_REPLICAS 8
 
 struct CgRowsGeom { int K, OT, slices, per, kranges; };
 struct CgRowsArgs { CgRowsConv t; CgRowsGeom g; };
@@ -141,19 +140,67 @@ __global__ __launch_bounds__(CG_ROWS_FWD_THREADS) void cg_rows_fwd_kernel(CgRows
 // ======================================================================================================================
 // backward: workgroup = (64 rows k of W, slice of the samples)
 // ======================================================================================================================
+// The dW tile of a backward workgroup ([16 OT][64 rows k], wave w holds the columns 16 w ..) leaves through the LDS that held W: rows along k
+// as 16-byte stores into this slice's partial (float atomics into shared replicas left in one burst at the end of the launch, needed the
+// replicas zeroed and made dW vary from run to run).
+template <int N>
+__device__ __forceinline__ void cg_rows_put_dw(float* sT, const cg_f32x4 (&wacc)[N], int OT, float* part, int O, int K, int k0, int tid, int wave, int l15, int slot) {
+  constexpr int WS = CG_ROWS_KB + 4;
+  __syncthreads();                                                // every wave has read its last W
+#pragma unroll
+  for (int i = 0; i < N; ++i) {
+    if (i < OT) {
+#pragma unroll
+      for (int q = 0; q < 4; ++q) sT[(16 * i + 4 * slot + q) * WS + 16 * wave + l15] = wacc[i][q];
+    }
+  }
+  __syncthreads();
+  for (int e = tid; e < 16 * OT * (CG_ROWS_KB / 4); e += CG_ROWS_BWD_THREADS) {
+    const int o = e >> 4, kk = 4 * (e & 15);
+    if (o < O && k0 + kk < K) *reinterpret_cast<float4*>(part + (long long)o * K + k0 + kk) = *reinterpret_cast<const float4*>(sT + o * WS + kk);      // K % 4 == 0
+  }
+}
+
+// VW consecutive floats (VW * 4 bytes aligned) global <-> registers, no condition: the callers clamp the address
+template <int VW>
+__device__ __forceinline__ void cg_rows_ldv(const float* __restrict__ p, float* v) {
+  if constexpr (VW == 4) {
+    const cg_f32x4 q = *reinterpret_cast<const cg_f32x4*>(p);
+    v[0] = q[0]; v[1] = q[1]; v[2] = q[2]; v[3] = q[3];
+  } else {
+    v[0] = p[0];
+  }
+}
+template <int VW>
+__device__ __forceinline__ void cg_rows_stv(float* __restrict__ p, const float* v) {
+  if constexpr (VW == 4) *reinterpret_cast<cg_f32x4*>(p) = cg_f32x4{v[0], v[1], v[2], v[3]};
+  else p[0] = v[0];
+}
+
 // (128 rows x 512 threads per workgroup: 57 us instead of 44.)
 // (Round 4 tried this kernel with compile-time OT, dy of the next sample through registers and clamped instead of conditional loads:
 // 90 us instead of 100 on the 64-output gate convolutions, but 152 us instead of 47 on the 32-output tower convolutions; not understood,
 // not shipped.)
+// Pieces: the 64 x V piece of x[b] (and of dx[b]) of a workgroup is one contiguous run, and so is the 16 x V piece of each wave: 16 V floats,
+// 16-byte aligned for any V.  A wave moves its piece as runs of VW floats (VW = 4 where dy[b] and the tensors are 16-byte aligned, else 1):
+// x global -> registers -> LDS rows [16][CG_ROWS_XS], where the lanes read their MFMA operand (row l15, four v per slot); the dx tile goes
+// accumulators -> the same LDS rows -> registers -> global.  The rows belong to the wave alone (wave barriers order them); the table `xo`
+// says where the floats of a lane's runs lie in them.  (Before: 16 four-byte loads and 8 four-byte stores per lane and sample, each load
+// instruction across all eleven cache lines of the piece.)
+// Staging is split: the loads of dy[b + 1] and x[b + 1] are issued in front of the matrix work of sample b and stored to LDS behind it
+// (dy[b + 1] used to be waited for and stored in front of the MFMAs of sample b: one exposed memory latency per sample).
+#define CG_ROWS_XS 36            // floats per LDS row of a piece: V <= 32 and four that are never read (column XS - 1 takes the floats of no one)
+template <int VW>
 __global__ __launch_bounds__(CG_ROWS_BWD_THREADS) void cg_rows_bwd_kernel(CgRowsArgs a) {
   const CgRowsConv& t = a.t; const CgRowsGeom& g = a.g;
-  const int K = g.K, V = t.V, O = t.O;
+  const int K = g.K, V = t.V, O = t.O, OV = O * V;
   const int kr = blockIdx.x, sl = blockIdx.y, k0 = kr * CG_ROWS_KB;
   const int b0 = sl * g.per, b1 = min(t.B, b0 + g.per);
   if (b0 >= t.B) return;
+  constexpr int WS = CG_ROWS_KB + 4, DS = 36, XS = CG_ROWS_XS, NG = 8 / VW;
   float* sW = reinterpret_cast<float*>(cg_dyn_lds);              // [16 * OT][KB + 4]  W[o][k0 ..]
-  float* sDY = sW + 16 * g.OT * (CG_ROWS_KB + 4);                 // [2][16 * OT][36]   dy of the current / next sample, v padded with zeros
-  const int WS = CG_ROWS_KB + 4, DS = 36;
+  float* sDY = sW + 16 * g.OT * WS;                               // [2][16 * OT][36]   dy of the current / next sample, v padded with zeros
+  float* sX = sDY + 2 * 16 * g.OT * DS;                           // [4 waves][16][XS]  a wave's piece of x[b + 1], then of dx[b]
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6), l15 = lane & 15, slot = lane >> 4;
   // eight loads of a thread in flight (a load - store loop waits out one memory latency per element: 9 to 17 of them in this prologue)
   for (int e0 = tid; e0 < 16 * g.OT * WS; e0 += 8 * CG_ROWS_BWD_THREADS) {
@@ -170,52 +217,78 @@ __global__ __launch_bounds__(CG_ROWS_BWD_THREADS) void cg_rows_bwd_kernel(CgRows
       if (e < 16 * g.OT * WS) sW[e] = (o < O && kk < CG_ROWS_KB && k0 + kk < K) ? v[j] : 0.f;
     }
   }
-  for (int e = tid; e < 2 * 16 * g.OT * DS; e += CG_ROWS_BWD_THREADS) sDY[e] = 0.f;
+  for (int e = tid; e < 2 * 16 * g.OT * DS + (CG_ROWS_BWD_THREADS / 64) * 16 * XS; e += CG_ROWS_BWD_THREADS) sDY[e] = 0.f;      // sDY and sX
   __syncthreads();
-  auto stage_dy = [&](int b, int buf) {
-    const float* src = t.dy + (long long)b * O * V;
-    float* dst = sDY + buf * 16 * g.OT * DS;
-    for (int e = tid; e < O * V; e += CG_ROWS_BWD_THREADS) { const int o = e / V, v = e - o * V; dst[o * DS + v] = src[e]; }
-  };
-  stage_dy(b0, 0);
   // a wave owns the 16 rows k = k0 + 16 wave + .. of the range: dW tiles [o][k] in registers over the slice
+  const int kw = k0 + 16 * wave;                                 // first row of this wave
+  const int nx = max(0, min(16, K - kw)) * V;                    // floats of this wave's piece (K % 4 == 0: a multiple of 4)
+  float* sXw = sX + wave * 16 * XS;
+  // run r of this lane: the floats VW (lane + 64 r) .. of the wave's piece; outside the piece the first run of the workgroup stands in
+  // for the load (k0 < K), LDS column XS - 1 for the store, and nothing is written to dx
+  int xg[NG], xo[8]; bool xok[NG];
+#pragma unroll
+  for (int r = 0; r < NG; ++r) {
+    const int f = VW * (lane + 64 * r);
+    xok[r] = f < nx;
+    xg[r] = xok[r] ? kw * V + f : k0 * V;
+#pragma unroll
+    for (int i = 0; i < VW; ++i) { const int e = f + i, row = e / V; xo[VW * r + i] = xok[r] ? row * XS + (e - row * V) : XS - 1; }
+  }
+  // the same for dy[b] (O * V floats, all 256 threads): run r of this thread -> [o][DS] rows of sDY
+  int dyg[NG], dyo[8];
+#pragma unroll
+  for (int r = 0; r < NG; ++r) {
+    const int f = VW * (tid + CG_ROWS_BWD_THREADS * r);
+    dyg[r] = f < OV ? f : 0;
+#pragma unroll
+    for (int i = 0; i < VW; ++i) { const int e = f + i, o = e / V; dyo[VW * r + i] = f < OV ? o * DS + (e - o * V) : DS - 1; }
+  }
+  float dr[8], xr[8];
+  auto stage_load = [&](int b) {
+    const float* dyb = t.dy + (long long)b * OV;
+    const float* xb = t.x + (long long)b * K * V;
+#pragma unroll
+    for (int r = 0; r < NG; ++r) cg_rows_ldv<VW>(dyb + dyg[r], dr + VW * r);
+#pragma unroll
+    for (int r = 0; r < NG; ++r) cg_rows_ldv<VW>(xb + xg[r], xr + VW * r);
+  };
+  auto stage_write = [&](int buf) {
+    float* dst = sDY + buf * 16 * g.OT * DS;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) dst[dyo[j]] = dr[j];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) sXw[xo[j]] = xr[j];
+  };
+  stage_load(b0);
+  stage_write(0);
   cg_f32x4 wacc[4];
 #pragma unroll
   for (int i = 0; i < 4; ++i) wacc[i] = cg_f32x4{0.f, 0.f, 0.f, 0.f};
-  const int kw = k0 + 16 * wave;                                 // first row of this wave
-  const bool v0ok = l15 < V, v1ok = 16 + l15 < V;
-  // this lane's share of x[b][kw + l15][:]: four consecutive v per slot (v = 4 slot + s) and the second half (16 + ..);
-  // the next sample's values are requested before the current sample's matrix work
-  const int krow = kw + l15;
-  auto load_x = [&](int b, float xa_[4], float xc_[4]) {
-    const float* xb = t.x + (long long)b * K * V;
-#pragma unroll
-    for (int s = 0; s < 4; ++s) {
-      const int v = 4 * slot + s;
-      xa_[s] = (krow < K && v < V) ? xb[(long long)krow * V + v] : 0.f;
-      xc_[s] = (krow < K && 16 + v < V) ? xb[(long long)krow * V + 16 + v] : 0.f;
-    }
-  };
   // optional input transform (see CgRowsConv.in_on): this lane's row k = (c, t) has ONE channel c; the values outside the tensor meet dy = 0
+  const int krow = kw + l15;
   const bool tr = t.in_on != 0;
   float tm = 0.f, ts = 1.f, tb = 0.f, ta = 1.f;
   if (tr) {
     const CgAff af = cg_tail_aff(t.in_bn, min(krow, K - 1) / t.T, t.C, 0.0, t.in_train, true, false);
     tm = af.mean; ts = af.gamma * af.rstd; tb = af.beta; ta = t.in_alpha[0];
   }
-  auto act = [&](float xv[4]) {
-    if (tr) {
-#pragma unroll
-      for (int s = 0; s < 4; ++s) xv[s] = cg_prelu((xv[s] - tm) * ts + tb, ta);
-    }
-  };
-  float xa[4], xc[4], xna[4], xnc[4];
-  load_x(b0, xa, xc);
-  act(xa); act(xc);
   for (int b = b0; b < b1; ++b) {
     const int buf = (b - b0) & 1;
-    __syncthreads();                                              // dy[b] is in sDY[buf]; the other buffer is free
-    if (b + 1 < b1) { stage_dy(b + 1, buf ^ 1); load_x(b + 1, xna, xnc); }
+    const bool more = b + 1 < b1;
+    __syncthreads();                                              // dy[b] is in sDY[buf], x[b] in the waves' rows; the other dy buffer is free
+    // this lane's share of x[b][kw + l15][:]: four consecutive v per slot (v = 4 slot + s) and the second half (16 + ..); rows outside the
+    // tensor and columns v >= V hold zeros (or what a dx tile left there: W^T dy of zeros), they meet dy = 0 or rows of dW that are not stored
+    const cg_f32x4 xa4 = *reinterpret_cast<const cg_f32x4*>(sXw + l15 * XS + 4 * slot);
+    const cg_f32x4 xc4 = *reinterpret_cast<const cg_f32x4*>(sXw + l15 * XS + 16 + 4 * slot);
+    float xa[4] = {xa4[0], xa4[1], xa4[2], xa4[3]}, xc[4] = {xc4[0], xc4[1], xc4[2], xc4[3]};
+    if (tr) {
+#pragma unroll
+      for (int s = 0; s < 4; ++s) { xa[s] = cg_prelu((xa[s] - tm) * ts + tb, ta); xc[s] = cg_prelu((xc[s] - tm) * ts + tb, ta); }
+    }
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();                              // every lane holds its operand: the rows are free for the dx tile
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    if (more) stage_load(b + 1);                                  // in flight over the matrix work below
     const float* dyb = sDY + buf * 16 * g.OT * DS;
     float* dxb = t.dx + (long long)b * K * V;
     // dx[k][v] = sum_o W[o][k] dy[o][v]: rows k of this wave, both halves of v
@@ -231,11 +304,19 @@ __global__ __launch_bounds__(CG_ROWS_BWD_THREADS) void cg_rows_bwd_kernel(CgRows
     }
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
-      const int k = kw + 4 * slot + q;
-      if (k < K) {
-        if (v0ok) dxb[(long long)k * V + l15] = c0[q];
-        if (v1ok) dxb[(long long)k * V + 16 + l15] = c1[q];
-      }
+      sXw[(4 * slot + q) * XS + l15] = c0[q];
+      sXw[(4 * slot + q) * XS + 16 + l15] = c1[q];
+    }
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    {
+      float dv[8];
+#pragma unroll
+      for (int j = 0; j < 8; ++j) dv[j] = sXw[xo[j]];
+#pragma unroll
+      for (int r = 0; r < NG; ++r)
+        if (xok[r]) cg_rows_stv<VW>(dxb + xg[r], dv + VW * r);
     }
     // dW[o][k] += sum_v dy[o][v] x[k][v]: A[i = o][kk = v] from LDS (float4 along v), B[kk = v][j = k] = this lane's x values
 #pragma unroll
@@ -251,31 +332,28 @@ __global__ __launch_bounds__(CG_ROWS_BWD_THREADS) void cg_rows_bwd_kernel(CgRows
         }
       }
     }
-#pragma unroll
-    for (int s = 0; s < 4; ++s) { xa[s] = xna[s]; xc[s] = xnc[s]; }
-    if (b + 1 < b1) { act(xa); act(xc); }
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();                              // the dx tile has left the rows
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    if (more) stage_write(buf ^ 1);
   }
-  float* ws = t.ws + (long long)(sl % CG_ROWS_REPLICAS) * O * K;
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    if (i < g.OT) {
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const int o = 16 * i + 4 * slot + q, k = kw + l15;
-        if (o < O && k < K) atomicAdd(&ws[(long long)o * K + k], wacc[i][q]);
-      }
-    }
-  }
+  cg_rows_put_dw<4>(sW, wacc, g.OT, t.ws + (long long)sl * O * K, O, K, k0, tid, wave, l15, slot);
 }
 
-__global__ void cg_rows_fold_kernel(CgRowsArgs a) {
+// dW[e] = sum over the slices' partials.  A workgroup takes 64 consecutive elements, its four waves every fourth slice; the order of the
+// sum is fixed, so dW is the same from run to run.
+__global__ __launch_bounds__(CG_ROWS_BWD_THREADS) void cg_rows_fold_kernel(CgRowsArgs a) {
   const CgRowsConv& t = a.t;
+  __shared__ float part[CG_ROWS_BWD_THREADS / 64][64];
   const long long n = (long long)t.O * a.g.K;
-  for (long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x; e < n; e += (long long)gridDim.x * blockDim.x) {
-    float s = 0.f;
-    for (int r = 0; r < CG_ROWS_REPLICAS; ++r) s += t.ws[r * n + e];
-    t.dW[e] = s;
-  }
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const long long e = (long long)blockIdx.x * 64 + lane, ec = e < n ? e : n - 1;
+  float s = 0.f;
+#pragma unroll 4
+  for (int r = wave; r < a.g.slices; r += CG_ROWS_BWD_THREADS / 64) s += t.ws[r * n + ec];
+  part[wave][lane] = s;
+  __syncthreads();
+  if (wave == 0 && e < n) t.dW[e] = (part[0][lane] + part[1][lane]) + (part[2][lane] + part[3][lane]);
 }
 
 // ======================================================================================================================
@@ -429,12 +507,28 @@ __global__ __launch_bounds__(CG_ROWS_BWD_THREADS) void cg_cols_bwd_kernel(CgRows
   }
   for (int e = tid; e < 2 * 16 * OT * DS; e += CG_ROWS_BWD_THREADS) sDY[e] = 0.f;
   __syncthreads();
-  auto stage_dy = [&](int b, int buf) {
+  // dy[b] (O * T <= 256 * OT * NT floats) global -> registers -> [o][DS] rows of sDY, split: the loads of sample b + 1 are issued in front of the
+  // matrix work of sample b and stored behind it.  Element j of this thread; outside dy the first element stands in for the load and
+  // column DS - 1 of row 0, which nobody reads, for the store.
+  int dyo[OT * NT];
+#pragma unroll
+  for (int j = 0; j < OT * NT; ++j) {
+    const int e = tid + CG_ROWS_BWD_THREADS * j, o = e / T;
+    dyo[j] = e < O * T ? o * DS + (e - o * T) : DS - 1;
+  }
+  float dr[OT * NT];
+  auto dy_load = [&](int b) {
     const float* src = t.dy + (long long)b * O * T;
-    float* dst = sDY + buf * 16 * OT * DS;
-    for (int e = tid; e < O * T; e += CG_ROWS_BWD_THREADS) { const int o = e / T, tt = e - o * T; dst[o * DS + tt] = src[e]; }
+#pragma unroll
+    for (int j = 0; j < OT * NT; ++j) { const int e = tid + CG_ROWS_BWD_THREADS * j; dr[j] = src[e < O * T ? e : 0]; }
   };
-  stage_dy(b0, 0);
+  auto dy_write = [&](int buf) {
+    float* dst = sDY + buf * 16 * OT * DS;
+#pragma unroll
+    for (int j = 0; j < OT * NT; ++j) dst[dyo[j]] = dr[j];
+  };
+  dy_load(b0);
+  dy_write(0);
   // a wave owns the 16 rows k = k0 + 16 wave + .. of the range: dW tiles [o][k] in registers over the slice
   cg_f32x4 wacc[OT];
 #pragma unroll
@@ -476,13 +570,20 @@ __global__ __launch_bounds__(CG_ROWS_BWD_THREADS) void cg_cols_bwd_kernel(CgRows
         for (int s = 0; s < 4; ++s) xv[tt][s] = cg_prelu((xv[tt][s] - tm) * ts + tb, ta);
     }
   };
+  // x[b] is taken over from the registers it was loaded into at the top of its own iteration, in front of the loads of sample b + 1: the one
+  // place where a load is waited for (the first sample's operand used to be loaded straight into `xa`; the compiler then could not tell
+  // those loads from the ones in flight and waited out the loads of sample b + 1 in front of the dW products of sample b)
   float xa[NT][4], xn[NT][4];
-  load_x(b0, xa);
-  act(xa);
+  load_x(b0, xn);
   for (int b = b0; b < b1; ++b) {
     const int buf = (b - b0) & 1;
     __syncthreads();                                              // dy[b] is in sDY[buf]; the other buffer is free
-    if (b + 1 < b1) { stage_dy(b + 1, buf ^ 1); load_x(b + 1, xn); }
+#pragma unroll
+    for (int tt = 0; tt < NT; ++tt)
+#pragma unroll
+      for (int s = 0; s < 4; ++s) xa[tt][s] = xn[tt][s];
+    act(xa);
+    if (b + 1 < b1) { dy_load(b + 1); load_x(b + 1, xn); }
     const float* dyb = sDY + buf * 16 * OT * DS;
     float* dxb = t.dx + (long long)b * K * T;
     // dx[k][t] = sum_o W[o][k] dy[o][t]: rows k of this wave, NT tiles of frames
@@ -519,21 +620,9 @@ __global__ __launch_bounds__(CG_ROWS_BWD_THREADS) void cg_cols_bwd_kernel(CgRows
         for (int s = 0; s < 4; ++s) wacc[i] = __builtin_amdgcn_mfma_f32_16x16x4f32(e4[s], xa[tt][s], wacc[i], 0, 0, 0);
       }
     }
-#pragma unroll
-    for (int tt = 0; tt < NT; ++tt)
-#pragma unroll
-      for (int s = 0; s < 4; ++s) xa[tt][s] = xn[tt][s];
-    if (b + 1 < b1) act(xa);
+    if (b + 1 < b1) dy_write(buf ^ 1);
   }
-  float* ws = t.ws + (long long)(sl % CG_ROWS_REPLICAS) * O * K;
-#pragma unroll
-  for (int i = 0; i < OT; ++i) {
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const int o = 16 * i + 4 * slot + q, k = kw + l15;
-      if (o < O && k < K) atomicAdd(&ws[(long long)o * K + k], wacc[i][q]);
-    }
-  }
+  cg_rows_put_dw<OT>(sW, wacc, OT, t.ws + (long long)sl * O * K, O, K, k0, tid, wave, l15, slot);
 }
 
 // ---- host side ---------------------------------------------------------------------------------------------------
@@ -551,7 +640,12 @@ static int cg_rows_geometry(const CgRowsConv* t, CgRowsGeom* g) {
   return CG_OK;
 }
 
-extern "C" long long cg_collapse_rows_ws_floats(int C, int T, int O) { return (long long)CG_ROWS_REPLICAS * O * C * T; }
+// one dW partial per sample slice, for the most slices the geometry can choose at this K (any B)
+static long long cg_rows_ws(long long K, int O) {
+  const long long kranges = (K + CG_ROWS_KB - 1) / CG_ROWS_KB, slices = 768 / kranges;
+  return (slices < 1 ? 1 : slices) * O * K;
+}
+extern "C" long long cg_collapse_rows_ws_floats(int C, int T, int O) { return cg_rows_ws((long long)C * T, O); }
 
 // include/cistgcn_hip.h : cg_collapse_rows_fwd / cg_collapse_rows_bwd
 extern "C" int cg_collapse_rows_fwd(const CgRowsConv* t, void* stream_) {
@@ -588,12 +682,16 @@ extern "C" int cg_collapse_rows_bwd(const CgRowsConv* t, void* stream_) {
   if (!t->dy || !t->dx || !t->dW || !t->ws) return CG_EARG;
   if (t->in_on && (!t->in_alpha || !t->in_bn.gamma || !t->in_bn.beta || !t->in_bn.save)) return CG_EARG;
   a.t = *t;
-  const size_t lds = ((size_t)16 * a.g.OT * (CG_ROWS_KB + 4) + (size_t)2 * 16 * a.g.OT * 36) * sizeof(float);
+  const size_t lds = ((size_t)16 * a.g.OT * (CG_ROWS_KB + 4) + (size_t)2 * 16 * a.g.OT * 36 + (size_t)(CG_ROWS_BWD_THREADS / 64) * 16 * CG_ROWS_XS) * sizeof(float);
   hipStream_t stream = (hipStream_t)stream_;
-  hipLaunchKernelGGL(cg_rows_bwd_kernel, dim3((unsigned)a.g.kranges, (unsigned)a.g.slices), dim3(CG_ROWS_BWD_THREADS), lds, stream, a);
+  const dim3 grid((unsigned)a.g.kranges, (unsigned)a.g.slices), block(CG_ROWS_BWD_THREADS);
+  // 16-byte runs where every sample's dy, x and dx piece is 16-byte aligned (the pieces of x and dx are whole multiples of four floats)
+  const bool wide = ((long long)t->O * t->V) % 4 == 0 && (((uintptr_t)t->dy | (uintptr_t)t->x | (uintptr_t)t->dx) & 15) == 0;
+  if (wide) hipLaunchKernelGGL(cg_rows_bwd_kernel<4>, grid, block, lds, stream, a);
+  else hipLaunchKernelGGL(cg_rows_bwd_kernel<1>, grid, block, lds, stream, a);
   st = cg_launch_status();
   if (st != CG_OK) return st;
-  hipLaunchKernelGGL(cg_rows_fold_kernel, dim3(128), dim3(256), 0, stream, a);
+  hipLaunchKernelGGL(cg_rows_fold_kernel, dim3((unsigned)(((long long)t->O * a.g.K + 63) / 64)), dim3(CG_ROWS_BWD_THREADS), 0, stream, a);
   return cg_launch_status();
 }
 
@@ -615,7 +713,7 @@ static int cg_cols_geometry(const CgRowsConv* t, CgRowsGeom* g) {
 static int cg_cols_nt(int T) { return T <= 16 ? 1 : T <= 32 ? 2 : 4; }
 
 extern "C" int cg_collapse_cols_supported(int C, int T, int V, int O) { return T >= 1 && T <= 64 && O >= 1 && O <= 64 && (((long long)C * V) & 3) == 0 ? 1 : 0; }
-extern "C" long long cg_collapse_cols_ws_floats(int C, int V, int O) { return (long long)CG_ROWS_REPLICAS * O * C * V; }
+extern "C" long long cg_collapse_cols_ws_floats(int C, int V, int O) { return cg_rows_ws((long long)C * V, O); }
 
 // include/cistgcn_hip.h : host-only, the backward grid of cg_collapse_rows_bwd (cols == 0) / cg_collapse_cols_bwd (no launch)
 extern "C" int cg_collapse_geometry(int B, int C, int T, int V, int O, int cols, int* out) {
@@ -684,6 +782,6 @@ extern "C" int cg_collapse_cols_bwd(const CgRowsConv* t, void* stream_) {
 #undef CG_COLS_BWD_LAUNCH
   st = cg_launch_status();
   if (st != CG_OK) return st;
-  hipLaunchKernelGGL(cg_rows_fold_kernel, dim3(128), dim3(256), 0, stream, a);
+  hipLaunchKernelGGL(cg_rows_fold_kernel, dim3((unsigned)(((long long)t->O * a.g.K + 63) / 64)), dim3(CG_ROWS_BWD_THREADS), 0, stream, a);
   return cg_launch_status();
 }

@@ -2442,7 +2442,7 @@ class _CollapseRows(torch.autograd.Function):
         t = _CollapseRows._block(x, w, ctx.tr)
         dx = torch.empty_like(x)
         dw = torch.empty_like(w)
-        zb, _z = _zeros(int(_lib.lib().cg_collapse_rows_ws_floats(C, T, w.shape[0])), x.device)
+        zb = torch.empty(int(_lib.lib().cg_collapse_rows_ws_floats(C, T, w.shape[0])), dtype=torch.float32, device=x.device)      # per-slice dW partials, all written
         t.dy, t.dx, t.dW, t.ws = dy.data_ptr(), dx.data_ptr(), dw.data_ptr(), zb.data_ptr()
         _lib.call("cg_collapse_rows_bwd", ctypes.byref(t), _stream(x))
         return None, None, dx if ctx.needs_input_grad[2] else None, dw if ctx.needs_input_grad[3] else None
@@ -2493,7 +2493,7 @@ class _CollapseCols(torch.autograd.Function):
         t = _CollapseRows._block(x, w, ctx.tr)
         dx = torch.empty_like(x)
         dw = torch.empty_like(w)
-        zb, _z = _zeros(int(_lib.lib().cg_collapse_cols_ws_floats(C, V, w.shape[0])), x.device)
+        zb = torch.empty(int(_lib.lib().cg_collapse_cols_ws_floats(C, V, w.shape[0])), dtype=torch.float32, device=x.device)      # per-slice dW partials, all written
         t.dy, t.dx, t.dW, t.ws = dy.data_ptr(), dx.data_ptr(), dw.data_ptr(), zb.data_ptr()
         _lib.call("cg_collapse_cols_bwd", ctypes.byref(t), _stream(x))
         return None, None, dx if ctx.needs_input_grad[2] else None, dw if ctx.needs_input_grad[3] else None

@@ -247,7 +247,7 @@ typedef struct CgRowsConv {
   const float* x; const float* W;
   float* y; double* stats;          /* stats: optional [CG_STAT_REPLICAS][O][2] f64 sums of y, zero on entry */
   const float* dy; float* dx; float* dW;
-  float* ws;                        /* cg_collapse_rows_ws_floats(C, T, O) zeroed floats */
+  float* ws;                        /* cg_collapse_rows_ws_floats(C, T, O) floats of scratch (need not be zeroed) */
   /* optional transform of the input on load (in_on != 0): x' = PReLU(BatchNorm2d(x)) over the C input channels with the shared slope
    * in_alpha[0]: the first level of a Map2Adj tower (CISTGCN.py:138-141 / :156-158) folded into the load path of its collapsing
    * convolution - the activated tensor is never stored.  Forward: in_bn.stats = f64 channel sums of x (train; workgroup 0 writes
@@ -263,7 +263,7 @@ int cg_collapse_rows_bwd(const CgRowsConv* t, void* stream);
 long long cg_collapse_rows_ws_floats(int C, int T, int O);
 /* The same for the joint axis: nn.Conv2d(C, O, (1, V)) (no bias), second convolution of Map2Adj.joint_compress, CISTGCN.py:152-163.
  * y[b,o,t] = sum_{c,v} W[o,c,v] x[b,c,t,v]; same argument block with W (O, C*V), y (B,O,T), dy (B,O,T), ws of
- * cg_collapse_cols_ws_floats(C, V, O) zeroed floats; T <= 64, O <= 64, C*V % 4 == 0 (cg_collapse_cols_supported; else cg_contract_many). */
+ * cg_collapse_cols_ws_floats(C, V, O) floats of scratch; T <= 64, O <= 64, C*V % 4 == 0 (cg_collapse_cols_supported; else cg_contract_many). */
 int cg_collapse_cols_fwd(const CgRowsConv* t, void* stream);
 int cg_collapse_cols_bwd(const CgRowsConv* t, void* stream);
 int cg_collapse_cols_supported(int C, int T, int V, int O);
