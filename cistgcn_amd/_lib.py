@@ -169,6 +169,11 @@ class EvalMetricsArgs(ctypes.Structure):      # CgEvalMetrics
                 ("out", c_void_p * 9), ("ws", c_void_p)]
 
 
+class AttackMetricsArgs(ctypes.Structure):      # CgAttackMetrics
+    _fields_ = [("B", c_int), ("T", c_int), ("J", c_int), ("pad", c_int),
+                ("adv", c_void_p), ("orig", c_void_p), ("out", c_void_p * 33), ("counts", c_void_p), ("gmax", c_void_p), ("ws", c_void_p)]
+
+
 P = c_void_p
 LL = c_longlong
 _SIGNATURES = {
@@ -256,6 +261,8 @@ _SIGNATURES = {
     "cg_attack_step_max_floats": [],
     "cg_eval_metrics": [POINTER(EvalMetricsArgs), P],
     "cg_eval_metrics_ws_doubles": [c_int, c_int, c_int],
+    "cg_attack_metrics": [POINTER(AttackMetricsArgs), P],
+    "cg_attack_metrics_ws_doubles": [c_int, c_int, c_int],
     "cg_adam_flat": [P, P, P, P, LL, c_float, c_float, c_float, c_float, c_float, c_float, c_float, LL, P],
 }
 EXPORTS = tuple(sorted(_SIGNATURES))

@@ -8,7 +8,7 @@
 // A frame is at most 64 joints x 3 floats; what a lane holds is widened to fp64 once and rounded to fp32 once, at the store, so the
 // distance to an fp64 evaluation is the final rounding.  Nothing is accumulated with floating-point atomics: two calls give the same
 // bits.  Neither pred, target nor speeds is written (the reference divides `speeds` in place, test.py:67).
-#include "cg_common.h"
+#include "eval_frame.h"
 
 #include <math.h>
 
@@ -37,23 +37,6 @@ struct CgEvalMetrics {      // mirrored by include/cistgcn_hip.h and cistgcn_amd
 // w_t = (t + 1) / To in fp32, as `arange(1, To + 1) / To` gives it (test.py:301-302)
 __device__ __forceinline__ double cg_em_wt(int t, int To) { return (double)((float)(t + 1) / (float)To); }
 
-// sum over the wavefront of N values at once, result in every lane (a butterfly: every lane adds the same pairs, so all lanes hold
-// the same bits); the N exchanges of a level are independent
-template <int N>
-__device__ __forceinline__ void cg_em_wave_sum(double (&v)[N]) {
-#pragma unroll
-  for (int off = CG_WAVE / 2; off > 0; off >>= 1) {
-#pragma unroll
-    for (int i = 0; i < N; ++i) v[i] += __shfl_xor(v[i], off, CG_WAVE);
-  }
-}
-
-__device__ __forceinline__ float cg_em_wave_max(float v) {
-#pragma unroll
-  for (int off = CG_WAVE / 2; off > 0; off >>= 1) v = fmaxf(v, __shfl_xor(v, off, CG_WAVE));
-  return v;
-}
-
 // sn + w_t of one joint: sn = speeds / (max over the joints of the frame + 1e-6) (test.py:67-69)
 __device__ __forceinline__ double cg_em_sn(float s, float frame_max) { return (double)s / ((double)frame_max + 1e-6); }
 
@@ -81,72 +64,6 @@ __global__ __launch_bounds__(CG_EM_PRE_THREADS) void cg_em_batch_max_kernel(cons
     __syncthreads();
   }
 }
-
-// ---------------------------------------------------------------------------------------------
-// 3x3 Procrustes rotation.  H = U diag(s) V^T; the reference forms R = V' U^T with the last ROW of V scaled by sigma = sign det(V U^T)
-// (losses.py:106-119), i.e. R = diag(1,1,sigma) V U^T, and V U^T is the transposed polar factor of H: it does not depend on the signs
-// or the order a particular SVD gives its vectors.  V and s^2 come from cyclic Jacobi rotations of H^T H in fp64, u_i = H v_i / s_i for
-// the two larger singular values and u_3 = +-(u_1 x u_2), on the side of H v_3 (so a flat pose, s_3 = 0, still has a rotation).
-// Every lane of the wave runs this on the same numbers.
-// ---------------------------------------------------------------------------------------------
-#define CG_EM_ROTATE(p, q, r)                                                              \
-  if (A[p][q] != 0.0) {                                                                    \
-    const double theta = (A[q][q] - A[p][p]) / (2.0 * A[p][q]);                            \
-    const double tt = (theta < 0.0 ? -1.0 : 1.0) / (fabs(theta) + sqrt(theta * theta + 1.0)); \
-    const double c = 1.0 / sqrt(tt * tt + 1.0), s = tt * c;                                \
-    const double apq = A[p][q], arp = A[r][p], arq = A[r][q];                              \
-    A[p][p] -= tt * apq;                                                                   \
-    A[q][q] += tt * apq;                                                                   \
-    A[p][q] = A[q][p] = 0.0;                                                               \
-    A[r][p] = A[p][r] = c * arp - s * arq;                                                 \
-    A[r][q] = A[q][r] = s * arp + c * arq;                                                 \
-    for (int k = 0; k < 3; ++k) {                                                          \
-      const double vp = V[k][p], vq = V[k][q];                                             \
-      V[k][p] = c * vp - s * vq;                                                           \
-      V[k][q] = s * vp + c * vq;                                                           \
-    }                                                                                      \
-  }
-
-#define CG_EM_SWAP_COLS(i, j)                                                              \
-  {                                                                                        \
-    const double l = lam[i]; lam[i] = lam[j]; lam[j] = l;                                  \
-    for (int k = 0; k < 3; ++k) { const double v = V[k][i]; V[k][i] = V[k][j]; V[k][j] = v; } \
-  }
-
-// R0 = V U^T and the singular values of H (sv[2] the smallest)
-__device__ __forceinline__ void cg_em_polar(const double (&H)[3][3], double (&R0)[3][3], double (&sv)[3]) {
-  double A[3][3], V[3][3] = {{1.0, 0.0, 0.0}, {0.0, 1.0, 0.0}, {0.0, 0.0, 1.0}};
-#pragma unroll
-  for (int i = 0; i < 3; ++i)
-#pragma unroll
-    for (int j = 0; j < 3; ++j) A[i][j] = H[0][i] * H[0][j] + H[1][i] * H[1][j] + H[2][i] * H[2][j];
-  for (int sweep = 0; sweep < 8; ++sweep) {       // quadratic convergence: 3x3 is at fp64 rounding after 5 sweeps
-    CG_EM_ROTATE(0, 1, 2)
-    CG_EM_ROTATE(0, 2, 1)
-    CG_EM_ROTATE(1, 2, 0)
-  }
-  double lam[3] = {A[0][0], A[1][1], A[2][2]};
-  if (lam[0] < lam[2]) CG_EM_SWAP_COLS(0, 2)
-  if (lam[1] < lam[2]) CG_EM_SWAP_COLS(1, 2)
-  double U[3][3];      // U[c][m]: component c of u_m
-#pragma unroll
-  for (int m = 0; m < 3; ++m) {
-    sv[m] = sqrt(fmax(lam[m], 0.0));
-#pragma unroll
-    for (int c = 0; c < 3; ++c) U[c][m] = H[c][0] * V[0][m] + H[c][1] * V[1][m] + H[c][2] * V[2][m];      // H v_m, scaled below
-  }
-#pragma unroll
-  for (int c = 0; c < 3; ++c) { U[c][0] /= sv[0]; U[c][1] /= sv[1]; }
-  const double x0 = U[1][0] * U[2][1] - U[2][0] * U[1][1], x1 = U[2][0] * U[0][1] - U[0][0] * U[2][1], x2 = U[0][0] * U[1][1] - U[1][0] * U[0][1];
-  const double side = x0 * U[0][2] + x1 * U[1][2] + x2 * U[2][2] < 0.0 ? -1.0 : 1.0;
-  U[0][2] = side * x0; U[1][2] = side * x1; U[2][2] = side * x2;
-#pragma unroll
-  for (int r = 0; r < 3; ++r)
-#pragma unroll
-    for (int c = 0; c < 3; ++c) R0[r][c] = V[r][0] * U[c][0] + V[r][1] * U[c][1] + V[r][2] * U[c][2];
-}
-
-__device__ __forceinline__ double cg_em_norm3(double a, double b, double c) { return sqrt(a * a + b * b + c * c); }
 
 // ---------------------------------------------------------------------------------------------
 // the main pass: wave w of workgroup g takes frames g * CG_EM_WAVES + w, + gridDim.x * CG_EM_WAVES, ...
@@ -178,60 +95,8 @@ __global__ __launch_bounds__(CG_EM_THREADS) void cg_eval_metrics_kernel(CgEvalMe
         mve = cg_em_norm3(d[0], d[1], d[2]);
       }
     }
-    const double e = cg_em_norm3(P[0] - X[0], P[1] - X[1], P[2] - X[2]);
-
-    // sums over the joints, first round: centroids and the two means of n_mpjpe (lanes past J hold zeros)
-    double r1[8] = {X[0], X[1], X[2], P[0], P[1], P[2], X[0] * P[0] + X[1] * P[1] + X[2] * P[2], P[0] * P[0] + P[1] * P[1] + P[2] * P[2]};
-    cg_em_wave_sum(r1);
-    const double scale = (r1[6] / J) / (r1[7] / J);
-    const double en = cg_em_norm3(scale * P[0] - X[0], scale * P[1] - X[1], scale * P[2] - X[2]);
-
-    // second round: the centred poses, the reference's replacement of small target coordinates, norms and X0^T Y0
-    double muX[3], muY[3], X0[3], Y0[3];
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-      muX[c] = r1[c] / J;
-      muY[c] = r1[3 + c] / J;
-      X0[c] = on ? X[c] - muX[c] : 0.0;
-      Y0[c] = on ? P[c] - muY[c] : 0.0;
-      if (on && X0[c] * X0[c] < 1e-6) X0[c] = 1e-3;      // losses.py:94, kept as it is
-    }
-    double r2[11];
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-#pragma unroll
-      for (int j = 0; j < 3; ++j) r2[3 * i + j] = X0[i] * Y0[j];
-    r2[9] = X0[0] * X0[0] + X0[1] * X0[1] + X0[2] * X0[2];
-    r2[10] = Y0[0] * Y0[0] + Y0[1] * Y0[1] + Y0[2] * Y0[2];
-    cg_em_wave_sum(r2);
-    const double normX = fmax(sqrt(r2[9]), 1e-3), normY = sqrt(r2[10]);
-    double H[3][3], R[3][3], sv[3];
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-#pragma unroll
-      for (int j = 0; j < 3; ++j) H[i][j] = r2[3 * i + j] / (normX * normY);      // 0 / 0 = NaN when every predicted joint coincides
-    cg_em_polar(H, R, sv);
-    const double det = R[0][0] * (R[1][1] * R[2][2] - R[1][2] * R[2][1]) - R[0][1] * (R[1][0] * R[2][2] - R[1][2] * R[2][0]) +
-                       R[0][2] * (R[1][0] * R[2][1] - R[1][1] * R[2][0]);
-    const double sigma = det > 0.0 ? 1.0 : (det < 0.0 ? -1.0 : det);      // torch.sign: 0 stays 0, NaN stays NaN
-    double al = (sv[0] + sv[1] + sigma * sv[2]) * normX / normY, tr[3];
-#pragma unroll
-    for (int c = 0; c < 3; ++c) R[2][c] *= sigma;
-#pragma unroll
-    for (int c = 0; c < 3; ++c) tr[c] = muX[c] - al * (muY[0] * R[0][c] + muY[1] * R[1][c] + muY[2] * R[2][c]);
-    // losses.py:130-132, element by element: NaN in the scale -> 1, in the rotation -> 0, in the translation -> 0
-    if (al != al) al = 1.0;
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-      if (tr[c] != tr[c]) tr[c] = 0.0;
-#pragma unroll
-      for (int r = 0; r < 3; ++r)
-        if (R[r][c] != R[r][c]) R[r][c] = 0.0;
-    }
-    double dpa[3];
-#pragma unroll
-    for (int c = 0; c < 3; ++c) dpa[c] = al * (P[0] * R[0][c] + P[1] * R[1][c] + P[2] * R[2][c]) + tr[c] - X[c];
-    const double epa = cg_em_norm3(dpa[0], dpa[1], dpa[2]);
+    double e, en, epa;
+    cg_em_frame_errors(P, X, on, J, e, en, epa);
 
     // the speed weights
     const float smax = cg_em_wave_max(sp);

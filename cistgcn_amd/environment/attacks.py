@@ -121,6 +121,19 @@ class _Attack:
             from ..runtime import _drop_graph_attributes
             _drop_graph_attributes(model)
 
+    def metrics(self, adv, orig, queries=None):
+        """The reference's "adversarial_metrics" dictionary for this batch (`_get_metrics(adv_inputs, inputs)`, test.py:205;
+        adversarial_attacks.py:187-342): how far `adv` (B,T,V,3) moved from the clean `orig`.  "metric_type" is `typ_eval`, "queries" the
+        given per-sample vector (`apply(...)["queries"]`) or 0 as for the one-step attacks (:154), and the 33 numeric entries of
+        `ops.ATTACK_METRICS` are numpy fp32, computed by `ops.attack_metrics` and fetched with one device-to-host copy.  The reference's
+        velocity-input branch (:238-301) serves MlpMixer only and has no counterpart."""
+        flat, layout, _, _ = ops._attack_metrics_flat(adv.detach(), orig.detach())
+        host = flat.cpu().numpy()
+        res = {"metric_type": self.typ_eval, "queries": 0 if queries is None else queries}
+        for k, (at, shape) in layout.items():
+            res[k] = host[at:at + (shape[0] if shape else 1)].reshape(shape)
+        return res
+
     def _apply(self, model, x0, target):
         B = x0.shape[0]
         state = ops.AttackState(B, x0.device)

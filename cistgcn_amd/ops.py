@@ -1398,6 +1398,75 @@ def eval_metrics(pred, target, speeds, bones, reduce="frames"):
     return out
 
 
+# order of CgAttackMetrics.out (include/cistgcn_hip.h): the numeric entries of the reference's "adversarial_metrics" dictionary
+_ATTACK_SUFFIXES = ("mpjpe", "n_mpjpe", "pa_mpjpe", "hausdorff_mean", "hausdorff_max", "mse", "cos_simil", "KLD", "JSD", "KSTest")
+ATTACK_METRICS = (("mpjpe", "n_mpjpe", "pa_mpjpe") + tuple("temporal_" + s for s in _ATTACK_SUFFIXES) + tuple("spatial_" + s for s in _ATTACK_SUFFIXES)
+                  + tuple(("cosine_simil" if s == "cos_simil" else s) + "_sample" for s in _ATTACK_SUFFIXES))
+ATTACK_BINS = 64
+
+
+def _attack_metrics_layout(B, T, J):
+    """name -> (offset, shape) of the 33 results inside one flat fp32 buffer, and its length"""
+    sizes = {"temporal": T, "spatial": J, "sample": B}
+    layout, at = {}, 0
+    for k in ATTACK_METRICS:
+        fam = "temporal" if k.startswith("temporal_") else "spatial" if k.startswith("spatial_") else "sample" if k.endswith("_sample") else None
+        layout[k] = (at, (sizes[fam],) if fam else ())
+        at += sizes[fam] if fam else 1
+    return layout, at
+
+
+def _attack_metrics_flat(adv, orig):
+    """the launch behind `attack_metrics`: (flat fp32 results, layout, counts, histogram ranges)"""
+    if adv.dtype != torch.float32 or orig.dtype != torch.float32:
+        raise ValueError("attack_metrics: adv and orig must be float32, got %s and %s" % (adv.dtype, orig.dtype))
+    if adv.dim() != 4 or adv.shape != orig.shape or adv.shape[3] != 3:
+        raise ValueError("attack_metrics: expected adv and orig of one shape (B,T,J,3), got %s and %s" % (tuple(adv.shape), tuple(orig.shape)))
+    if adv.device != orig.device:
+        raise ValueError("attack_metrics: adv is on %s, orig on %s" % (adv.device, orig.device))
+    B, T, J, _ = adv.shape
+    if B < 1 or T < 1 or J < 2 or J > 64:
+        raise ValueError("attack_metrics: needs B >= 1, T >= 1 and 2 <= J <= 64, got B=%d T=%d J=%d" % (B, T, J))
+    stream = _stream(adv)      # refuses host tensors before anything is allocated or launched
+    adv = adv if adv.is_contiguous() else _copy(adv)
+    orig = orig if orig.is_contiguous() else _copy(orig)
+    dev = adv.device
+    layout, n = _attack_metrics_layout(B, T, J)
+    flat = torch.empty(n, dtype=torch.float32, device=dev)
+    G = B + T + J
+    counts = torch.empty(2 * G * ATTACK_BINS, dtype=torch.int32, device=dev)      # zero-filled by the call
+    gmax = torch.empty(G, dtype=torch.float32, device=dev)
+    ws = torch.empty(int(_lib.lib().cg_attack_metrics_ws_doubles(B, T, J)), dtype=torch.float64, device=dev)
+    a = _lib.AttackMetricsArgs()
+    a.B, a.T, a.J = B, T, J
+    a.adv, a.orig, a.counts, a.gmax, a.ws = _ptr(adv), _ptr(orig), _ptr(counts), _ptr(gmax), _ptr(ws)
+    for q, k in enumerate(ATTACK_METRICS):
+        a.out[q] = flat.data_ptr() + 4 * layout[k][0]
+    _lib.call("cg_attack_metrics", ctypes.byref(a), stream)
+    return flat, layout, counts, gmax
+
+
+def attack_metrics(adv, orig, return_counts=False):
+    """How far the attacked input `adv` moved from the clean `orig`, both (B,T,J,3) with 2 <= J <= 64: the 33 numeric entries of
+    `ComputeAttackMetrics._get_metrics(adv_inputs, inputs)` (adversarial_attacks.py:187-342, test.py:205) as a dict of fp32 device
+    tensors under the names in `ATTACK_METRICS` - three scalars, `temporal_*` (T,), `spatial_*` (J,) and `*_sample` (B,).  `adv` is
+    `predicted` and `orig` is `target` in n_mpjpe / pa_mpjpe, the Hausdorff distances take for every point of `adv` the nearest of
+    `orig`, KLD is KL(adv || orig).  KLD / JSD / KSTest of a group whose joints all coincide (histogram range 0) are NaN.
+    return_counts=True adds the histograms behind the last three: int32 `counts_sample` (2,B,64), `counts_temporal` (2,T,64),
+    `counts_spatial` (2,J,64) (index 0 `adv`, 1 `orig`) and their ranges `max_sample`, `max_temporal`, `max_spatial`.
+    No input is written, nothing is read back, two calls give the same bits."""
+    flat, layout, counts, gmax = _attack_metrics_flat(adv, orig)
+    out = {k: flat[at:at + (shape[0] if shape else 1)].view(shape) for k, (at, shape) in layout.items()}
+    if return_counts:
+        B, T, J, _ = adv.shape
+        at = 0
+        for fam, n in (("sample", B), ("temporal", T), ("spatial", J)):
+            out["counts_" + fam] = counts[2 * at * ATTACK_BINS:2 * (at + n) * ATTACK_BINS].view(2, n, ATTACK_BINS)
+            out["max_" + fam] = gmax[at:at + n]
+            at += n
+    return out
+
+
 def cumsum_time(x):
     """cumulative sum over axis 1 of a 4-D (possibly strided) tensor"""
     return _Cumsum.apply(x)

@@ -567,6 +567,37 @@ typedef struct CgEvalMetrics {
 int cg_eval_metrics(const CgEvalMetrics* a, void* stream);
 long long cg_eval_metrics_ws_doubles(int B, int To, int J);
 
+/* ---- attack distortion metrics (csrc/attack_metrics.hip) ---------------------------------------------
+ * The numeric entries of the "adversarial_metrics" dictionary (environment/adversarial_attacks.py::ComputeAttackMetrics._get_metrics
+ * :187-342, called as `_get_metrics(adv_inputs, inputs)` at environment/test.py:205): adv is the reference's `in_seq`, orig its `adv_seq`.
+ * out[0..2] = mpjpe, n_mpjpe, pa_mpjpe (one value each, :192,:198,:204); then three families of ten, out[3 + 10 * family + q] with
+ * family 0 temporal_* (T,), 1 spatial_* (J,), 2 *_sample (B,) and q in the order
+ *   0 mpjpe          losses.mpjpe (losses/losses.py:50-61), |adv - orig|                          (:189-193)
+ *   1 n_mpjpe        losses.n_mpjpe (:147-160), adv is `predicted`                               (:195-199)
+ *   2 pa_mpjpe       losses.pa_mpjpe (:79-144), as in cg_eval_metrics                            (:201-205)
+ *   3 hausdorff_mean HausdorffDistance("mean") (:106-147): min over the points of orig for every point of adv    (:212-214)
+ *   4 hausdorff_max  HausdorffDistance("max")                                                    (:216-218)
+ *   5 mse            nn.MSELoss(reduction='none')                                                (:232-234)
+ *   6 cos_simil      nn.CosineSimilarity(eps=1e-6): over the flattened sample, else along the batch axis and averaged (:207-210)
+ *   7 KLD            CustomKLD(bins=64) (:72-85), KL(adv || orig)                                (:220-222)
+ *   8 JSD            CustomJSD(bins=64) (:55-69)                                                 (:224-226)
+ *   9 KSTest         CustomKolmogorovSmirnovTest(bins=64) (:88-103)                              (:228-230)
+ * The last three are over 64-bin density histograms of the joint-to-joint distances inside a frame (convert_to_dists :39-48), grouped
+ * by sample, frame index or first joint; the 65 edges run from 0 to the group's maximum over both tensors, edge k = fl32(k / 64) * max
+ * in fp32, and the binned distances carry the reference's fp32 bits.  A group whose maximum is 0 (all its joints coincide) gives NaN
+ * in these three.  counts: int32 [2][B][64] | [2][T][64] | [2][J][64] (0 adv, 1 orig), zero-filled here; gmax: [B] | [T] | [J].
+ * adv / orig contiguous and never written; B >= 1, T >= 1, 2 <= J <= 64, else CG_ESHAPE.  ws: cg_attack_metrics_ws_doubles(B,T,J)
+ * doubles (0 for an unsupported shape).  No floating-point atomics: two calls give the same bits. */
+typedef struct CgAttackMetrics {
+  int B, T, J, pad;
+  const float* adv; const float* orig;
+  float* out[33];
+  int32_t* counts; float* gmax;
+  double* ws;
+} CgAttackMetrics;
+int cg_attack_metrics(const CgAttackMetrics* a, void* stream);
+long long cg_attack_metrics_ws_doubles(int B, int T, int J);
+
 #ifdef __cplusplus
 }
 #endif
