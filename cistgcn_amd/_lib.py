@@ -255,6 +255,7 @@ _SIGNATURES = {
     "cg_stgcn_domain_geometry": [c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, POINTER(c_int)],
     "cg_block_input_geometry": [c_int, c_int, c_int, c_int, POINTER(c_int)],
     "cg_norm_act_rows_per_block": [POINTER(View4)],
+    "cg_glue_geometry": [c_int, c_int, c_int, POINTER(c_int)],
     "cg_mpjpe_sample_fwd": [P, P, P, c_int, c_int, P],
     "cg_mpjpe_sample_bwd": [P, P, P, P, c_int, c_int, P],
     "cg_attack_step": [POINTER(AttackStep), P],

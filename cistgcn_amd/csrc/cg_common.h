@@ -55,6 +55,21 @@ static inline hipError_t cg_lds_limit(const void* fn, size_t bytes) {
   return hipSuccess;
 }
 
+// ---- limits of the glue launchers (stages.hip, optim.hip, rowops.hip), named so that cg_glue_geometry (stages.hip) answers from
+// the numbers the launchers use: grids of the grid-stride kernels, the register budget of the sliced SE-gate backward, the
+// dynamic LDS a kernel may take before cg_lds_limit has to raise its limit
+#define CG_GLUE_THREADS 256
+#define CG_MPJPE_MAX_BLOCKS 1024               // cg_mpjpe_fwd: one float atomic per workgroup onto the loss
+#define CG_FLAT_MAX_BLOCKS 2048                // cg_adam_flat, cg_scale
+#define CG_ZERO_MAX_BLOCKS 4096                // cg_zero_fill, 16 bytes per thread and pass
+#define CG_SE_THREADS 256
+#define CG_SE_MAXACC 8                         // sliced SE-gate backward: C * H <= CG_SE_THREADS * CG_SE_MAXACC
+#define CG_SE_MAX_WORKGROUPS 64
+#define CG_LDS_DEFAULT (64 * 1024)
+#define CG_DSTD_THREADS 1024
+#define CG_DSTD_ROWS_IN_FLIGHT 4
+#define CG_DSTD_LDS_MAX (160 * 1024)
+
 static inline int cg_launch_status() {
   hipError_t e = hipGetLastError();
   return e == hipSuccess ? CG_OK : (int)e;

@@ -29,9 +29,9 @@ extern "C" int cg_adam_flat(float* param, const float* grad, float* exp_avg, flo
   if (n <= 0 || step_count <= 0) return CG_ESHAPE;
   const float bc1 = 1.f - powf(beta1, (float)step_count);
   const float bc2_sqrt = sqrtf(1.f - powf(beta2, (float)step_count));
-  long long blocks = (n + 255) / 256;
-  if (blocks > 2048) blocks = 2048;
-  hipLaunchKernelGGL(cg_adam_flat_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream_, param, grad, exp_avg, exp_avg_sq,
+  long long blocks = (n + CG_GLUE_THREADS - 1) / CG_GLUE_THREADS;
+  if (blocks > CG_FLAT_MAX_BLOCKS) blocks = CG_FLAT_MAX_BLOCKS;
+  hipLaunchKernelGGL(cg_adam_flat_kernel, dim3((unsigned)blocks), dim3(CG_GLUE_THREADS), 0, (hipStream_t)stream_, param, grad, exp_avg, exp_avg_sq,
                      n, lr, beta1, beta2, eps, weight_decay, grad_scale, clip_value, bc1, bc2_sqrt);
   return cg_launch_status();
 }
@@ -75,8 +75,8 @@ __global__ void cg_scale_kernel(float* __restrict__ p, long long n, float s) {
 extern "C" int cg_scale(float* p, long long n, float s, void* stream_) {
   if (!p) return CG_EARG;
   if (n <= 0) return CG_ESHAPE;
-  long long blocks = (n + 255) / 256;
-  if (blocks > 2048) blocks = 2048;
-  hipLaunchKernelGGL(cg_scale_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream_, p, n, s);
+  long long blocks = (n + CG_GLUE_THREADS - 1) / CG_GLUE_THREADS;
+  if (blocks > CG_FLAT_MAX_BLOCKS) blocks = CG_FLAT_MAX_BLOCKS;
+  hipLaunchKernelGGL(cg_scale_kernel, dim3((unsigned)blocks), dim3(CG_GLUE_THREADS), 0, (hipStream_t)stream_, p, n, s);
   return cg_launch_status();
 }

@@ -800,10 +800,10 @@ int cg_zero_fill(void* p, long long bytes, hipStream_t stream) {
   if (head > 0) hipLaunchKernelGGL(cg_zero_kernel, dim3(1), dim3(64), 0, stream, (uint4*)nullptr, 0LL, b, (int)head);
   if (body > 0 || tail > 0) {
     const long long n16 = body / 16;
-    long long blocks = (n16 + 255) / 256;
+    long long blocks = (n16 + CG_GLUE_THREADS - 1) / CG_GLUE_THREADS;
     if (blocks < 1) blocks = 1;
-    if (blocks > 4096) blocks = 4096;
-    hipLaunchKernelGGL(cg_zero_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, reinterpret_cast<uint4*>(b + head), n16,
+    if (blocks > CG_ZERO_MAX_BLOCKS) blocks = CG_ZERO_MAX_BLOCKS;
+    hipLaunchKernelGGL(cg_zero_kernel, dim3((unsigned)blocks), dim3(CG_GLUE_THREADS), 0, stream, reinterpret_cast<uint4*>(b + head), n16,
                        b + head + body, (int)tail);
   }
   return cg_launch_status();

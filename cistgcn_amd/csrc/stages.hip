@@ -88,7 +88,7 @@ extern "C" int cg_feature_lift_bwd(const float* x, const float* df, float* dx, l
 HIP_DYNAMIC_SHARED(unsigned char, cg_dyn_lds)
 
 // lanes that share a row of V values: 16, 32 or 64 (a row wider than 64 is walked in steps of 64)
-__device__ __forceinline__ int cg_stats_lpr(int V) { return V <= 16 ? 16 : V <= 32 ? 32 : 64; }
+__host__ __device__ __forceinline__ int cg_stats_lpr(int V) { return V <= 16 ? 16 : V <= 32 ? 32 : 64; }
 // sum over the `lpr` lanes of a row group, in every lane of the group
 __device__ __forceinline__ float cg_stats_group_sum(float v, int lpr) {
   v = cg_row16_sum(v);
@@ -101,13 +101,13 @@ __device__ __forceinline__ float cg_stats_group_sum(float v, int lpr) {
 // values stay in registers between the two sums), then per-c mean and std
 __device__ __forceinline__ void cg_stats_rows(const float* xb, int C, int T, int V, float* rm, float* rq, float* cm, float* cs) {
   const int lpr = cg_stats_lpr(V), gl = threadIdx.x & (lpr - 1), grp = threadIdx.x / lpr, ngrp = blockDim.x / lpr;
-  const int rows = C * T, iters = (rows + 4 * ngrp - 1) / (4 * ngrp);
+  const int rows = C * T, iters = (rows + CG_DSTD_ROWS_IN_FLIGHT * ngrp - 1) / (CG_DSTD_ROWS_IN_FLIGHT * ngrp);
   for (int it = 0; it < iters; ++it) {                 // every lane runs every iteration: the group sums are wave-wide exchanges
     float x0[4], s[4], m[4], q[4];
     int rr[4];
 #pragma unroll
     for (int k = 0; k < 4; ++k) {                      // four rows per group in flight
-      rr[k] = (4 * it + k) * ngrp + grp;
+      rr[k] = (CG_DSTD_ROWS_IN_FLIGHT * it + k) * ngrp + grp;
       const bool ok = rr[k] < rows && gl < V;
       x0[k] = ok ? xb[(long long)rr[k] * V + gl] : 0.f;
     }
@@ -142,7 +142,7 @@ __device__ __forceinline__ void cg_stats_rows(const float* xb, int C, int T, int
   __syncthreads();
 }
 
-__global__ __launch_bounds__(1024) void cg_dstd_stats_fwd_kernel(const float* __restrict__ x, float* __restrict__ out, int C, int T, int V) {
+__global__ __launch_bounds__(CG_DSTD_THREADS) void cg_dstd_stats_fwd_kernel(const float* __restrict__ x, float* __restrict__ out, int C, int T, int V) {
   float* rm = (float*)cg_dyn_lds;
   float* rq = rm + C * T;
   float* cm = rq + C * T;
@@ -174,7 +174,7 @@ __global__ __launch_bounds__(1024) void cg_dstd_stats_fwd_kernel(const float* __
 }
 
 // backward: d x[c,t,v] = x * P[c,t] + Q[c,t] with row coefficients from the four statistics' gradients
-__global__ __launch_bounds__(1024) void cg_dstd_stats_bwd_kernel(const float* __restrict__ x, const float* __restrict__ dout, float* __restrict__ dx,
+__global__ __launch_bounds__(CG_DSTD_THREADS) void cg_dstd_stats_bwd_kernel(const float* __restrict__ x, const float* __restrict__ dout, float* __restrict__ dx,
                                          int C, int T, int V) {
   float* rm = (float*)cg_dyn_lds;
   float* rq = rm + C * T;
@@ -233,18 +233,37 @@ static size_t cg_dstd_lds(int C, int T) { return (size_t)(4 * C * T + 2 * C + 2 
 
 extern "C" int cg_dstd_stats_fwd(const float* x, float* out, int B, int C, int T, int V, void* stream_) {
   if (!x || !out) return CG_EARG;
-  if (B <= 0 || C < 2 || T <= 0 || V < 2 || cg_dstd_lds(C, T) > 160 * 1024) return CG_ESHAPE;
-  if (cg_lds_limit((const void*)cg_dstd_stats_fwd_kernel, cg_dstd_lds(C, T)) != hipSuccess) return CG_ESHAPE;
-  hipLaunchKernelGGL(cg_dstd_stats_fwd_kernel, dim3(B), dim3(1024), cg_dstd_lds(C, T), (hipStream_t)stream_, x, out, C, T, V);
+  if (B <= 0 || C < 2 || T <= 0 || V < 2 || cg_dstd_lds(C, T) > CG_DSTD_LDS_MAX) return CG_ESHAPE;
+  if (cg_dstd_lds(C, T) > CG_LDS_DEFAULT && cg_lds_limit((const void*)cg_dstd_stats_fwd_kernel, cg_dstd_lds(C, T)) != hipSuccess) return CG_ESHAPE;
+  hipLaunchKernelGGL(cg_dstd_stats_fwd_kernel, dim3(B), dim3(CG_DSTD_THREADS), cg_dstd_lds(C, T), (hipStream_t)stream_, x, out, C, T, V);
   return cg_launch_status();
 }
 
 extern "C" int cg_dstd_stats_bwd(const float* x, const float* dout, float* dx, int B, int C, int T, int V, void* stream_) {
   if (!x || !dout || !dx) return CG_EARG;
-  if (B <= 0 || C < 2 || T <= 0 || V < 2 || cg_dstd_lds(C, T) > 160 * 1024) return CG_ESHAPE;
-  if (cg_lds_limit((const void*)cg_dstd_stats_bwd_kernel, cg_dstd_lds(C, T)) != hipSuccess) return CG_ESHAPE;
-  hipLaunchKernelGGL(cg_dstd_stats_bwd_kernel, dim3(B), dim3(1024), cg_dstd_lds(C, T), (hipStream_t)stream_, x, dout, dx, C, T, V);
+  if (B <= 0 || C < 2 || T <= 0 || V < 2 || cg_dstd_lds(C, T) > CG_DSTD_LDS_MAX) return CG_ESHAPE;
+  if (cg_dstd_lds(C, T) > CG_LDS_DEFAULT && cg_lds_limit((const void*)cg_dstd_stats_bwd_kernel, cg_dstd_lds(C, T)) != hipSuccess) return CG_ESHAPE;
+  hipLaunchKernelGGL(cg_dstd_stats_bwd_kernel, dim3(B), dim3(CG_DSTD_THREADS), cg_dstd_lds(C, T), (hipStream_t)stream_, x, dout, dx, C, T, V);
   return cg_launch_status();
+}
+
+// include/cistgcn_hip.h : cg_glue_geometry (host only)
+extern "C" int cg_glue_geometry(int C, int T, int V, int* out) {
+  if (!out) return CG_EARG;
+  if (C < 2 || T <= 0 || V < 2) return CG_ESHAPE;
+  const int lpr = cg_stats_lpr(V), per = CG_DSTD_ROWS_IN_FLIGHT * (CG_DSTD_THREADS / lpr), rows = C * T;
+  out[0] = CG_MPJPE_MAX_BLOCKS * CG_GLUE_THREADS;
+  out[1] = CG_FLAT_MAX_BLOCKS * CG_GLUE_THREADS;
+  out[2] = CG_ZERO_MAX_BLOCKS * CG_GLUE_THREADS * 16;
+  out[3] = CG_SE_THREADS * CG_SE_MAXACC;
+  out[4] = CG_SE_MAX_WORKGROUPS;
+  out[5] = CG_LDS_DEFAULT;
+  out[6] = cg_dstd_lds(C, T) > CG_DSTD_LDS_MAX ? -1 : (int)cg_dstd_lds(C, T);
+  out[7] = lpr;
+  out[8] = per;
+  out[9] = (rows + per - 1) / per;
+  out[10] = rows - (out[9] - 1) * per;
+  return CG_OK;
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -312,8 +331,6 @@ __global__ void cg_se_gate_bwd_kernel(const float* __restrict__ pooled, const fl
 // The same gradients with the weight gradients kept in registers: a workgroup walks a slice of the batch and adds its dW1 / dW2
 // partial sums once at the end.  One workgroup per sample sent B atomics to every one of the 2 C H addresses (B = 256: 24 us for a
 // 64 x 8 gate, 80 us for the 3 x 1 gate of the output block, where all of them hit the same six words).
-#define CG_SE_THREADS 256
-#define CG_SE_MAXACC 8                         // C * H <= CG_SE_THREADS * CG_SE_MAXACC
 __global__ __launch_bounds__(CG_SE_THREADS) void cg_se_gate_bwd_sliced_kernel(const float* __restrict__ pooled, const float* __restrict__ W1,
                                                                                const float* __restrict__ W2, const float* __restrict__ gate,
                                                                                const float* __restrict__ dgate, float* __restrict__ dpooled,
@@ -384,7 +401,7 @@ extern "C" int cg_se_gate_bwd(const float* pooled, const float* W1, const float*
     if (zs != CG_OK) return zs;
   }
   if ((long long)C * H <= CG_SE_THREADS * CG_SE_MAXACC) {
-    const int nwg = B < 64 ? B : 64;
+    const int nwg = B < CG_SE_MAX_WORKGROUPS ? B : CG_SE_MAX_WORKGROUPS;
     hipLaunchKernelGGL(cg_se_gate_bwd_sliced_kernel, dim3(nwg), dim3(CG_SE_THREADS), (size_t)(2 * C + 2 * H) * 4, stream, pooled, W1, W2, gate, dgate,
                        dpooled, dW1, dW2, B, C, H);
     return cg_launch_status();
@@ -451,9 +468,9 @@ extern "C" int cg_mpjpe_fwd(const float* pred, const float* tgt, float* loss, lo
   hipStream_t stream = (hipStream_t)stream_;
   const int zs = cg_zero_fill(loss, (long long)sizeof(float), stream);
   if (zs != CG_OK) return zs;
-  long long blocks = (N + 255) / 256;
-  if (blocks > 1024) blocks = 1024;
-  hipLaunchKernelGGL(cg_mpjpe_fwd_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, pred, tgt, loss, N);
+  long long blocks = (N + CG_GLUE_THREADS - 1) / CG_GLUE_THREADS;
+  if (blocks > CG_MPJPE_MAX_BLOCKS) blocks = CG_MPJPE_MAX_BLOCKS;
+  hipLaunchKernelGGL(cg_mpjpe_fwd_kernel, dim3((unsigned)blocks), dim3(CG_GLUE_THREADS), 0, stream, pred, tgt, loss, N);
   return cg_launch_status();
 }
 

@@ -36,6 +36,12 @@ def _chk(t, name="tensor"):
     return t
 
 
+def _dense(t, name="tensor"):
+    """The operand of a kernel that takes a raw pointer and no view: float32 (else TypeError), strided input is copied by a kernel."""
+    _chk(t, name)
+    return t if t.is_contiguous() else _copy(t)
+
+
 def _view4(t):
     """(sizes, strides) of a 2/3/4-D tensor as a CgView4 (missing trailing dims have size 1)."""
     if t.dim() < 2 or t.dim() > 4:
@@ -465,6 +471,19 @@ def _sum_keep_builder(t, labels, keep):
     return lambda out: _contract_prepare("%s,%s->%s" % (labels, rest, keep), t, one, sizes=sizes, sx={l: 0 for l in rest}, out=out)
 
 
+def _bias(bias, bias_label, spec, a, x):
+    """the bias of a contraction as the kernel reads it: float32, one contiguous value per index of `bias_label`"""
+    if bias is None:
+        return None
+    _chk(bias, "bias")
+    ins, _ = spec.split("->")
+    la, lx = ins.split(",")
+    n = a.shape[la.index(bias_label)] if bias_label in la else x.shape[lx.index(bias_label)] if bias_label and bias_label in lx else None
+    if bias.dim() != 1 or bias.numel() != n:
+        raise ValueError("contract: bias of shape %s along index %r of %s" % (tuple(bias.shape), bias_label, spec))
+    return bias if bias.is_contiguous() else _copy(bias)
+
+
 class _ContractMany(torch.autograd.Function):
     """Several independent contractions in one launch (forward) and all their gradients in one launch (backward)."""
 
@@ -472,7 +491,7 @@ class _ContractMany(torch.autograd.Function):
     def forward(ctx, metas, *ts):
         ctx.set_materialize_grads(False)      # the channel-sum outputs never receive a gradient: do not zero-fill one
         n = len(metas)
-        trip = [ts[3 * i:3 * i + 3] for i in range(n)]
+        trip = [(ts[3 * i], ts[3 * i + 1], _bias(ts[3 * i + 2], metas[i][1], metas[i][0], ts[3 * i], ts[3 * i + 1])) for i in range(n)]
         builders = [(lambda out, m=m, t=t: _contract_prepare(m[0], t[0], t[1], t[2], m[1], stats_label=m[2], out=out))
                     for m, t in zip(metas, trip)]
         preps = _contract_launch(builders, trip[0][1].device)
@@ -575,6 +594,7 @@ class _Contract(torch.autograd.Function):
     def forward(ctx, a, x, bias, spec, bias_label, stats_label):
         ctx.set_materialize_grads(False)      # the channel-sum output never receives a gradient: do not zero-fill one
         ctx.spec, ctx.bias_label = spec, bias_label
+        bias = _bias(bias, bias_label, spec, a, x)
         ctx.save_for_backward(a, x)
         if stats_label is None:
             return _contract_raw(spec, a, x, bias, bias_label), None
@@ -627,10 +647,12 @@ def _na_fill_fwd(a, x, pre, add, gamma, beta, alpha, cfg, pending_stats):
     y = torch.empty(x.shape, dtype=torch.float32, device=dev)
     a.x, a.xv, a.y, a.yv = x.data_ptr(), v, y.data_ptr(), _view4(y)
     if pre is not None:
+        _chk(pre, "gate")
         if tuple(pre.shape) != (B, C) or not pre.is_contiguous():
             raise ValueError("norm_act: gate must be a contiguous (B,C) tensor")
         a.pre = pre.data_ptr()
     if add is not None:
+        _chk(add, "addend")
         if add.shape != x.shape:
             raise ValueError("norm_act: addend shape %s != %s" % (tuple(add.shape), tuple(x.shape)))
         a.add, a.av = add.data_ptr(), _view4(add)
@@ -640,6 +662,9 @@ def _na_fill_fwd(a, x, pre, add, gamma, beta, alpha, cfg, pending_stats):
     if bn is not None:
         train = cfg["train"]
         a.bn_mode = 1 if train else 2
+        for t, name in ((gamma, "BatchNorm weight"), (beta, "BatchNorm bias")):
+            if _chk(t, name).numel() != C or not t.is_contiguous():
+                raise ValueError("norm_act: %s must be a contiguous tensor of %d channels" % (name, C))
         a.gamma, a.beta = gamma.data_ptr(), beta.data_ptr()
         a.running_mean, a.running_var = bn.running_mean.data_ptr(), bn.running_var.data_ptr()
         a.num_batches_tracked = bn.num_batches_tracked.data_ptr()
@@ -650,6 +675,11 @@ def _na_fill_fwd(a, x, pre, add, gamma, beta, alpha, cfg, pending_stats):
             if B * P <= 1:
                 raise ValueError("Expected more than 1 value per channel when training, got input size %s" % (tuple(x.shape),))
             stats = cfg.get("stats")
+            if stats is not None:
+                if stats.dtype != torch.float64:
+                    raise TypeError("norm_act: channel sums must be float64, got %s" % stats.dtype)
+                if stats.numel() != 2 * C * _lib.STAT_REPLICAS or not stats.is_contiguous():
+                    raise ValueError("norm_act: channel sums must be a contiguous tensor of 2 * %d * %d doubles" % (C, _lib.STAT_REPLICAS))
             if stats is None:
                 stats = _arena(dev).take(2 * C * _lib.STAT_REPLICAS)
                 it = _lib.StatsArgs()
@@ -660,6 +690,8 @@ def _na_fill_fwd(a, x, pre, add, gamma, beta, alpha, cfg, pending_stats):
     if p > 0.0:
         a.drop_p, a.seed, a.salt = p, seed_state(dev).data_ptr(), cfg["salt"]
     if alpha is not None:
+        if _chk(alpha, "PReLU weight").numel() not in (1, C) or not alpha.is_contiguous():
+            raise ValueError("norm_act: PReLU weight must be a contiguous tensor of 1 or %d slopes" % C)
         a.alpha, a.alpha_n = alpha.data_ptr(), alpha.numel()
     emitted = None
     if cfg.get("emit_stats"):
@@ -738,7 +770,7 @@ class _NormActMany(torch.autograd.Function):
             if alpha is not None:
                 nalpha = alpha.numel()
                 a.alpha, a.alpha_n = alpha.data_ptr(), nalpha
-            a.dy, a.dyv = dy.data_ptr(), _view4(dy)
+            a.dy, a.dyv = _chk(dy, "upstream gradient").data_ptr(), _view4(dy)
             need = ctx.needs_input_grad[1 + 6 * i:7 + 6 * i]
             dx = dpre = dadd = dgamma = dbeta = dalpha = None
             if need[0]:
@@ -823,7 +855,7 @@ class _ReduceBC(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dout):
         arg, = ctx.saved_tensors
-        dout = dout if dout.is_contiguous() else _copy(dout)
+        dout = _dense(dout, "upstream gradient")
         dx = torch.empty(ctx.shape, dtype=torch.float32, device=dout.device)
         v = _view4(dx)
         _lib.call("cg_reduce_bc_bwd", _ptr(dout), _ptr(arg), ctx.kind, _ptr(dx), ctypes.byref(v), _stream(dout))
@@ -843,6 +875,9 @@ def max_bc(x):
 class _SEGate(torch.autograd.Function):
     @staticmethod
     def forward(ctx, pooled, w1, w2):
+        if pooled.dim() != 2 or tuple(w1.shape) != (w1.shape[0], pooled.shape[1]) or tuple(w2.shape) != (pooled.shape[1], w1.shape[0]):
+            raise ValueError("se_gate: expected pooled (B,C), w1 (H,C), w2 (C,H), got %s, %s, %s" % (tuple(pooled.shape), tuple(w1.shape), tuple(w2.shape)))
+        pooled, w1, w2 = _dense(pooled, "pooled"), _dense(w1, "w1"), _dense(w2, "w2")
         B, C = pooled.shape
         H = w1.shape[0]
         gate = torch.empty(B, C, dtype=torch.float32, device=pooled.device)
@@ -855,7 +890,7 @@ class _SEGate(torch.autograd.Function):
         pooled, w1, w2, gate = ctx.saved_tensors
         B, C = pooled.shape
         H = w1.shape[0]
-        dgate = dgate if dgate.is_contiguous() else _copy(dgate)
+        dgate = _dense(dgate, "upstream gradient")
         dp = torch.empty_like(pooled)
         dw, _ = _zeros(2 * C * H, pooled.device)
         dw1, dw2 = dw[:C * H].view(w1.shape), dw[C * H:].view(w2.shape)
@@ -872,6 +907,9 @@ def se_gate(pooled, w1, w2):
 # strided copies: cat / pad / sums
 # ----------------------------------------------------------------------------------------------
 def _add_into(y, a, b=None, c=None):
+    for t in (a, b, c):
+        if t is not None:
+            _chk(t)
     vy, va = _view4(y), _view4(a)
     vb = _view4(b) if b is not None else None
     vc = _view4(c) if c is not None else None
@@ -888,13 +926,17 @@ def _sum_tensors(ts):
     if y.dim() > 4:
         y = y.reshape(y.shape[0], -1)
     ts = list(ts)
+    for g in ts:
+        _chk(g, "gradient")
+        if g.shape != out.shape:
+            raise ValueError("sum of gradients: shape %s against %s" % (tuple(g.shape), tuple(out.shape)))
     while ts:
         part, ts = ts[:_SUM_MAX], ts[_SUM_MAX:]
         if ts:                                  # more than eight: fold the partial sum into the next round
             ts.insert(0, out)
         arr = (_lib.SumItem * len(part))()
         for i, g in enumerate(part):
-            g = g if g.dim() >= 2 else g.view(1, -1)
+            g = g if g.dim() >= 2 else g.reshape(-1).unsqueeze(0)
             if g.dim() > 4:
                 g = g.reshape(g.shape[0], -1)
             arr[i].a, arr[i].av = g.data_ptr(), _view4(g)
@@ -934,7 +976,9 @@ def fanout(x, n):
 
 def _copy(t):
     y = torch.empty(t.shape, dtype=torch.float32, device=t.device)
-    if t.dim() > 4 or t.dim() < 2:
+    if t.dim() == 1:
+        _add_into(y.view(1, -1), t.unsqueeze(0))
+    elif t.dim() > 4 or t.dim() < 2:
         flat = t.reshape(1, -1) if t.is_contiguous() else None
         if flat is None:
             raise ValueError("copy: unsupported rank")
@@ -951,6 +995,10 @@ class _Cat(torch.autograd.Function):
     @staticmethod
     def forward(ctx, bcast, *ts):
         ref = next(t for t, bc in zip(ts, bcast) if not bc)
+        for t, bc in zip(ts, bcast):
+            _chk(t, "cat_channels input")
+            if bc and t.dim() != 2:
+                raise ValueError("cat_channels: a broadcast input is a (B,C) map, got %s" % (tuple(t.shape),))
         chans = [t.shape[1] for t in ts]
         shape = list(ref.shape)
         shape[1] = sum(chans)
@@ -971,6 +1019,7 @@ class _Cat(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dy):
+        _chk(dy, "upstream gradient")
         outs, c0 = [], 0
         for i, (bc, c) in enumerate(zip(ctx.bcast, ctx.chans)):
             g = dy.narrow(1, c0, c)
@@ -1193,7 +1242,7 @@ class _FeatureLift(torch.autograd.Function):
     def backward(ctx, df):
         x, = ctx.saved_tensors
         B, T, V, _ = x.shape
-        df = df if df.is_contiguous() else _copy(df)
+        df = _dense(df, "upstream gradient")
         dx = torch.empty_like(x)
         _lib.call("cg_feature_lift_bwd", _ptr(x), _ptr(df), _ptr(dx), B, T, V, _stream(x))
         return dx
@@ -1206,7 +1255,8 @@ def feature_lift(x):
 class _DstdStats(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x):
-        if not x.is_contiguous():
+        _chk(x, "x")
+        if x.dim() != 4 or not x.is_contiguous():
             raise ValueError("dstd_stats expects a contiguous (B,C,T,V) tensor")
         B, C, T, V = x.shape
         out = torch.empty(B, 2 + 2 * T, dtype=torch.float32, device=x.device)
@@ -1218,7 +1268,7 @@ class _DstdStats(torch.autograd.Function):
     def backward(ctx, dout):
         x, = ctx.saved_tensors
         B, C, T, V = x.shape
-        dout = dout if dout.is_contiguous() else _copy(dout)
+        dout = _dense(dout, "upstream gradient")
         dx = torch.empty_like(x)
         _lib.call("cg_dstd_stats_bwd", _ptr(x), _ptr(dout), _ptr(dx), B, C, T, V, _stream(x))
         return dx
@@ -1231,6 +1281,7 @@ def dstd_stats(x):
 class _Cumsum(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x):
+        _chk(x, "x")
         y = torch.empty(x.shape, dtype=torch.float32, device=x.device)
         vx, vy = _view4(x), _view4(y)
         _lib.call("cg_cumsum", _ptr(x), ctypes.byref(vx), _ptr(y), ctypes.byref(vy), 0, _stream(x))
@@ -1238,6 +1289,7 @@ class _Cumsum(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dy):
+        _chk(dy, "upstream gradient")
         dx = torch.empty(dy.shape, dtype=torch.float32, device=dy.device)
         vy, vx = _view4(dy), _view4(dx)
         _lib.call("cg_cumsum", _ptr(dy), ctypes.byref(vy), _ptr(dx), ctypes.byref(vx), 1, _stream(dy))
@@ -1253,7 +1305,7 @@ class _Rank1Adj(torch.autograd.Function):
         ctx.set_materialize_grads(False)
         n = len(domains)
         B, V, T = sq[0].shape
-        sq = [t if t.is_contiguous() else _copy(t) for t in sq]
+        sq = [_dense(t, "s" if i % 2 == 0 else "q") for i, t in enumerate(sq)]
         outs = []
         arr = (_lib.Rank1 * n)()
         for i, dom in enumerate(domains):
@@ -1279,7 +1331,7 @@ class _Rank1Adj(torch.autograd.Function):
             arr = (_lib.Rank1 * len(live))()
             keep = []
             for k, i in enumerate(live):
-                d = douts[i] if (douts[i].is_contiguous() and douts[i].data_ptr() % 16 == 0) else _copy(douts[i])
+                d = douts[i] if (_chk(douts[i], "upstream gradient").is_contiguous() and douts[i].data_ptr() % 16 == 0) else _copy(douts[i])
                 ds, dq = torch.empty_like(sq[2 * i]), torch.empty_like(sq[2 * i + 1])
                 arr[k].s, arr[k].q, arr[k].dout = sq[2 * i].data_ptr(), sq[2 * i + 1].data_ptr(), d.data_ptr()
                 arr[k].ds, arr[k].dq, arr[k].domain = ds.data_ptr(), dq.data_ptr(), ctx.domains[i]
@@ -1488,7 +1540,7 @@ class _Mpjpe(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g):
         pred, target = ctx.saved_tensors
-        g = g.reshape(1)
+        g = _chk(g, "upstream gradient").reshape(1)
         d = torch.empty_like(pred)
         _lib.call("cg_mpjpe_bwd", _ptr(pred), _ptr(target), _ptr(g), _ptr(d), pred.numel() // 3, _stream(pred))
         return d, None
@@ -1520,7 +1572,7 @@ class _MpjpePerSample(torch.autograd.Function):
         _chk(w, "upstream gradient")
         if w.numel() != B:
             raise ValueError("mpjpe_per_sample: upstream gradient of %d elements for %d samples" % (w.numel(), B))
-        w = w if w.is_contiguous() else w.contiguous()
+        w = w.reshape(B) if w.is_contiguous() else _copy(w.reshape(B))
         d = torch.empty_like(pred)
         _lib.call("cg_mpjpe_sample_bwd", _ptr(pred), _ptr(target), _ptr(w), _ptr(d), B, pred.numel() // (3 * B), _stream(pred))
         return d, None
@@ -2438,6 +2490,9 @@ class _SplitChannels(torch.autograd.Function):
             c0 += c
             if g is None:
                 raise RuntimeError("split_channels: every piece needs a gradient")
+            _chk(g, "upstream gradient")
+            if g.shape != dst.shape:
+                raise ValueError("split_channels: gradient of shape %s for a piece of shape %s" % (tuple(g.shape), tuple(dst.shape)))
             it = _lib.CopyItem()
             it.y, it.yv, it.a, it.av = dst.data_ptr(), _view4(dst), g.data_ptr(), _view4(g)
             items.append(it)

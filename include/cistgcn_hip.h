@@ -455,7 +455,13 @@ long long cg_context_heads_red_doubles(int C);
  *                              1 when this launch tries the plane kernels first (then the five numbers before describe the fall-back) }
  *   cg_block_input_geometry    out[3] = { planes (channels) per span, spans per sample, grid of the streaming kernels = B * spans } (a workgroup
  *                              owns one span of one sample; the last span of a sample is short when C is no multiple of the span)
- *   cg_norm_act_rows_per_block samples of one channel per workgroup of the row kernels (cg_norm_act_*, cg_chan_stats) for the view */
+ *   cg_norm_act_rows_per_block samples of one channel per workgroup of the row kernels (cg_norm_act_*, cg_chan_stats) for the view
+ *   cg_glue_geometry           limits of the glue launchers and the plan of cg_dstd_stats_* for a (C,T,V) sample: out[11] = { points one grid of
+ *                              cg_mpjpe_fwd covers, elements one grid of cg_adam_flat / cg_scale covers, bytes one grid of cg_zero covers (past
+ *                              these a thread strides), largest C * H of the sliced cg_se_gate_bwd kernel (above it: one workgroup per
+ *                              sample, atomics), its largest grid (more samples: a workgroup walks several), dynamic LDS bytes a kernel
+ *                              gets without a raised limit, LDS bytes of cg_dstd_stats_bwd (-1: unsupported), lanes per row, rows per
+ *                              iteration of a workgroup, iterations, rows of the last iteration } */
 int cg_map2adj_tail_geometry(int B, int Kc, int J, int* out);
 int cg_dstd_tail_geometry(int B, int C, int T, int V, int* out);
 int cg_pointwise_maps_geometry(int B, int Cin, int P, int n, const int* M, int bwd, int* out);
@@ -464,6 +470,7 @@ int cg_fpn_conv_geometry(int B, int C, int O, int H, int W, int* out);
 int cg_stgcn_domain_geometry(int B, int Cin, int Cout, int T, int V, int domain, int bwd, int kind, int* out);
 int cg_block_input_geometry(int B, int C, int T, int V, int* out);
 int cg_norm_act_rows_per_block(const CgView4* xv);
+int cg_glue_geometry(int C, int T, int V, int* out);
 
 /* ---- evaluation harness counterpart, environment/test.py:97-132 ----------------------
  * y[r,k,:] = x[r,idx[k],:] : `inputs[:, :, dim_used]` (32 -> 22 joints); x (rows,Jin,3), y (rows,Jout,3) contiguous */

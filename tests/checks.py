@@ -157,11 +157,12 @@ def kink_adjusted(got, refs, floors, what, log, leaves, rel=5e-5, both_ways=Fals
     return refs
 
 
-def _run(fn_dev, fn_ref, inputs, device, rel=2e-5, what="", ref_sees_dev_out=False, log=None, params=None):
+def _run(fn_dev, fn_ref, inputs, device, rel=2e-5, what="", ref_sees_dev_out=False, log=None, params=None, ref_dtype=None):
     """fn_dev / fn_ref map a list of leaf tensors to one output; compares output and all input grads.  ref_sees_dev_out: fn_ref also gets the
-    HIP output (keyword dev_out), to take its PReLU branches (`log`, a BranchLog; elements whose branch cannot be read get no upstream gradient)."""
+    HIP output (keyword dev_out), to take its PReLU branches (`log`, a BranchLog; elements whose branch cannot be read get no upstream gradient).
+    ref_dtype: the reference runs in this type (torch.float64) on the same float32 values; default: float32 as the inputs."""
     dev_in = [_leaf(t, device) for t in inputs]
-    ref_in = [_leaf(t, "cpu") for t in inputs]
+    ref_in = [_leaf(t if ref_dtype is None else t.to(ref_dtype), "cpu") for t in inputs]
     ops.begin_step(device)
     y = fn_dev(*dev_in)
     r = fn_ref(*ref_in, dev_out=y) if ref_sees_dev_out else fn_ref(*ref_in)
@@ -170,7 +171,7 @@ def _run(fn_dev, fn_ref, inputs, device, rel=2e-5, what="", ref_sees_dev_out=Fal
     if log is not None and log.unknown is not None:
         g = g.masked_fill(log.unknown, 0.0)
     y.backward(g.to(device))
-    r.backward(g, retain_graph=log is not None)
+    r.backward(g.to(r.dtype), retain_graph=log is not None)
     if log is not None:          # inputs and `params` = (device parameters, reference parameters) together, kink terms accounted for
         pairs = [(a, b) for a, b in zip(dev_in, ref_in) if b.grad is not None] + list(zip(*params))
         assert_grads_at_kinks([a.grad for a, _ in pairs], [b.grad for _, b in pairs], [max(1e-3, float(b.grad.abs().max())) for _, b in pairs],
