@@ -123,7 +123,8 @@ class RowsConv(ctypes.Structure):
     _fields_ = [("B", c_int), ("C", c_int), ("T", c_int), ("V", c_int), ("O", c_int), ("pad", c_int),
                 ("x", c_void_p), ("W", c_void_p), ("y", c_void_p), ("stats", c_void_p),
                 ("dy", c_void_p), ("dx", c_void_p), ("dW", c_void_p), ("ws", c_void_p),
-                ("in_on", c_int), ("in_train", c_int), ("in_bn", TailBN), ("in_alpha", c_void_p), ("in_tap", c_void_p)]
+                ("in_on", c_int), ("in_train", c_int), ("in_bn", TailBN), ("in_alpha", c_void_p), ("in_tap", c_void_p),
+                ("sums", c_void_p), ("red", c_void_p), ("dgamma", c_void_p), ("dbeta", c_void_p), ("dalpha", c_void_p)]
 
 
 class BlockInput(ctypes.Structure):
@@ -224,6 +225,7 @@ _SIGNATURES = {
     "cg_collapse_cols_bwd": [POINTER(RowsConv), P],
     "cg_collapse_cols_supported": [c_int, c_int, c_int, c_int],
     "cg_collapse_cols_ws_floats": [c_int, c_int, c_int],
+    "cg_collapse_sums_ws_floats": [c_int, c_int],
     "cg_fpn_conv_fwd": [POINTER(FpnConv), P],
     "cg_fpn_conv_bwd": [POINTER(FpnConv), P],
     "cg_fpn_conv_supported": [c_int, c_int, c_int, c_int, c_int],

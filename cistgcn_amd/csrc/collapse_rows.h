@@ -22,4 +22,12 @@ struct CgRowsConv {
   const float* in_alpha;
   float* in_tap;                    // forward, optional (with in_on): the activated input x' (B,C,T,V), written as it is formed - for the PReLU branch
                                     // records of the parity tests (production never asks for it: not storing x' is the point)
+  // backward, optional (with in_on; `sums` and `red` together): the channel sums of the BatchNorm / PReLU backward that belongs to the
+  // producer of x, formed from the operands the kernel holds anyway - with gh = dx PReLU'(u), xhat = (x - mean) rstd:
+  //   red[2c] = sum gh, red[2c + 1] = sum gh xhat, red[2C] = sum_{u <= 0} dx u (red[2C + 1 .. 2C + CG_ALPHA_SLOTS - 1] = 0)
+  // exactly what cg_norm_act_bwd_reduce_many leaves for cg_pointwise_maps_bwd (`bn_red`), in a fixed order: nothing has to be zeroed,
+  // the same bits from run to run.  dgamma[c] = red[2c + 1], dbeta[c] = red[2c], dalpha[0] = red[2C] (each optional).
+  double* sums;                     // cg_collapse_sums_ws_floats(C, T or V) floats of scratch (per-slice partials; need not be zeroed)
+  double* red;                      // [2C + CG_ALPHA_SLOTS] f64
+  float* dgamma; float* dbeta; float* dalpha;
 };

@@ -16,7 +16,7 @@ HIP_DYNAMIC_SHARED(unsigned char, cg_dyn_lds)
 #define CG_ROWS_BWD_THREADS 256
 #define CG_ROWS_KB 64            // rows of W per backward workgroup
 
-struct CgRowsGeom { int K, OT, slices, per, kranges; };
+struct CgRowsGeom { int K, OT, slices, per, kranges, rpc; };      // rpc: rows k per channel (T on the frame axis, V on the joint axis)
 struct CgRowsArgs { CgRowsConv t; CgRowsGeom g; };
 
 // ======================================================================================================================
@@ -177,6 +177,49 @@ __device__ __forceinline__ void cg_rows_stv(float* __restrict__ p, const float* 
   else p[0] = v[0];
 }
 
+// ---- channel sums of the producer's BatchNorm / PReLU backward (CgRowsConv.sums / red) -----------------------------------------
+// The collapsing backward holds, per element of x, the raw value and dh = (W^T dy): everything the reduction pass of the producer's
+// BatchNorm / PReLU backward would read back from memory (cg_norm_act_bwd_reduce_many: 2 x 36 MB per map at B = 256).  With the
+// template switch SUMS a lane adds up, for ITS row k (one channel), s1 = sum gh, s2 = sum gh xhat, sa = sum_{u <= 0} dh u with
+// gh = dh PReLU'(u), xhat = (x - mean) rstd: f32 over the few values of one sample (or of one frame tile), f64 from there on.
+// Positions outside the tensor (rows k >= K, columns v >= V, frames t >= T) need no mask: the zero padding of W and dy makes dh exactly
+// 0 there, x is a finite stand-in (zeros, an old dx tile = 0, or the clamped duplicate of a neighbour), so every term is 0.
+// u is formed by the very expression of the operand, `cg_rows_u`.
+__device__ __forceinline__ float cg_rows_u(float x, float tm, float ts, float tb) { return (x - tm) * ts + tb; }
+__device__ __forceinline__ void cg_rows_sum_term(float x, float dh, float tm, float ts, float tb, float trs, float ta, float& p1, float& p2, float& pa) {
+  const float u = cg_rows_u(x, tm, ts, tb);
+  const float gh = u > 0.f ? dh : ta * dh;
+  p1 += gh; p2 += gh * ((x - tm) * trs);
+  if (!(u > 0.f)) pa += dh * u;
+}
+// doubles of CgRowsConv.sums: per slice [2][Kp] row sums (s1, s2; Kp = 64 kranges) and [kranges] slope sums of the workgroups
+__host__ __device__ __forceinline__ long long cg_rows_sums_stride(int kranges) { return (2ll * CG_ROWS_KB + 1) * kranges; }
+// A workgroup's sums leave through LDS (free by now): the four slots of a row are added in a fixed order, the 64 rows' slope sums too.
+__device__ __forceinline__ void cg_rows_put_sums(double* sS, double s1, double s2, double sa, double* sums, int kranges, int sl, int kr, int tid) {
+  __syncthreads();                                                // every wave is done with W, dy and its rows
+  sS[tid] = s1; sS[CG_ROWS_BWD_THREADS + tid] = s2; sS[2 * CG_ROWS_BWD_THREADS + tid] = sa;
+  __syncthreads();
+  double* dst = sums + (long long)sl * cg_rows_sums_stride(kranges);
+  if (tid < CG_ROWS_KB) {                                         // row tid of the range: wave tid / 16, lanes l15 + 16 slot
+    const int i = 64 * (tid >> 4) + (tid & 15);
+    double r[3];
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+      const double* q = sS + CG_ROWS_BWD_THREADS * j + i;
+      r[j] = (q[0] + q[16]) + (q[32] + q[48]);
+    }
+    dst[kr * CG_ROWS_KB + tid] = r[0];
+    dst[(long long)kranges * CG_ROWS_KB + kr * CG_ROWS_KB + tid] = r[1];
+    sS[3 * CG_ROWS_BWD_THREADS + tid] = r[2];
+  }
+  __syncthreads();
+  if (tid == 0) {
+    double s = 0.0;
+    for (int i = 0; i < CG_ROWS_KB; ++i) s += sS[3 * CG_ROWS_BWD_THREADS + i];
+    dst[2ll * kranges * CG_ROWS_KB + kr] = s;
+  }
+}
+
 // (128 rows x 512 threads per workgroup: 57 us instead of 44.)
 // (Round 4 tried this kernel with compile-time OT, dy of the next sample through registers and clamped instead of conditional loads:
 // 90 us instead of 100 on the 64-output gate convolutions, but 152 us instead of 47 on the 32-output tower convolutions; not understood,
@@ -190,7 +233,7 @@ __device__ __forceinline__ void cg_rows_stv(float* __restrict__ p, const float* 
 // Staging is split: the loads of dy[b + 1] and x[b + 1] are issued in front of the matrix work of sample b and stored to LDS behind it
 // (dy[b + 1] used to be waited for and stored in front of the MFMAs of sample b: one exposed memory latency per sample).
 #define CG_ROWS_XS 36            // floats per LDS row of a piece: V <= 32 and four that are never read (column XS - 1 takes the floats of no one)
-template <int VW>
+template <int VW, bool SUMS>
 __global__ __launch_bounds__(CG_ROWS_BWD_THREADS) void cg_rows_bwd_kernel(CgRowsArgs a) {
   const CgRowsConv& t = a.t; const CgRowsGeom& g = a.g;
   const int K = g.K, V = t.V, O = t.O, OV = O * V;
@@ -267,11 +310,12 @@ __global__ __launch_bounds__(CG_ROWS_BWD_THREADS) void cg_rows_bwd_kernel(CgRows
   // optional input transform (see CgRowsConv.in_on): this lane's row k = (c, t) has ONE channel c; the values outside the tensor meet dy = 0
   const int krow = kw + l15;
   const bool tr = t.in_on != 0;
-  float tm = 0.f, ts = 1.f, tb = 0.f, ta = 1.f;
+  float tm = 0.f, ts = 1.f, tb = 0.f, ta = 1.f, trs = 1.f;
   if (tr) {
     const CgAff af = cg_tail_aff(t.in_bn, min(krow, K - 1) / t.T, t.C, 0.0, t.in_train, true, false);
-    tm = af.mean; ts = af.gamma * af.rstd; tb = af.beta; ta = t.in_alpha[0];
+    tm = af.mean; ts = af.gamma * af.rstd; tb = af.beta; ta = t.in_alpha[0]; trs = af.rstd;
   }
+  double s1 = 0.0, s2 = 0.0, sa = 0.0;                             // SUMS: this lane's share of row krow over the slice
   for (int b = b0; b < b1; ++b) {
     const int buf = (b - b0) & 1;
     const bool more = b + 1 < b1;
@@ -283,7 +327,7 @@ __global__ __launch_bounds__(CG_ROWS_BWD_THREADS) void cg_rows_bwd_kernel(CgRows
     float xa[4] = {xa4[0], xa4[1], xa4[2], xa4[3]}, xc[4] = {xc4[0], xc4[1], xc4[2], xc4[3]};
     if (tr) {
 #pragma unroll
-      for (int s = 0; s < 4; ++s) { xa[s] = cg_prelu((xa[s] - tm) * ts + tb, ta); xc[s] = cg_prelu((xc[s] - tm) * ts + tb, ta); }
+      for (int s = 0; s < 4; ++s) { xa[s] = cg_prelu(cg_rows_u(xa[s], tm, ts, tb), ta); xc[s] = cg_prelu(cg_rows_u(xc[s], tm, ts, tb), ta); }
     }
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();                              // every lane holds its operand: the rows are free for the dx tile
@@ -318,6 +362,19 @@ __global__ __launch_bounds__(CG_ROWS_BWD_THREADS) void cg_rows_bwd_kernel(CgRows
       for (int r = 0; r < NG; ++r)
         if (xok[r]) cg_rows_stv<VW>(dxb + xg[r], dv + VW * r);
     }
+    if constexpr (SUMS) {
+      // one more read of the rows, in the operand pattern: dh next to the raw x this lane still holds (xa4 / xc4).  No mask: rows
+      // k >= K and columns v >= V of the tile are W^T dy of zeros
+      const cg_f32x4 ha4 = *reinterpret_cast<const cg_f32x4*>(sXw + l15 * XS + 4 * slot);
+      const cg_f32x4 hc4 = *reinterpret_cast<const cg_f32x4*>(sXw + l15 * XS + 16 + 4 * slot);
+      float p1 = 0.f, p2 = 0.f, pa = 0.f;
+#pragma unroll
+      for (int s = 0; s < 4; ++s) {
+        cg_rows_sum_term(xa4[s], ha4[s], tm, ts, tb, trs, ta, p1, p2, pa);
+        cg_rows_sum_term(xc4[s], hc4[s], tm, ts, tb, trs, ta, p1, p2, pa);
+      }
+      s1 += (double)p1; s2 += (double)p2; sa += (double)pa;
+    }
     // dW[o][k] += sum_v dy[o][v] x[k][v]: A[i = o][kk = v] from LDS (float4 along v), B[kk = v][j = k] = this lane's x values
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
@@ -337,13 +394,56 @@ __global__ __launch_bounds__(CG_ROWS_BWD_THREADS) void cg_rows_bwd_kernel(CgRows
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
     if (more) stage_write(buf ^ 1);
   }
+  if constexpr (SUMS) cg_rows_put_sums(reinterpret_cast<double*>(cg_dyn_lds), s1, s2, sa, t.sums, g.kranges, sl, kr, tid);
   cg_rows_put_dw<4>(sW, wacc, g.OT, t.ws + (long long)sl * O * K, O, K, k0, tid, wave, l15, slot);
 }
 
 // dW[e] = sum over the slices' partials.  A workgroup takes 64 consecutive elements, its four waves every fourth slice; the order of the
 // sum is fixed, so dW is the same from run to run.
+// SUMS: the launch also folds the row sums of the backward kernel (CgRowsConv.sums) into `red`, dgamma, dbeta, dalpha - channel c by
+// workgroup c (mod the grid), the slope by the last workgroup; 256 threads take the (slice, row) entries in a fixed assignment, then a tree.
+__device__ __forceinline__ void cg_rows_fold_tree(double (*sR)[CG_ROWS_BWD_THREADS], int tid) {
+  __syncthreads();
+  for (int w = CG_ROWS_BWD_THREADS / 2; w > 0; w >>= 1) {
+    if (tid < w) { sR[0][tid] += sR[0][tid + w]; sR[1][tid] += sR[1][tid + w]; }
+    __syncthreads();
+  }
+}
+template <bool SUMS>
 __global__ __launch_bounds__(CG_ROWS_BWD_THREADS) void cg_rows_fold_kernel(CgRowsArgs a) {
   const CgRowsConv& t = a.t;
+  if constexpr (SUMS) {
+    __shared__ double sR[2][CG_ROWS_BWD_THREADS];
+    const int tid = threadIdx.x, C = t.C, rpc = a.g.rpc, kranges = a.g.kranges;
+    const long long Kp = (long long)kranges * CG_ROWS_KB, stride = cg_rows_sums_stride(kranges);
+    for (int c = blockIdx.x; c < C; c += gridDim.x) {
+      double a1 = 0.0, a2 = 0.0;
+      for (int e = tid; e < a.g.slices * rpc; e += CG_ROWS_BWD_THREADS) {
+        const int r = e / rpc;
+        const double* q = t.sums + r * stride + (long long)c * rpc + (e - r * rpc);
+        a1 += q[0]; a2 += q[Kp];
+      }
+      sR[0][tid] = a1; sR[1][tid] = a2;
+      cg_rows_fold_tree(sR, tid);
+      if (tid == 0) {
+        t.red[2 * c] = sR[0][0]; t.red[2 * c + 1] = sR[1][0];
+        if (t.dbeta) t.dbeta[c] = (float)sR[0][0];
+        if (t.dgamma) t.dgamma[c] = (float)sR[1][0];
+      }
+      __syncthreads();
+    }
+    if (blockIdx.x == gridDim.x - 1) {
+      double a1 = 0.0;
+      for (int e = tid; e < a.g.slices * kranges; e += CG_ROWS_BWD_THREADS) {
+        const int r = e / kranges;
+        a1 += t.sums[r * stride + 2 * Kp + (e - r * kranges)];
+      }
+      sR[0][tid] = a1; sR[1][tid] = 0.0;
+      cg_rows_fold_tree(sR, tid);
+      if (tid < CG_ALPHA_SLOTS) t.red[2 * C + tid] = tid == 0 ? sR[0][0] : 0.0;      // the total in the first slot: cg_alpha_sum adds all of them
+      if (tid == 0 && t.dalpha) t.dalpha[0] = (float)sR[0][0];
+    }
+  }
   __shared__ float part[CG_ROWS_BWD_THREADS / 64][64];
   const long long n = (long long)t.O * a.g.K;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -480,8 +580,11 @@ __global__ __launch_bounds__(CG_ROWS_FWD_THREADS) void cg_cols_fwd_kernel(CgRows
   }
 }
 
-template <int OT, int NT>
-__global__ __launch_bounds__(CG_ROWS_BWD_THREADS) void cg_cols_bwd_kernel(CgRowsArgs a, unsigned magicV) {
+// SUMS (see cg_rows_sum_term): the lane's x operand is row l15 with four consecutive frames per slot, its dx results are the rows 4 slot + q
+// at frame l15 - the tile is turned through 16 wave-private LDS rows of 16 NT frames, so that dh meets the raw x in the operand layout,
+// where a lane has one channel.
+template <int OT, int NT, bool SUMS>
+__global__ __launch_bounds__(CG_ROWS_BWD_THREADS, (SUMS && OT <= 2) ? 2 : 1) void cg_cols_bwd_kernel(CgRowsArgs a, unsigned magicV) {
   const CgRowsConv& t = a.t; const CgRowsGeom& g = a.g;
   const int K = g.K, V = t.V, T = t.T, O = t.O, TV = T * V;
   const int kr = blockIdx.x, sl = blockIdx.y, k0 = kr * CG_ROWS_KB;
@@ -557,23 +660,24 @@ __global__ __launch_bounds__(CG_ROWS_BWD_THREADS) void cg_cols_bwd_kernel(CgRows
       for (int s = 0; s < 4; ++s) xv[tt][s] = xr[tx[tt][s]];
   };
   const bool tr = t.in_on != 0;                                   // optional input transform: this lane's row k = (c, v) has one channel
-  float tm = 0.f, ts = 1.f, tb = 0.f, ta = 1.f;
+  float tm = 0.f, ts = 1.f, tb = 0.f, ta = 1.f, trs = 1.f;
   if (tr) {
     const CgAff af = cg_tail_aff(t.in_bn, cl, t.C, 0.0, t.in_train, true, false);
-    tm = af.mean; ts = af.gamma * af.rstd; tb = af.beta; ta = t.in_alpha[0];
+    tm = af.mean; ts = af.gamma * af.rstd; tb = af.beta; ta = t.in_alpha[0]; trs = af.rstd;
   }
   auto act = [&](float xv[NT][4]) {
     if (tr) {
 #pragma unroll
       for (int tt = 0; tt < NT; ++tt)
 #pragma unroll
-        for (int s = 0; s < 4; ++s) xv[tt][s] = cg_prelu((xv[tt][s] - tm) * ts + tb, ta);
+        for (int s = 0; s < 4; ++s) xv[tt][s] = cg_prelu(cg_rows_u(xv[tt][s], tm, ts, tb), ta);
     }
   };
+  double s1 = 0.0, s2 = 0.0, sa = 0.0;                             // SUMS: this lane's share of row kl over the slice
   // x[b] is taken over from the registers it was loaded into at the top of its own iteration, in front of the loads of sample b + 1: the one
   // place where a load is waited for (the first sample's operand used to be loaded straight into `xa`; the compiler then could not tell
   // those loads from the ones in flight and waited out the loads of sample b + 1 in front of the dW products of sample b)
-  float xa[NT][4], xn[NT][4];
+  float xa[NT][4], xn[NT][4], xraw[SUMS ? NT : 1][4];
   load_x(b0, xn);
   for (int b = b0; b < b1; ++b) {
     const int buf = (b - b0) & 1;
@@ -581,7 +685,10 @@ __global__ __launch_bounds__(CG_ROWS_BWD_THREADS) void cg_cols_bwd_kernel(CgRows
 #pragma unroll
     for (int tt = 0; tt < NT; ++tt)
 #pragma unroll
-      for (int s = 0; s < 4; ++s) xa[tt][s] = xn[tt][s];
+      for (int s = 0; s < 4; ++s) {
+        xa[tt][s] = xn[tt][s];
+        if constexpr (SUMS) xraw[tt][s] = xn[tt][s];              // the raw value: xhat and the branch cannot be had from the activated one
+      }
     act(xa);
     if (b + 1 < b1) { dy_load(b + 1); load_x(b + 1, xn); }
     const float* dyb = sDY + buf * 16 * OT * DS;
@@ -609,6 +716,26 @@ __global__ __launch_bounds__(CG_ROWS_BWD_THREADS) void cg_cols_bwd_kernel(CgRows
           if (dok[q]) dxb[doff[q] + tt * V] = c[j][q];
       }
     }
+    if constexpr (SUMS) {
+      // No mask: rows k >= K meet zero rows of W, frames t >= T zero columns of dy - dh is 0 where this lane's x is the clamped
+      // duplicate of row K - 1 or of frame T - 1.
+      float* sTw = sDY + 2 * 16 * OT * DS + wave * 16 * DS;        // [4 waves][16][DS] behind the dy buffers: a wave's dx tile, rows k x frames
+#pragma unroll
+      for (int j = 0; j < NT; ++j)
+#pragma unroll
+        for (int q = 0; q < 4; ++q) sTw[(4 * slot + q) * DS + 16 * j + l15] = c[j][q];
+      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+      __builtin_amdgcn_wave_barrier();
+      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+#pragma unroll
+      for (int tt = 0; tt < NT; ++tt) {
+        const cg_f32x4 h4 = *reinterpret_cast<const cg_f32x4*>(sTw + l15 * DS + 16 * tt + 4 * slot);
+        float p1 = 0.f, p2 = 0.f, pa = 0.f;
+#pragma unroll
+        for (int s = 0; s < 4; ++s) cg_rows_sum_term(xraw[tt][s], h4[s], tm, ts, tb, trs, ta, p1, p2, pa);
+        s1 += (double)p1; s2 += (double)p2; sa += (double)pa;
+      }
+    }
     // dW[o][k] += sum_t dy[o][t] x[k][t]: A[i = o][kk = t] from LDS (float4 along t), B[kk = t][j = k] = this lane's x values
 #pragma unroll
     for (int i = 0; i < OT; ++i) {
@@ -622,6 +749,7 @@ __global__ __launch_bounds__(CG_ROWS_BWD_THREADS) void cg_cols_bwd_kernel(CgRows
     }
     if (b + 1 < b1) dy_write(buf ^ 1);
   }
+  if constexpr (SUMS) cg_rows_put_sums(reinterpret_cast<double*>(cg_dyn_lds), s1, s2, sa, t.sums, g.kranges, sl, kr, tid);
   cg_rows_put_dw<OT>(sW, wacc, OT, t.ws + (long long)sl * O * K, O, K, k0, tid, wave, l15, slot);
 }
 
@@ -637,6 +765,7 @@ static int cg_rows_geometry(const CgRowsConv* t, CgRowsGeom* g) {
   slices = slices < 1 ? 1 : (slices > t->B ? t->B : slices);
   g->per = (t->B + slices - 1) / slices;
   g->slices = (t->B + g->per - 1) / g->per;
+  g->rpc = t->T;
   return CG_OK;
 }
 
@@ -646,6 +775,23 @@ static long long cg_rows_ws(long long K, int O) {
   return (slices < 1 ? 1 : slices) * O * K;
 }
 extern "C" long long cg_collapse_rows_ws_floats(int C, int T, int O) { return cg_rows_ws((long long)C * T, O); }
+// include/cistgcn_hip.h : floats of CgRowsConv.sums (f64 partials of the most slices the geometry can choose at K = C * rows, any B)
+extern "C" long long cg_collapse_sums_ws_floats(int C, int rows) {
+  const long long K = (long long)C * rows, kranges = (K + CG_ROWS_KB - 1) / CG_ROWS_KB, slices = 768 / kranges;
+  return 2 * (slices < 1 ? 1 : slices) * cg_rows_sums_stride((int)kranges);
+}
+// the optional sums of the backward: 1 asked for, 0 not, < 0 a bad combination
+static int cg_rows_want_sums(const CgRowsConv* t) {
+  if (!t->sums && !t->red) return (t->dgamma || t->dbeta || t->dalpha) ? CG_EARG : 0;
+  return (t->sums && t->red && t->in_on) ? 1 : CG_EARG;
+}
+
+static int cg_rows_fold(const CgRowsArgs& a, int sums, hipStream_t stream) {
+  const dim3 grid((unsigned)(((long long)a.t.O * a.g.K + 63) / 64)), block(CG_ROWS_BWD_THREADS);
+  if (sums) hipLaunchKernelGGL(cg_rows_fold_kernel<true>, grid, block, 0, stream, a);
+  else hipLaunchKernelGGL(cg_rows_fold_kernel<false>, grid, block, 0, stream, a);
+  return cg_launch_status();
+}
 
 // include/cistgcn_hip.h : cg_collapse_rows_fwd / cg_collapse_rows_bwd
 extern "C" int cg_collapse_rows_fwd(const CgRowsConv* t, void* stream_) {
@@ -681,18 +827,24 @@ extern "C" int cg_collapse_rows_bwd(const CgRowsConv* t, void* stream_) {
   if (st != CG_OK) return st;
   if (!t->dy || !t->dx || !t->dW || !t->ws) return CG_EARG;
   if (t->in_on && (!t->in_alpha || !t->in_bn.gamma || !t->in_bn.beta || !t->in_bn.save)) return CG_EARG;
+  const int sums = cg_rows_want_sums(t);
+  if (sums < 0) return sums;
   a.t = *t;
   const size_t lds = ((size_t)16 * a.g.OT * (CG_ROWS_KB + 4) + (size_t)2 * 16 * a.g.OT * 36 + (size_t)(CG_ROWS_BWD_THREADS / 64) * 16 * CG_ROWS_XS) * sizeof(float);
   hipStream_t stream = (hipStream_t)stream_;
   const dim3 grid((unsigned)a.g.kranges, (unsigned)a.g.slices), block(CG_ROWS_BWD_THREADS);
   // 16-byte runs where every sample's dy, x and dx piece is 16-byte aligned (the pieces of x and dx are whole multiples of four floats)
   const bool wide = ((long long)t->O * t->V) % 4 == 0 && (((uintptr_t)t->dy | (uintptr_t)t->x | (uintptr_t)t->dx) & 15) == 0;
-  if (wide) hipLaunchKernelGGL(cg_rows_bwd_kernel<4>, grid, block, lds, stream, a);
-  else hipLaunchKernelGGL(cg_rows_bwd_kernel<1>, grid, block, lds, stream, a);
+  if (sums) {
+    if (wide) hipLaunchKernelGGL((cg_rows_bwd_kernel<4, true>), grid, block, lds, stream, a);
+    else hipLaunchKernelGGL((cg_rows_bwd_kernel<1, true>), grid, block, lds, stream, a);
+  } else {
+    if (wide) hipLaunchKernelGGL((cg_rows_bwd_kernel<4, false>), grid, block, lds, stream, a);
+    else hipLaunchKernelGGL((cg_rows_bwd_kernel<1, false>), grid, block, lds, stream, a);
+  }
   st = cg_launch_status();
   if (st != CG_OK) return st;
-  hipLaunchKernelGGL(cg_rows_fold_kernel, dim3((unsigned)(((long long)t->O * a.g.K + 63) / 64)), dim3(CG_ROWS_BWD_THREADS), 0, stream, a);
-  return cg_launch_status();
+  return cg_rows_fold(a, sums, stream);
 }
 
 // ---- joint axis ----
@@ -708,6 +860,7 @@ static int cg_cols_geometry(const CgRowsConv* t, CgRowsGeom* g) {
   slices = slices < 1 ? 1 : (slices > t->B ? t->B : slices);
   g->per = (t->B + slices - 1) / slices;
   g->slices = (t->B + g->per - 1) / g->per;
+  g->rpc = t->V;
   return CG_OK;
 }
 static int cg_cols_nt(int T) { return T <= 16 ? 1 : T <= 32 ? 2 : 4; }
@@ -766,22 +919,29 @@ extern "C" int cg_collapse_cols_bwd(const CgRowsConv* t, void* stream_) {
   if (st != CG_OK) return st;
   if (!t->dy || !t->dx || !t->dW || !t->ws) return CG_EARG;
   if (t->in_on && (!t->in_alpha || !t->in_bn.gamma || !t->in_bn.beta || !t->in_bn.save)) return CG_EARG;
+  const int sums = cg_rows_want_sums(t);
+  if (sums < 0) return sums;
   a.t = *t;
   const int nt = cg_cols_nt(t->T);
-  const size_t lds = ((size_t)16 * a.g.OT * (CG_ROWS_KB + 4) + (size_t)2 * 16 * a.g.OT * (16 * nt + 4)) * sizeof(float);
+  const size_t lds = ((size_t)16 * a.g.OT * (CG_ROWS_KB + 4) + (size_t)2 * 16 * a.g.OT * (16 * nt + 4) +
+                      (sums ? (size_t)(CG_ROWS_BWD_THREADS / 64) * 16 * (16 * nt + 4) : 0)) * sizeof(float);
   const dim3 grid((unsigned)a.g.kranges, (unsigned)a.g.slices), block(CG_ROWS_BWD_THREADS);
   hipStream_t stream = (hipStream_t)stream_;
   const unsigned magic = cg_cols_magic(t->V);
-#define CG_COLS_BWD_LAUNCH(N, M)                                                                \
+#define CG_COLS_BWD_LAUNCH_S(N, M, S)                                                           \
   {                                                                                            \
-    hipError_t e = cg_lds_limit((const void*)cg_cols_bwd_kernel<N, M>, lds);                    \
+    hipError_t e = cg_lds_limit((const void*)cg_cols_bwd_kernel<N, M, S>, lds);                 \
     if (e != hipSuccess) return (int)e;                                                        \
-    hipLaunchKernelGGL((cg_cols_bwd_kernel<N, M>), grid, block, lds, stream, a, magic);          \
+    hipLaunchKernelGGL((cg_cols_bwd_kernel<N, M, S>), grid, block, lds, stream, a, magic);       \
   }
-  CG_COLS_DISPATCH(a.g.OT, nt, CG_COLS_BWD_LAUNCH)
+#define CG_COLS_BWD_LAUNCH(N, M) CG_COLS_BWD_LAUNCH_S(N, M, false)
+#define CG_COLS_BWD_LAUNCH_SUMS(N, M) CG_COLS_BWD_LAUNCH_S(N, M, true)
+  if (sums) { CG_COLS_DISPATCH(a.g.OT, nt, CG_COLS_BWD_LAUNCH_SUMS) }
+  else { CG_COLS_DISPATCH(a.g.OT, nt, CG_COLS_BWD_LAUNCH) }
+#undef CG_COLS_BWD_LAUNCH_SUMS
 #undef CG_COLS_BWD_LAUNCH
+#undef CG_COLS_BWD_LAUNCH_S
   st = cg_launch_status();
   if (st != CG_OK) return st;
-  hipLaunchKernelGGL(cg_rows_fold_kernel, dim3((unsigned)(((long long)t->O * a.g.K + 63) / 64)), dim3(CG_ROWS_BWD_THREADS), 0, stream, a);
-  return cg_launch_status();
+  return cg_rows_fold(a, sums, stream);
 }

@@ -2402,11 +2402,14 @@ class _TowerMaps(torch.autograd.Function):
         dhs = [d if d.is_contiguous() else _copy(d) for d in dhs]
         dev, f32, train = x.device, torch.float32, bool(cfg["train"])
         stream = _stream(x)
-        # pass 1: channel sums of the gradient in front of the BatchNorm, slope gradients, dgamma / dbeta
-        arr = (NormAct * n)()
-        reds, smalls = [], []
-        for i in range(n):
-            a, bn = arr[i], cfg["bn"][i]
+        # pass 1: channel sums of the gradient in front of the BatchNorm, slope gradients, dgamma / dbeta - only for the maps whose
+        # consumer's backward has not left them in the transform record (collapse_rows / collapse_cols form them on the way)
+        done = [tr if "red" in tr else None for tr in getattr(ctx, "deferred", ())] or [None] * n
+        todo = [i for i in range(n) if done[i] is None]
+        arr = (NormAct * max(1, len(todo)))()
+        reds, smalls = [None if d is None else d["red"] for d in done], [None if d is None else d["small"] for d in done]
+        for j, i in enumerate(todo):
+            a, bn = arr[j], cfg["bn"][i]
             M = ws[i].shape[0]
             a.x, a.xv, a.dy, a.dyv = ys[i].data_ptr(), _view4(ys[i]), dhs[i].data_ptr(), _view4(dhs[i])
             a.bn_mode = 1 if train else 2
@@ -2422,8 +2425,9 @@ class _TowerMaps(torch.autograd.Function):
             a.red, a.dgamma, a.dbeta = red.data_ptr(), small[0].data_ptr(), small[1].data_ptr()
             if nal:
                 a.dalpha = small[2].data_ptr()
-            reds.append(red); smalls.append(small)
-        _lib.call("cg_norm_act_bwd_reduce_many", arr, n, stream)
+            reds[i], smalls[i] = red, small
+        if todo:
+            _lib.call("cg_norm_act_bwd_reduce_many", arr, len(todo), stream)
         # pass 2: dx and dW_i (db_i) with BatchNorm / PReLU undone on load
         t = _PointwiseMaps._block(x, ws, [None] * n)
         dx = torch.empty_like(x)
@@ -2539,6 +2543,22 @@ class _CollapseRows(torch.autograd.Function):
         return t
 
     @staticmethod
+    def _ask_sums(t, tr, x, rows):
+        """backward with a `transform`: the kernel also forms the channel sums of the producer's BatchNorm / PReLU backward and leaves them in
+        the transform record, where `_TowerMaps.backward` (which runs later) finds them (`fuse_sums` False in the record: not asked for).
+        Returns the kernel's scratch: the caller holds it over the launch."""
+        if tr is None or not tr.get("fuse_sums", True):
+            return None
+        C = x.shape[1]
+        red = _arena(x.device).take(2 * C + _lib.ALPHA_SLOTS)
+        small = torch.empty(3, C, dtype=torch.float32, device=x.device)
+        sums = torch.empty(int(_lib.lib().cg_collapse_sums_ws_floats(C, rows)) // 2, dtype=torch.float64, device=x.device)      # per-slice partials, all written
+        t.sums, t.red = sums.data_ptr(), red.data_ptr()
+        t.dgamma, t.dbeta, t.dalpha = small[0].data_ptr(), small[1].data_ptr(), small[2].data_ptr()
+        tr["red"], tr["small"] = red, small
+        return sums
+
+    @staticmethod
     def forward(ctx, want_stats, tr, x, w):
         ctx.set_materialize_grads(False)
         _chk(x)
@@ -2568,7 +2588,9 @@ class _CollapseRows(torch.autograd.Function):
         dw = torch.empty_like(w)
         zb = torch.empty(int(_lib.lib().cg_collapse_rows_ws_floats(C, T, w.shape[0])), dtype=torch.float32, device=x.device)      # per-slice dW partials, all written
         t.dy, t.dx, t.dW, t.ws = dy.data_ptr(), dx.data_ptr(), dw.data_ptr(), zb.data_ptr()
+        zs = _CollapseRows._ask_sums(t, ctx.tr, x, T)
         _lib.call("cg_collapse_rows_bwd", ctypes.byref(t), _stream(x))
+        del zb, zs
         return None, None, dx if ctx.needs_input_grad[2] else None, dw if ctx.needs_input_grad[3] else None
 
 
@@ -2619,7 +2641,9 @@ class _CollapseCols(torch.autograd.Function):
         dw = torch.empty_like(w)
         zb = torch.empty(int(_lib.lib().cg_collapse_cols_ws_floats(C, V, w.shape[0])), dtype=torch.float32, device=x.device)      # per-slice dW partials, all written
         t.dy, t.dx, t.dW, t.ws = dy.data_ptr(), dx.data_ptr(), dw.data_ptr(), zb.data_ptr()
+        zs = _CollapseRows._ask_sums(t, ctx.tr, x, V)
         _lib.call("cg_collapse_cols_bwd", ctypes.byref(t), _stream(x))
+        del zb, zs
         return None, None, dx if ctx.needs_input_grad[2] else None, dw if ctx.needs_input_grad[3] else None
 
 

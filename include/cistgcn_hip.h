@@ -257,6 +257,14 @@ typedef struct CgRowsConv {
   CgTailBN in_bn;
   const float* in_alpha;
   float* in_tap;                    /* forward, optional (with in_on): the activated input x' (B,C,T,V), written as it is formed (branch records of the parity tests) */
+  /* backward, optional (with in_on; `sums` and `red` together): the channel sums of the BatchNorm / PReLU backward of the producer of x,
+   * formed from the operands the kernel holds anyway.  With gh = dx PReLU'(u) and xhat = (x - mean) rstd:
+   *   red[2c] = sum gh, red[2c + 1] = sum gh xhat, red[2C] = sum_{u <= 0} dx u, red[2C + 1 .. 2C + CG_ALPHA_SLOTS - 1] = 0
+   * - what cg_norm_act_bwd_reduce_many leaves for cg_pointwise_maps_bwd (`bn_red`), summed in a fixed order (nothing to zero, the same
+   * bits from run to run); dgamma[c] = red[2c + 1], dbeta[c] = red[2c], dalpha[0] = red[2C] (each optional). */
+  double* sums;                     /* cg_collapse_sums_ws_floats(C, T) (rows) / (C, V) (cols) floats of scratch (need not be zeroed) */
+  double* red;                      /* [2C + CG_ALPHA_SLOTS] f64 */
+  float* dgamma; float* dbeta; float* dalpha;
 } CgRowsConv;
 int cg_collapse_rows_fwd(const CgRowsConv* t, void* stream);
 int cg_collapse_rows_bwd(const CgRowsConv* t, void* stream);
@@ -268,6 +276,8 @@ int cg_collapse_cols_fwd(const CgRowsConv* t, void* stream);
 int cg_collapse_cols_bwd(const CgRowsConv* t, void* stream);
 int cg_collapse_cols_supported(int C, int T, int V, int O);
 long long cg_collapse_cols_ws_floats(int C, int V, int O);
+/* host-only: floats of CgRowsConv.sums for C channels of `rows` rows each (rows = T for cg_collapse_rows_bwd, V for cg_collapse_cols_bwd), any B */
+long long cg_collapse_sums_ws_floats(int C, int rows);
 
 /* ---- dilated 3x3 convolutions of the time extrapolator, FPN CISTGCN.py:54-79: n <= 3 convolutions with padding = dilation =
  * dil[i] of ONE input (B,C,H,W) = (batch, frames, channels, joints).  A sample fits in LDS with its halo: forward, input gradient

@@ -1,0 +1,40 @@
+"""The channel sums the collapsing backward kernels form on the way (CgRowsConv.sums / red, csrc/collapse_rows.hip) on the CPU shim: against
+fp64 at 16 * 2^-24 * sum |term|, next to cg_norm_act_bwd_reduce_many on the same inputs, bit-equal from run to run; the mixed case through
+`ops` and the agreement with the route through the reduction pass.  Checks, shapes and bounds: tests/tower_sums_checks.py."""
+import pytest
+
+import emu
+import collapse_pieces_shapes as S
+import tower_sums_checks as C
+
+
+@pytest.fixture(scope="module", autouse=True)
+def _emulated_kernels():
+    emu.install()
+    yield
+    emu.uninstall()
+
+
+def test_geometry_has_the_properties_the_shapes_are_chosen_for():
+    C.assert_properties()
+
+
+@pytest.mark.parametrize("train", (True, False), ids=("train", "eval"))
+@pytest.mark.parametrize("shape", C.FRAME, ids=C.ident)
+def test_frame_axis_sums(shape, train):
+    C.check_sums("cpu", shape, cols=False, train=train)
+
+
+@pytest.mark.parametrize("train", (True, False), ids=("train", "eval"))
+@pytest.mark.parametrize("shape", C.JOINT, ids=C.ident)
+def test_joint_axis_sums(shape, train):
+    C.check_sums("cpu", shape, cols=True, train=train)
+
+
+def test_mixed_case_two_maps_fused_one_without_sums():
+    C.check_routes_agree("cpu", (5, 10, (6, 12, 8), 14, 6, 5), fuse=(True, True, False))
+
+
+@pytest.mark.parametrize("shape", S.TOWER, ids=S.ident)
+def test_fused_route_agrees_with_the_reduction_pass(shape):
+    C.check_routes_agree("cpu", shape, fuse=[True] * len(shape[2]))
