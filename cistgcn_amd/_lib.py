@@ -148,6 +148,19 @@ class GateHead(ctypes.Structure):
                 ("drop_p", c_float), ("pad2", c_int), ("seed", c_void_p), ("p", GatePath * 2)]
 
 
+class MidItem(ctypes.Structure):
+    _fields_ = [("kind", c_int), ("C", c_int), ("L", c_int), ("O", c_int), ("sb_", c_int), ("ns_", c_int),
+                ("x", c_void_p), ("x_ld", c_longlong), ("bn", TailBN), ("stats_ld", c_longlong), ("alpha", c_void_p), ("W", c_void_p),
+                ("salt", c_uint), ("pad", c_int), ("y", c_void_p), ("tap", c_void_p),
+                ("dy", c_void_p), ("dx", c_void_p), ("dW", c_void_p), ("dgamma", c_void_p), ("dbeta", c_void_p), ("dalpha", c_void_p),
+                ("g", c_void_p), ("part", c_void_p), ("wpart", c_void_p)]
+
+
+class BlockMid(ctypes.Structure):
+    _fields_ = [("B", c_int), ("train", c_int), ("n", c_int), ("pad", c_int),
+                ("drop_p", c_float), ("pad2", c_int), ("seed", c_void_p), ("it", MidItem * 6)]
+
+
 class CtxHeads(ctypes.Structure):
     _fields_ = [("B", c_int), ("P", c_int), ("C", c_int), ("train", c_int), ("x", c_void_p), ("xstats", c_void_p),
                 ("w", c_void_p * 2), ("bn", TailBN * 2), ("alpha", c_void_p * 2),
@@ -240,6 +253,10 @@ _SIGNATURES = {
     "cg_gate_head_bwd": [POINTER(GateHead), P],
     "cg_gate_head_supported": [c_int, c_int, c_int],
     "cg_gate_head_scratch_floats": [c_int, c_int, c_int],
+    "cg_block_mid_fwd": [POINTER(BlockMid), P],
+    "cg_block_mid_bwd": [POINTER(BlockMid), P],
+    "cg_block_mid_supported": [c_int, c_int, c_int, c_int, c_int],
+    "cg_block_mid_geometry": [c_int, c_int, c_int, c_int, c_int, POINTER(c_int)],
     "cg_context_heads_fwd": [POINTER(CtxHeads), P],
     "cg_context_heads_bwd": [POINTER(CtxHeads), P],
     "cg_context_heads_red_doubles": [c_int],

@@ -234,6 +234,7 @@ class CISTGCN(nn.Module):
         self.fused_adj = True        # seed, expansor and adjacency of both Map2Adj towers as phase kernels (ops.map2adj_tail)
         self.fused_maps = True       # the first-level maps of a block (towers, gates, residual maps) and of the context heads stacked
         self.fused_defer = True      # BatchNorm + PReLU of the first tower level applied by the collapsing kernels on load
+        self.fused_mid = True        # the gates' and towers' BatchNorm -> Dropout -> map between the collapsing kernels and the fused tails (ops.block_mid)
         self.stack_min_elements = 1 << 21      # block inputs smaller than this keep one contraction per first-level map
         # The reference edits the config lists in place (CISTGCN.py:514-517,548); copies are used here
         # so that one `opt` can build several models.
@@ -464,12 +465,20 @@ class CISTGCN(nn.Module):
         # 1. every first-level map of xn
         # the two gate paths start with the same (T,1) convolution shape on the same input: one convolution of the stacked weights
         # (the block input travels once instead of twice, forward and in both gradients)
-        gate_rows = None
+        gate_rows = gate_sums = None
+        # the middle of the block as one operator (csrc/block_mid.hip): only between the whole-sample collapsing kernels and the two fused tails
+        adj_fused = self.fused_adj and T <= 64 and V <= 64
+        mid_on = self.fused_mid and big and adj_fused
+        g4s, g4t = m.conv_s[4], m.conv_t[4]
+        mid_g = (mid_on and gates and x_gates is not None and g4s.bias is None and g4t.bias is None
+                 and tuple(g4s.kernel_size) == (1, V) and tuple(g4t.kernel_size) == (1, V) and g4s.out_channels == g4t.out_channels
+                 and ops.gate_head_ok(B, g4s.out_channels, 2 + 2 * T, (m.conv_s[7], m.conv_t[7], m.map_s[3], m.map_t[3]))
+                 and ops.block_mid_ok(B, [(0, cs.out_channels, V, g4s.out_channels, m.conv_s[3]), (0, cs.out_channels, V, g4t.out_channels, m.conv_t[3])]))
         if gates:
             O = cs.out_channels
             w2 = ops.cat_channels([cs.weight.view(1, O, -1), ct.weight.view(1, O, -1)]).view(2 * O, cs.in_channels, xn.shape[2])
             if x_gates is not None:
-                gate_rows = ops.collapse_rows(x_gates, w2)[0]            # whole-sample kernel (csrc/collapse_rows.hip)
+                gate_rows, gate_sums = ops.collapse_rows(x_gates, w2, mid_g and tr)      # whole-sample kernel (csrc/collapse_rows.hip)
                 items = []
             else:
                 items = [(("och,bchw->bow", w2, xn, None, None, None), None)]
@@ -548,10 +557,17 @@ class CISTGCN(nn.Module):
             if has_bres:
                 calls.append(dict(x=o[k], bn=m.residual[1]))
         # site numbers as on the row-kernel path in every case: gates, four (dropout-free) tower sites, residual maps
+        mid_x = mid_salts = None
+        if mid_g:
+            # conv_s.1 / conv_t.1 with their Dropout and PReLU run inside ops.block_mid below; their sites are numbered here
+            mid_x, mid_salts = [gs[0].squeeze(2), gt[0].squeeze(2)], (self._site + 1, self._site + 2)
+            self._site += 2
+            if self.drop_trace is not None:
+                self.drop_trace[m.conv_s[1]], self.drop_trace[m.conv_t[1]] = mid_salts
         if towers_done is None:
-            r = self._na_many(calls)
+            r = [None, None] + (self._na_many(calls[2:]) if len(calls) > 2 else []) if mid_g else self._na_many(calls)
         else:
-            r = self._na_many(calls[:2])
+            r = [None, None] if mid_g else self._na_many(calls[:2])
             self._site += 4
             r = r + towers_done + (self._na_many(calls[2 + n_tower_calls:]) if len(calls) > 2 + n_tower_calls else [])
         if res_done is not None:
@@ -561,7 +577,7 @@ class CISTGCN(nn.Module):
         res = r[6:8] if has_res else x_res
         bres = r[-1] if has_bres else x_bres
         # 3. collapsing convolutions
-        items = [_cols_item(gs, m.conv_s[4], tr), _cols_item(gt, m.conv_t[4], tr)]
+        items = [] if mid_g else [_cols_item(gs, m.conv_s[4], tr), _cols_item(gt, m.conv_t[4], tr)]
         rows3, cols3 = {}, {}
         for i, a in enumerate(maps):
             c3 = a.time_compress[3]
@@ -586,7 +602,7 @@ class CISTGCN(nn.Module):
             tp_ = [b_ for a_ in maps for b_ in (a_.time_compress[2], a_.joint_compress[2])]
             for mod, tr_ in zip(tp_, tower_tr):
                 self.act_trace[mod] = (tr_["tap"].detach(), None)
-        o = _run_items(items)
+        o = ([None, None] if mid_g else []) + (_run_items(items) if items else [])
         if rows3 or cols3:                                               # back into the order gates | (time, joint) per tower
             rest, o = o[2:], o[:2]
             for i in range(len(maps)):
@@ -594,21 +610,53 @@ class CISTGCN(nn.Module):
                 o.append(cols3[i] if i in cols3 else rest.pop(0))
         # 4. BatchNorm tails
         Cg = m.conv_s[4].out_channels
-        gate_fused = (o[0][0].shape[1] == Cg and o[0][0].numel() == B * Cg and
-                      ops.gate_head_ok(B, Cg, stats_s.shape[1], (m.conv_s[7], m.conv_t[7], m.map_s[3], m.map_t[3])))
+        gate_fused = mid_g or (o[0][0].shape[1] == Cg and o[0][0].numel() == B * Cg and
+                               ops.gate_head_ok(B, Cg, stats_s.shape[1], (m.conv_s[7], m.conv_t[7], m.map_s[3], m.map_t[3])))
         tower_calls = []
         for i, a in enumerate(maps):
             tower_calls += [dict(x=o[2 + 2 * i], bn=a.time_compress[4], drop=True), dict(x=o[3 + 2 * i], bn=a.joint_compress[4], drop=True)]
+        tower_mid = [(a.time_compress, a.joint_compress)[k] for a in maps for k in (0, 1)]
+        mid_t = (mid_on and gate_fused and len(rows3) == len(maps) and len(cols3) == len(maps) and all(c[6].bias is None for c in tower_mid)
+                 and ops.block_mid_ok(B, [(1, o[2 + k][0].shape[1], o[2 + k][0].numel() // (B * o[2 + k][0].shape[1]), c[6].out_channels, None)
+                                          for k, c in enumerate(tower_mid)]))
         if gate_fused:
             # everything of the two gate paths behind their (1,V) convolutions in ONE launch (csrc/gate_head.hip); the site ids are the ones
             # the row-kernel chain numbers: conv_s.5 / conv_t.5 in front of the four tower sites, map_s.1 / map_t.1 behind them
             s2 = (self._site + 1, self._site + 2)
             self._site += 2
-            r = [None, None] + self._na_many(tower_calls)
+            if mid_t:
+                tower_salts = tuple(self._site + 1 + k for k in range(len(tower_mid)))
+                self._site += len(tower_mid)
+                if self.drop_trace is not None:
+                    for c, salt in zip(tower_mid, tower_salts):
+                        self.drop_trace[c[4]] = salt
+                r = [None] * (2 + len(tower_mid))
+            else:
+                r = [None, None] + self._na_many(tower_calls)
             s3 = (self._site + 1, self._site + 2)
             self._site += 2
             if self.drop_trace is not None:
                 self.drop_trace[m.conv_s[5]], self.drop_trace[m.conv_t[5]], self.drop_trace[m.map_s[1]], self.drop_trace[m.map_t[1]] = s2[0], s2[1], s3[0], s3[1]
+            mid_out = []
+            if mid_g or mid_t:
+                # gates: BatchNorm -> Dropout -> PReLU -> (1,V) convolution; towers: BatchNorm -> Dropout -> last 1x1 map: one launch, two backward
+                mitems = []
+                if mid_g:
+                    for i, cv in enumerate((m.conv_s, m.conv_t)):
+                        mitems.append(dict(kind=0, x=mid_x[i], bn=cv[1], prelu=cv[3], weight=cv[4].weight.view(Cg, -1, V), salt=mid_salts[i],
+                                           stats=(gate_sums, i * mid_x[i].shape[1], 2 * mid_x[i].shape[1]) if tr else None))
+                if mid_t:
+                    for k, c in enumerate(tower_mid):
+                        y, st = o[2 + k]
+                        mitems.append(dict(kind=1, x=y.view(B, y.shape[1], -1), bn=c[4], prelu=None, weight=c[6].weight.view(c[6].out_channels, y.shape[1]),
+                                           salt=tower_salts[k], stats=(st, 0, y.shape[1]) if tr else None))
+                mtaps = [] if self.act_trace is not None else None
+                mid_out = ops.block_mid(mitems, tr, drop_p=self.dropout, taps=mtaps)
+                if mid_g:
+                    o[0], o[1] = (mid_out[0], None), (mid_out[1], None)
+                    mid_out = mid_out[2:]
+                    if mtaps is not None:
+                        self.act_trace[m.conv_s[3]], self.act_trace[m.conv_t[3]] = (mtaps[0].unsqueeze(2), None), (mtaps[1].unsqueeze(2), None)
             taps = [] if self.act_trace is not None else None
             m.w1, m.w2 = ops.gate_head([o[0][0].view(B, Cg), o[1][0].view(B, Cg)], [stats_s, stats_t], [m.conv_s, m.conv_t], [m.map_s, m.map_t], tr,
                                        drop_p=self.dropout, salts=((s2[0], s3[0]), (s2[1], s3[1])), taps=taps)
@@ -623,9 +671,12 @@ class CISTGCN(nn.Module):
             ht = ops.cat_channels([r[1].view(B, -1), stats_t])
             items = [_lin_item(hs, m.map_s[0], tr), _lin_item(ht, m.map_t[0], tr)]
         # 5. gate Linear + last tower maps
-        for i, a in enumerate(maps):
-            items += [_pw_item(r[2 + 2 * i], a.time_compress[6], False), _pw_item(r[3 + 2 * i], a.joint_compress[6], False)]
-        o = _run_items(items)
+        if mid_t:
+            o = [(y, None) for y in mid_out]
+        else:
+            for i, a in enumerate(maps):
+                items += [_pw_item(r[2 + 2 * i], a.time_compress[6], False), _pw_item(r[3 + 2 * i], a.joint_compress[6], False)]
+            o = _run_items(items)
         if gate_fused:
             o = [None, None] + o
         else:
@@ -635,7 +686,7 @@ class CISTGCN(nn.Module):
         for i, d in enumerate(doms):
             q, s = o[2 + 2 * i][0].view(B, T, V), o[3 + 2 * i][0].view(B, V, T)
             seeds.append((0 if d.domain == "space" else 1, s, q))
-        if self.fused_adj and T <= 64 and V <= 64:
+        if adj_fused:
             # seed, expansor and adjacency of both towers in two phase launches (csrc/map2adj_tail.hip); the seed is never stored
             if not gate_fused:
                 o = _run_items([_lin_item(g[0], m.map_s[4], False), _lin_item(g[1], m.map_t[4], False)])

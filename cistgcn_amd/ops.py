@@ -2156,6 +2156,134 @@ def gate_head(zs, stats, convs, maps, train, drop_p=0.0, salts=((0, 0), (0, 0)),
     return list(_GateHead.apply(cfg, n, *ts))
 
 
+def _mid_geometry(B, kind, C, L, O):
+    out = (ctypes.c_int * 8)()
+    _lib.check(_lib.lib().cg_block_mid_geometry(B, kind, C, L, O, out), "cg_block_mid_geometry")      # host-only query: not a launch
+    return list(out)
+
+
+def block_mid_ok(B, items):
+    """True when `block_mid` takes the items: (kind, C, L, O, prelu or None) each, kind 0 = full, 1 = pointwise."""
+    return 1 <= len(items) <= 6 and all(bool(_lib.lib().cg_block_mid_supported(B, k, C, L, O)) and (p is None or p.weight.numel() == 1)
+                                        for k, C, L, O, p in items)
+
+
+class _BlockMid(torch.autograd.Function):
+    """Middle of a DSTD_GC block (csrc/block_mid.hip): per item x (B,C,L) -> BatchNorm2d -> Dropout [-> PReLU] -> bias-free map, full
+    (B,O) or pointwise (B,O,L).  Tensor inputs per item: x, gamma, beta, alpha (or None), W (5 each)."""
+
+    @staticmethod
+    def _block(cfg, ts, saves, train, dev):
+        items = cfg["items"]
+        t = _lib.BlockMid()
+        t.B, t.train, t.n = ts[0].shape[0], 1 if train else 0, len(items)
+        p = float(cfg.get("drop_p", 0.0)) if train else 0.0
+        t.drop_p = p
+        if p > 0.0:
+            t.seed = seed_state(dev).data_ptr()
+        for i, it in enumerate(items):
+            x, _, _, a, w = ts[5 * i:5 * i + 5]
+            q = t.it[i]
+            q.kind, q.C, q.L, q.O = it["kind"], x.shape[1], x.shape[2], w.shape[0]
+            q.x, q.x_ld = x.data_ptr(), x.stride(0)
+            _tail_bn(q.bn, it["bn"], None, saves[i], train)
+            st = it.get("stats")
+            if train and st is not None:
+                q.bn.stats, q.stats_ld = st[0].data_ptr() + 16 * st[1], st[2]
+            q.alpha, q.W, q.salt = _ptr(a), w.data_ptr(), it["salt"]
+        return t, p
+
+    @staticmethod
+    def forward(ctx, cfg, *ts):
+        ctx.set_materialize_grads(False)
+        items = cfg["items"]
+        dev, f32, train = ts[0].device, torch.float32, bool(cfg["train"])
+        B = ts[0].shape[0]
+        ts = list(ts)
+        for i, it in enumerate(items):
+            x, w = ts[5 * i], ts[5 * i + 4]
+            _chk(x)
+            C, L = x.shape[1], x.shape[2]
+            if x.dim() != 3 or (L > 1 and x.stride(2) != 1) or (C > 1 and x.stride(1) != L) or x.stride(0) < C * L:
+                raise ValueError("block_mid expects (B,C,L) inputs with dense samples")
+            if w.numel() != w.shape[0] * C * (L if it["kind"] == 0 else 1):
+                raise ValueError("block_mid: weight %s does not fit input %s" % (tuple(w.shape), tuple(x.shape)))
+            if not w.is_contiguous():
+                ts[5 * i + 4] = _copy(w)
+            if train and it.get("stats") is None:
+                raise ValueError("block_mid needs the producer's channel sums in train mode")
+            if train and B * L < 2:
+                raise ValueError("Expected more than 1 value per channel when training, got input size %s" % (tuple(x.shape),))
+        saves = [torch.empty(2, ts[5 * i].shape[1], dtype=f32, device=dev) for i in range(len(items))]
+        t, p = _BlockMid._block(cfg, ts, saves, train, dev)
+        taps = cfg.get("taps")
+        ys = []
+        for i, it in enumerate(items):
+            x, w = ts[5 * i], ts[5 * i + 4]
+            ys.append(torch.empty((B, w.shape[0]) if it["kind"] == 0 else (B, w.shape[0], x.shape[2]), dtype=f32, device=dev))
+            t.it[i].y = ys[-1].data_ptr()
+            if taps is not None:
+                taps.append(torch.empty(x.shape, dtype=f32, device=dev) if ts[5 * i + 3] is not None else None)
+                t.it[i].tap = _ptr(taps[-1])
+        _lib.call("cg_block_mid_fwd", ctypes.byref(t), _stream(ts[0]))
+        ctx.cfg, ctx.p = cfg, p
+        ctx.seed_epoch = seed_epoch(dev) if p > 0.0 else None
+        ctx.has_alpha = [ts[5 * i + 3] is not None for i in range(len(items))]
+        ctx.save_for_backward(*[v for v in ts if v is not None], *saves)
+        return tuple(ys)
+
+    @staticmethod
+    def backward(ctx, *dys):
+        cfg = ctx.cfg
+        items = cfg["items"]
+        n = len(items)
+        sv = list(ctx.saved_tensors)
+        saves = sv[len(sv) - n:]
+        ts = []
+        for i in range(n):
+            ts += [sv.pop(0), sv.pop(0), sv.pop(0), sv.pop(0) if ctx.has_alpha[i] else None, sv.pop(0)]
+        dev, f32, train = ts[0].device, torch.float32, bool(cfg["train"])
+        _check_seed_epoch(ctx, dev, "block_mid")
+        B = ts[0].shape[0]
+        t, _ = _BlockMid._block(cfg, ts, saves, train, dev)
+        keep, grads = [], []
+        for i, it in enumerate(items):
+            x, _, _, a, w = ts[5 * i:5 * i + 5]
+            C, L, O = x.shape[1], x.shape[2], w.shape[0]
+            d = dys[i]
+            if d is None:
+                d = _zeros(B * O * (1 if it["kind"] == 0 else L), dev)[0]
+            d = d if d.is_contiguous() else _copy(d)
+            geo = _mid_geometry(B, it["kind"], C, L, O)
+            dx = torch.empty(B, C, L, dtype=f32, device=dev)
+            dw = torch.empty(w.shape, dtype=f32, device=dev)
+            small = torch.empty(3, C, dtype=f32, device=dev)
+            g = torch.empty(B * C * L, dtype=f32, device=dev)                       # all three: every element written by launch 1
+            part = torch.empty(geo[4], dtype=torch.float64, device=dev)
+            wpart = torch.empty(geo[5], dtype=f32, device=dev)
+            q = t.it[i]
+            q.dy, q.dx, q.dW, q.g, q.part, q.wpart = d.data_ptr(), dx.data_ptr(), dw.data_ptr(), g.data_ptr(), part.data_ptr(), wpart.data_ptr()
+            q.dgamma, q.dbeta, q.dalpha = small[0].data_ptr(), small[1].data_ptr(), small[2].data_ptr() if a is not None else None
+            keep += [d, g, part, wpart]
+            grads += [dx, small[0], small[1], small[2, :1].reshape(a.shape) if a is not None else None, dw]
+        _lib.call("cg_block_mid_bwd", ctypes.byref(t), _stream(ts[0]))
+        del keep
+        return (None,) + tuple(g if (g is not None and ctx.needs_input_grad[1 + k]) else None for k, g in enumerate(grads))
+
+
+def block_mid(items, train, drop_p=0.0, taps=None):
+    """Outputs of up to six items of a block's middle in one launch (two backward).  An item is a dict: kind (0 full: y (B,O) from W (O,C,L);
+    1 pointwise: y (B,O,L) from W (O,C)), x (B,C,L) with dense samples, bn (BatchNorm2d holder), prelu (single-slope holder or None), weight,
+    salt (dropout site id) and, in train mode, stats = (f64 sums tensor of the producing collapse kernel, first channel, channels per row).
+    `taps`: list that receives per item the PReLU output (None for items without PReLU)."""
+    cfg = {"train": bool(train), "drop_p": float(drop_p), "taps": taps,
+           "items": tuple({"kind": int(it["kind"]), "bn": it["bn"], "salt": int(it["salt"]), "stats": it.get("stats")} for it in items)}
+    ts = []
+    for it in items:
+        ts += [it["x"], it["bn"].weight, it["bn"].bias, it["prelu"].weight if it.get("prelu") is not None else None, it["weight"]]
+    return list(_BlockMid.apply(cfg, *ts))
+
+
 def context_heads_ok(x, hidden):
     """True when `context_heads` takes the two one-channel heads of x (B,1,H,W)."""
     return x.dim() == 4 and x.shape[1] == 1 and x.is_contiguous() and hidden <= 64 and x.shape[2] * x.shape[3] <= 16384

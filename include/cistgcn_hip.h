@@ -418,6 +418,43 @@ int cg_gate_head_bwd(const CgGateHead* t, void* stream);
 int cg_gate_head_supported(int B, int C, int S);
 long long cg_gate_head_scratch_floats(int B, int C, int S);
 
+/* ---- middle of a DSTD_GC block (csrc/block_mid.hip): CISTGCN.py:331-352 (conv_s|t slots 5-7 and the (1,V) convolution) and :138-163
+ * (time_compress / joint_compress slots 4-6) --------------------------------------------------------------------------
+ * up to six items, each x (B,C,L) -> BatchNorm2d -> Dropout [-> PReLU] = h, then
+ *   kind 0 (full):      y[b,o]   = sum_{c,l} W[o,c,l] h[b,c,l]     (B,O)
+ *   kind 1 (pointwise): y[b,o,l] = sum_c W[o,c] h[b,c,l]           (B,O,L)
+ * C, L, O <= 64.  One launch forward (train mode: bn.stats = the producer's replicated f64 sums of x, rows of stats_ld channels), two backward,
+ * cut at the batch statistics.  Backward scratch per item (sizes from cg_block_mid_geometry, nothing has to be zero): g (B,C,L) floats, `part`
+ * doubles, `wpart` floats.  No atomics: every gradient is the same from run to run.  sb_ / ns_ are filled in by the launcher. */
+typedef struct CgMidItem {
+  int kind, C, L, O;
+  int sb_, ns_;
+  const float* x; long long x_ld;
+  CgTailBN bn; long long stats_ld;
+  const float* alpha;
+  const float* W;
+  unsigned int salt; int pad;
+  float* y;
+  float* tap;
+  const float* dy;
+  float* dx;
+  float* dW; float* dgamma; float* dbeta; float* dalpha;
+  float* g;
+  double* part;
+  float* wpart;
+} CgMidItem;
+typedef struct CgBlockMid {
+  int B, train, n, pad;
+  float drop_p; int pad2; const unsigned long long* seed;
+  CgMidItem it[6];
+} CgBlockMid;
+int cg_block_mid_fwd(const CgBlockMid* t, void* stream);
+int cg_block_mid_bwd(const CgBlockMid* t, void* stream);
+int cg_block_mid_supported(int B, int kind, int C, int L, int O);
+/* out[8]: samples per slice, slices, dynamic LDS bytes forward / backward, `part` doubles, `wpart` floats, passes of the full product over
+ * the groups of four output rows, passes of the full backward over the columns */
+int cg_block_mid_geometry(int B, int kind, int C, int L, int O, int* out);
+
 /* ---- ContextLayer heads 1 and 3, CISTGCN.py:408-418 with :465 / :467 ---------------------------------
  * Conv2d(1, C, 1, bias=False) -> BatchNorm2d(C) -> PReLU of the one-channel tensor x (B,1,T_out,3V), reduced over the positions:
  *   head 0 (context_conv1): y[0][b,c] = max_p z (first arg-max in `arg`), head 1 (context_conv3): y[1][b,c] = mean_p z.

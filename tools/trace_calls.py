@@ -45,6 +45,9 @@ def call(name, *args):
                                                       " ystats" if args[0][i].ystats else "") for i in range(n))
     elif name == "cg_sum_many":
         tag += " n=%d %s" % (args[3], tuple(args[1]._obj.n))
+    elif name in ("cg_block_mid_fwd", "cg_block_mid_bwd"):
+        t = args[0]._obj
+        tag += " B%d " % t.B + " | ".join("%s C%d L%d O%d" % ("pw" if t.it[i].kind else "full", t.it[i].C, t.it[i].L, t.it[i].O) for i in range(t.n))
     elif name.startswith("cg_dstd_tail") or name.startswith("cg_map2adj_tail"):
         tag += " phase %d" % (args[1] if name.startswith("cg_dstd") else args[2])
     rows.append((tag, nbytes, e0, e1))
