@@ -177,6 +177,13 @@ class AttackStep(ctypes.Structure):
                 ("steps", c_void_p), ("frozen_at", c_void_p)]
 
 
+class DeepfoolStep(ctypes.Structure):
+    _fields_ = [("B", c_int), ("T", c_int), ("To", c_int), ("V", c_int), ("patience", c_int), ("pad", c_int),
+                ("x", c_void_p), ("grad", c_void_p), ("pred", c_void_p), ("mask", c_void_p), ("loss", c_void_p),
+                ("best", c_void_p), ("stall", c_void_p), ("active", c_void_p), ("w", c_void_p), ("queries", c_void_p), ("n_active", c_void_p),
+                ("steps", c_void_p), ("frozen_at", c_void_p)]
+
+
 class EvalMetricsArgs(ctypes.Structure):      # CgEvalMetrics
     _fields_ = [("B", c_int), ("To", c_int), ("J", c_int), ("Nb", c_int), ("frames", c_int), ("pad", c_int),
                 ("pred", c_void_p), ("target", c_void_p), ("speeds", c_void_p), ("bones", c_void_p),
@@ -279,6 +286,7 @@ _SIGNATURES = {
     "cg_mpjpe_sample_bwd": [P, P, P, P, c_int, c_int, P],
     "cg_attack_step": [POINTER(AttackStep), P],
     "cg_attack_step_max_floats": [],
+    "cg_deepfool_step": [POINTER(DeepfoolStep), P],
     "cg_eval_metrics": [POINTER(EvalMetricsArgs), P],
     "cg_eval_metrics_ws_doubles": [c_int, c_int, c_int],
     "cg_attack_metrics": [POINTER(AttackMetricsArgs), P],

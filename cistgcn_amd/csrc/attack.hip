@@ -3,11 +3,13 @@
 //   cg_mpjpe_sample_fwd / _bwd   losses.mpjpe(reduce_axis=[1,2]) (losses/losses.py:50-61 as called at :175-178) and its adjoint with
 //                                one upstream weight per sample (the fixed-shape form of the `[op_mask]` re-slicing of :518-521)
 //   cg_attack_step               compute_gradient (:401-417, :469-496, :581-610) + the early-stop bookkeeping (:517, :529-538)
+//   cg_deepfool_step             DEEPFOOL's compute_gradient (:697-717) + the same bookkeeping (:755-767)
 // One workgroup per sample everywhere: a sample is T*V*3 floats (15 KB at T=50, V=25), its three reductions (y extent, |grad|_1,
 // max |x_adv - x0|) never leave the workgroup, nothing is accumulated with floating-point atomics and every result is
 // bit-reproducible from run to run (the bookkeeping compares losses with `>`).
 #include "cg_common.h"
 
+#include <limits.h>
 #include <math.h>
 
 #define CG_ATTACK_THREADS 256
@@ -209,5 +211,91 @@ extern "C" int cg_attack_step(const CgAttackStep* a, void* stream_) {
   const size_t lds = (size_t)n * 3 * sizeof(float);
   if (cg_lds_limit((const void*)cg_attack_step_kernel, lds) != hipSuccess) return CG_ESHAPE;
   hipLaunchKernelGGL(cg_attack_step_kernel, dim3((unsigned)a->B), dim3(CG_ATTACK_THREADS), lds, (hipStream_t)stream_, *a);
+  return cg_launch_status();
+}
+
+// ---------------------------------------------------------------------------------------------
+// the DeepFool step (DEEPFOOL.compute_gradient, :697-717): x += mask * r,  r = -grad * mean_t(pred) / (||grad||_1 + 1e-10)
+// ---------------------------------------------------------------------------------------------
+struct CgDeepfoolStep {      // mirrored by include/cistgcn_hip.h and cistgcn_amd/_lib.py
+  int B, T, To, V, patience, pad;
+  float* x;             // (B,T,V,3) in: x_i, out: x_adv (= the next x_i)
+  const float* grad;    // (B,T,V,3) d(sum_b w_b loss_b)/dx_i
+  const float* pred;    // (B,To,V,3) the prediction of the same forward pass
+  const float* mask;    // (T,V) 1 = this joint of this frame may move; null = all
+  const float* loss;    // (B,) loss_b of this iteration; null (with the eight below) = no bookkeeping, every sample steps
+  float* best; int* stall; int* active; float* w; int* queries; int* n_active; int* steps; int* frozen_at;      // as in CgAttackStep
+};
+
+// The To-means of the prediction's V*3 columns stay in LDS (f64) up to this many columns; a wider skeleton re-reads its column in
+// every element, in the same order, so the two paths give the same bits.  Half the default dynamic LDS: no driver call to raise it.
+#define CG_DEEPFOOL_LDS_COLS (CG_LDS_DEFAULT / 2 / (int)sizeof(double))
+
+__device__ __forceinline__ double cg_deepfool_col_mean(const float* pred, int c, int cols, int To) {
+  double s = 0.0;
+  for (int t = 0; t < To; ++t) s += (double)pred[(long long)t * cols + c];
+  return s / (double)To;
+}
+
+// The L1 norm and the column means are accumulated in f64 in a fixed order (lanes, then waves; frames in order); r is rounded to
+// fp32 once and added once.  An element that does not move (frozen sample, mask 0, r = 0) is not written.
+__global__ __launch_bounds__(CG_ATTACK_THREADS) void cg_deepfool_step_kernel(CgDeepfoolStep a, int staged) {
+  __shared__ double redd[CG_ATTACK_THREADS / CG_WAVE];
+  const int b = blockIdx.x, tid = threadIdx.x, cols = a.V * 3;
+  const long long n = (long long)a.T * cols;
+  const bool book = a.loss != nullptr;
+  const bool act = book ? a.active[b] != 0 : true;      // at the START of this iteration; thread 0 rewrites it behind several barriers
+  // A frozen sample is left alone entirely (there is no reset here), so a launch that starts with every sample frozen changes nothing
+  // without the frozen_at >= k census of cg_attack_step_kernel; steps / frozen_at are kept up for the state's other users.
+  if (!act) {
+    if (tid == 0) a.steps[b] += 1;
+    return;
+  }
+
+  const float* g = a.grad + (long long)b * n;
+  const float* p = a.pred + (long long)b * a.To * cols;
+  float* x = a.x + (long long)b * n;
+  double* pm = reinterpret_cast<double*>(cg_dyn_lds);
+  double l1 = 0.0;
+  for (long long i = tid; i < n; i += CG_ATTACK_THREADS) l1 += (double)fabsf(g[i]);
+  if (staged)
+    for (int c = tid; c < cols; c += CG_ATTACK_THREADS) pm[c] = cg_deepfool_col_mean(p, c, cols, a.To);
+  const double norm1 = cg_attack_reduce(l1, redd, CgOpAdd()) + 1e-10;      // its barriers also publish pm
+  for (long long i = tid; i < n; i += CG_ATTACK_THREADS) {
+    const float m = a.mask ? a.mask[i / 3] : 1.f;
+    if (m == 0.f) continue;
+    const int c = (int)(i % cols);
+    const double mean = staged ? pm[c] : cg_deepfool_col_mean(p, c, cols, a.To);
+    const float r = (float)(-((double)g[i] * mean) / norm1);      // an all-zero gradient: 0 / 1e-10 = 0, not NaN
+    if (r != 0.f) x[i] = x[i] + m * r;
+  }
+
+  if (book && tid == 0) {       // the bookkeeping of cg_attack_step_kernel (:755-767 repeat :529-538)
+    const int k = a.steps[b];
+    a.steps[b] = k + 1;
+    a.queries[b] += 1;
+    const float l = a.loss[b];
+    int st = a.stall[b];
+    if (l > a.best[b]) a.best[b] = l;
+    else a.stall[b] = ++st;
+    const bool freeze = st >= a.patience;
+    a.w[b] = freeze ? 0.f : 1.f / (float)a.B;
+    if (freeze) {
+      a.active[b] = 0;
+      a.frozen_at[b] = k;
+      atomicAdd(a.n_active, -1);
+    }
+  }
+}
+
+extern "C" int cg_deepfool_step(const CgDeepfoolStep* a, void* stream_) {
+  if (!a || !a->x || !a->grad || !a->pred) return CG_EARG;
+  const int given = !!a->loss + !!a->best + !!a->stall + !!a->active + !!a->w + !!a->queries + !!a->n_active + !!a->steps + !!a->frozen_at;
+  if (given != 0 && given != 9) return CG_EARG;
+  if (a->B <= 0 || a->T <= 0 || a->To <= 0 || a->V <= 0 || (given && a->patience <= 0)) return CG_ESHAPE;
+  if (a->V > INT_MAX / 3) return CG_ESHAPE;
+  const int cols = a->V * 3, staged = cols <= CG_DEEPFOOL_LDS_COLS;
+  hipLaunchKernelGGL(cg_deepfool_step_kernel, dim3((unsigned)a->B), dim3(CG_ATTACK_THREADS), staged ? (size_t)cols * sizeof(double) : 0,
+                     (hipStream_t)stream_, *a, staged);
   return cg_launch_status();
 }

@@ -1,5 +1,5 @@
 """Input-space attacks on the eval-mode model, on the device: counterparts of the reference's robustness tooling
-(`environment/adversarial_attacks.py`: FGSM :375-437, IFGSM :442-548, MIFGSM :553-665, NOATTACK :781-805).
+(`environment/adversarial_attacks.py`: FGSM :375-437, IFGSM :442-548, MIFGSM :553-665, DEEPFOOL :668-776, NOATTACK :781-805).
 
 The classes take the reference's constructor keywords, so an `adversarial_attacks:` YAML section maps onto them directly, and
 `attack.apply(model, x, target)` returns the adversarial poses.  `x` (B,T,V,3) is the model's own joint set (the `test_mode=False`
@@ -55,16 +55,20 @@ def selection_mask(T, V, joints=None, frames=None, device=None):
     return m.contiguous().to(device)
 
 
-def loss_and_input_grad(model, x, target, w):
+def loss_and_input_grad(model, x, target, w, with_pred=False):
     """Eval-mode forward, one loss per sample and d(sum_b w_b loss_b)/dx.  `x` is a leaf that requires grad; the parameters'
-    `.grad` are not touched.  Returns (loss (B,), grad like x), both detached."""
+    `.grad` are not touched.  Returns (loss (B,), grad like x), both detached; with `with_pred` also the prediction of this pass
+    (B,To,V,3), detached and contiguous."""
     from ..runtime import _drop_graph_attributes
     pred, = model(x)
     loss = ops.mpjpe_per_sample(pred, target)
     grad, = torch.autograd.grad(loss, x, grad_outputs=w)
     _drop_graph_attributes(model)      # the interpretation attributes would keep this pass's autograd graph alive
     grad = grad if grad.is_contiguous() else ops._copy(grad)
-    return loss.detach(), grad
+    if not with_pred:
+        return loss.detach(), grad
+    pred = pred.detach()
+    return loss.detach(), grad, pred if pred.is_contiguous() else ops._copy(pred)
 
 
 class _Attack:
@@ -100,6 +104,11 @@ class _Attack:
     def step(self, x_i, x0, grad, loss, state, mask, g):
         ops.attack_step(self.mode, x_i, x0, grad, self.epsilon, iterations=self.iterations, mu=self.mu, mask=mask, g=g, loss=loss,
                         state=state, patience=PATIENCE)
+
+    def iterate(self, model, x_i, x0, target, state, mask, g):
+        """One iteration on the leaf `x_i`: what `_apply` loops over and `runtime.GraphedAttack` captures."""
+        loss, grad = loss_and_input_grad(model, x_i, target, state.w)
+        self.step(x_i.detach(), x0, grad, loss, state, mask, g)
 
     @staticmethod
     def _prepare(x, target):
@@ -140,8 +149,7 @@ class _Attack:
         x_i = x0.clone().requires_grad_(True)      # a leaf the step kernel rewrites in place between two passes
         mask, g = self.mask(x0), self.new_momentum(x0)
         for k in range(self.iterations):
-            loss, grad = loss_and_input_grad(model, x_i, target, state.w)
-            self.step(x_i.detach(), x0, grad, loss, state, mask, g)
+            self.iterate(model, x_i, x0, target, state, mask, g)
             done = k + 1
             if done >= PATIENCE and done < self.iterations and done % self.poll_every == 0 and int(state.n_active.item()) == 0:
                 break
@@ -175,6 +183,44 @@ class MIFGSM(_Attack):
     mode = "mifgsm"
 
 
+class DEEPFOOL(_Attack):
+    """The reference's DeepFool for multi-output regression (:668-776), the one attack of the family that steps in proportion to the
+    gradient: per iteration and sample r = -grad * (mean of the prediction over its frames) / (||grad||_1 + 1e-10), x = x + mask * r
+    (`ops.deepfool_step`).  No epsilon and no projection; queries, the highest loss and the freeze after 5 iterations without a higher
+    loss are IFGSM's.  What is kept and what is dropped of the reference:
+
+    * `overshoot` is accepted and stored; the reference never reads it either.
+    * The `_init_func` call in front of the reference's loop (:739) is not made: in eval mode its prediction is overwritten in
+      iteration 0 and its gradient only doubles that of iteration 0, which the L1 normalisation removes.  `queries` never counted it.
+    * The prediction's joints are broadcast onto the input's (:699), so the model's output must have the input's V: ValueError else.
+    * With `frames=None` the reference resets its mask to all ones and so ignores a joints-only selection (:709-710, as IFGSM does at
+      :481-482).  Here `selection_mask` is used unchanged, as in the other attacks: joints-only restricts the joints.
+    * Deviation: the reference differentiates the mean loss of the samples still optimised, here sample b enters with the fixed
+      weight 1/B (the fixed batch shape above).  r is unchanged by that rescaling except through the 1e-10 beside the L1 norm:
+      relative 1e-9 at the ||grad||_1 of about 0.1 of the recorded model.
+    * A frozen sample does not move, and an all-zero gradient gives r = 0 / 1e-10 = 0, as in the reference."""
+    mode = "deepfool"
+
+    def __init__(self, typ_eval="len_y", *, iterations=10, overshoot=0.02, joints=None, frames=None, db="h36m"):
+        super().__init__(typ_eval, iterations=iterations, joints=joints, frames=frames, db=db)
+        self.overshoot = float(overshoot)
+
+    @staticmethod
+    def _prepare(x, target):
+        x0, target = _Attack._prepare(x, target)
+        if target.shape[2] != x0.shape[2]:
+            raise ValueError("attacks: DEEPFOOL broadcasts the predicted joints onto the input's and needs V_in == V_out, got %d and %d"
+                             % (x0.shape[2], target.shape[2]))
+        return x0, target
+
+    def iterate(self, model, x_i, x0, target, state, mask, g):
+        loss, grad, pred = loss_and_input_grad(model, x_i, target, state.w, with_pred=True)
+        ops.deepfool_step(x_i.detach(), grad, pred, mask=mask, loss=loss, state=state, patience=PATIENCE)
+
+
+DeepFool = DEEPFOOL
+
+
 class NoAttack(_Attack):
     """Returns the input unchanged together with dL/dx of the full-mean loss (:781-805, where the gradient is left on the input)."""
     mode = "none"
@@ -192,7 +238,8 @@ class NoAttack(_Attack):
 
 NOATTACK = NoAttack      # the reference's spelling, as an `adversarial_attacks:` YAML section names it
 
-_BY_NAME = {"FGSM": FGSM, "IFGSM": IFGSM, "MIFGSM": MIFGSM, "NOATTACK": NoAttack, "NoAttack": NoAttack}
+_BY_NAME = {"FGSM": FGSM, "IFGSM": IFGSM, "MIFGSM": MIFGSM, "DEEPFOOL": DEEPFOOL, "DeepFool": DEEPFOOL, "NOATTACK": NoAttack,
+            "NoAttack": NoAttack}
 
 
 def from_config(section):

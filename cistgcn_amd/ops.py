@@ -1652,6 +1652,46 @@ def attack_step(mode, x, x0, grad, epsilon, iterations=1, mu=0.0, mask=None, g=N
     return x
 
 
+def deepfool_step(x, grad, pred, mask=None, loss=None, state=None, patience=5):
+    """One step of the reference's DeepFool on the whole batch in one launch (include/cistgcn_hip.h, cg_deepfool_step): `x` (B,T,V,3)
+    holds the current iterate and is overwritten by x + mask * r with r_b = -grad_b * mean over To of pred_b / (||grad_b||_1 + 1e-10);
+    `grad` is the gradient of the weighted per-sample losses at `x` and `pred` (B,To,V,3) the prediction of the same pass, whose
+    joints are broadcast onto the input's.  `mask` (T,V) of 0/1 restricts the joints and frames that move; `loss` (B,) and `state`
+    (`AttackState`, updated in place) drive the early stop as in `attack_step`, and without them every sample steps.  No autograd,
+    no host synchronisation."""
+    for t, name in ((x, "x"), (grad, "grad")):
+        if t.dtype != torch.float32 or t.dim() != 4 or t.shape != x.shape or t.shape[-1] != 3 or not t.is_contiguous():
+            raise ValueError("deepfool_step: %s must be a contiguous float32 (B,T,V,3) tensor like x, got %s %s" % (name, t.dtype, tuple(t.shape)))
+    B, T, V, _ = x.shape
+    if pred.dtype != torch.float32 or pred.dim() != 4 or pred.shape[0] != B or pred.shape[3] != 3 or not pred.is_contiguous():
+        raise ValueError("deepfool_step: pred must be a contiguous float32 (B,To,V,3) tensor, got %s %s" % (pred.dtype, tuple(pred.shape)))
+    if pred.shape[2] != V:
+        raise ValueError("deepfool_step: the prediction's joints are broadcast onto the input's, so both need the same V: got %d and %d"
+                         % (pred.shape[2], V))
+    if min(B, T, V, pred.shape[1]) < 1:
+        raise ValueError("deepfool_step: empty operand, x %s pred %s" % (tuple(x.shape), tuple(pred.shape)))
+    for t, name in ((grad, "grad"), (pred, "pred"), (mask, "mask"), (loss, "loss")):
+        if t is not None and t.device != x.device:
+            raise ValueError("deepfool_step: x is on %s, %s on %s" % (x.device, name, t.device))
+    a = _lib.DeepfoolStep()
+    a.B, a.T, a.To, a.V, a.patience = B, T, pred.shape[1], V, int(patience)
+    a.x, a.grad, a.pred = _ptr(x), _ptr(grad), _ptr(pred)
+    if mask is not None:
+        if mask.dtype != torch.float32 or tuple(mask.shape) != (T, V) or not mask.is_contiguous():
+            raise ValueError("deepfool_step: mask must be a contiguous float32 (T,V) tensor, got %s %s" % (mask.dtype, tuple(mask.shape)))
+        a.mask = _ptr(mask)
+    if (loss is None) != (state is None):
+        raise ValueError("deepfool_step: loss (B,) and an AttackState go together")
+    if state is not None:
+        if loss.numel() != B or state.B != B or loss.dtype != torch.float32 or not loss.is_contiguous():
+            raise ValueError("deepfool_step: loss must be a contiguous float32 (B,) tensor and the AttackState of the same batch")
+        a.loss, a.best, a.stall, a.active = _ptr(loss), _ptr(state.best), _ptr(state.stall), _ptr(state.active)
+        a.w, a.queries, a.n_active = _ptr(state.w), _ptr(state.queries), _ptr(state.n_active)
+        a.steps, a.frozen_at = _ptr(state.steps), _ptr(state.frozen_at)
+    _lib.call("cg_deepfool_step", ctypes.byref(a), _stream(x))
+    return x
+
+
 # ----------------------------------------------------------------------------------------------
 # fused ST-GCN stage
 # ----------------------------------------------------------------------------------------------

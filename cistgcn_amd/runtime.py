@@ -392,8 +392,9 @@ class GraphedForward:
 
 
 class GraphedAttack:
-    """One iteration of an iterative input attack (`environment.attacks.IFGSM` / `MIFGSM`) as a HIP graph: eval-mode forward,
-    `ops.mpjpe_per_sample`, backward to the input with the device-resident per-sample weights as root gradient, `ops.attack_step`.
+    """One iteration of an iterative input attack (`environment.attacks.IFGSM` / `MIFGSM` / `DEEPFOOL`) as a HIP graph: eval-mode
+    forward, `ops.mpjpe_per_sample`, backward to the input with the device-resident per-sample weights as root gradient,
+    `ops.attack_step` or `ops.deepfool_step`.
     The batch keeps its shape whatever samples are frozen (see environment/attacks.py), the bookkeeping lives in device memory and the
     step kernel writes the weights of the next backward, so `run()` is `iterations` graph launches without a host round trip.
 
@@ -402,11 +403,10 @@ class GraphedAttack:
     captured in eval mode and gets its mode back; replays do not depend on the mode the model is in later."""
 
     def __init__(self, model, x, target, attack, warmup=2):
-        from .environment import attacks
-        if attack.mode not in ("ifgsm", "mifgsm"):
-            raise ValueError("GraphedAttack captures an iterative attack (IFGSM / MIFGSM), got %s" % type(attack).__name__)
+        if attack.mode not in ("ifgsm", "mifgsm", "deepfool"):
+            raise ValueError("GraphedAttack captures an iterative attack (IFGSM / MIFGSM / DEEPFOOL), got %s" % type(attack).__name__)
         self.model, self.attack = model, attack
-        self.x0, self.target = attacks._Attack._prepare(x, target)
+        self.x0, self.target = attack._prepare(x, target)
         self.x0, self.target = self.x0.clone(), self.target.clone()
         self.x_i = self.x0.clone().requires_grad_(True)
         self.state = ops.AttackState(self.x0.shape[0], self.x0.device)
@@ -435,9 +435,7 @@ class GraphedAttack:
         self.reset()
 
     def _iteration(self):
-        from .environment.attacks import loss_and_input_grad
-        loss, grad = loss_and_input_grad(self.model, self.x_i, self.target, self.state.w)
-        self.attack.step(self.x_i.detach(), self.x0, grad, loss, self.state, self.mask, self.g)
+        self.attack.iterate(self.model, self.x_i, self.x0, self.target, self.state, self.mask, self.g)
 
     def reset(self, x=None, target=None):
         """Re-arm for the next batch (same shapes) without re-capturing: new clean input / target if given, the iterate back at the

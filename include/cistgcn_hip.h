@@ -592,6 +592,21 @@ typedef struct CgAttackStep {
 } CgAttackStep;
 int cg_attack_step(const CgAttackStep* a, void* stream);
 long long cg_attack_step_max_floats(void);
+/* One DeepFool step (DEEPFOOL.compute_gradient :697-717 with the bookkeeping of :755-767), one workgroup per sample:
+ *   n1_b = ||grad_b||_1 + 1e-10;  r_b[t,v,c] = -grad_b[t,v,c] * mean_to(pred_b[to,v,c]) / n1_b;  x = x + mask * r
+ * (`-(grad[:, None] * pred[:, :, None]).mean(1) / norm_grad`: the prediction's joints are broadcast onto the input's, so pred has the
+ * V of x).  No epsilon, no reset.  The L1 norm and the To-means are accumulated in f64 in a fixed order, r is rounded to fp32 once;
+ * no floating-point atomics, two calls give the same bits.  An all-zero gradient gives r = 0.  An element that does not move (frozen
+ * sample, mask 0, r = 0) is not written, so a launch that starts with every sample frozen changes nothing but `steps`.
+ * The bookkeeping is that of cg_attack_step on the same buffers; loss and the eight state pointers are given together, or all
+ * NULL for a plain step of every sample.  mask (T,V) of 0/1 or NULL.  No shape limit: the To-means stay in LDS up to 4096 columns
+ * (V*3) and are re-read per element beyond.  NULL x / grad / pred or a partial state: CG_EARG; a non-positive extent: CG_ESHAPE. */
+typedef struct CgDeepfoolStep {
+  int B, T, To, V, patience, pad;
+  float* x; const float* grad; const float* pred; const float* mask; const float* loss;
+  float* best; int* stall; int* active; float* w; int* queries; int* n_active; int* steps; int* frozen_at;
+} CgDeepfoolStep;
+int cg_deepfool_step(const CgDeepfoolStep* a, void* stream);
 
 /* ---- evaluation metrics (csrc/eval_metrics.hip) ------------------------------------------------------
  * What environment/test.py::Metrics.compute (:65-94) reports per batch, except `mae`, in one pass on the device: out[] in the order
