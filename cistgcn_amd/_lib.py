@@ -91,7 +91,8 @@ class DstdTail(ctypes.Structure):
                 ("dr", c_void_p * 2), ("dw", c_void_p * 2), ("red_t", c_void_p * 2), ("dy", c_void_p * 2),
                 ("dgamma_t", c_void_p * 2), ("dbeta_t", c_void_p * 2), ("dalpha_d", c_void_p * 2),
                 ("dgamma_p", c_void_p * 2), ("dbeta_p", c_void_p * 2), ("dalpha_p", c_void_p * 2),
-                ("dgamma_c", c_void_p), ("dbeta_c", c_void_p), ("dalpha_c", c_void_p)]
+                ("dgamma_c", c_void_p), ("dbeta_c", c_void_p), ("dalpha_c", c_void_p),
+                ("rows_c", c_void_p), ("fmom", c_void_p * 2), ("red_q", c_void_p * 2), ("rs_shared", c_int), ("pad2", c_int)]
 
 
 class AdjTail(ctypes.Structure):

@@ -36,4 +36,15 @@ struct CgDstdTail {
   float* dgamma_t[2]; float* dbeta_t[2]; float* dalpha_d[2];
   float* dgamma_p[2]; float* dbeta_p[2]; float* dalpha_p[2];
   float* dgamma_c; float* dbeta_c; float* dalpha_c;
+  double* rows_c;               // optional [B][C][CG_TAIL_ROWSUMS] f64: row sums of K1 from which phase 2 forms red_c without reading a tensor
+                                // (nothing to zero; given to phases 1 AND 2 or to neither)
+  // The tcn BatchNorm's backward sums a phase early (train mode, rows of whole quads; `fmom` and `red_q` together): with q = keep * PReLU_d'(u) * w
+  // the sums of g_t = q * dz and of g_t * yhat are linear in the two means of the prelu BatchNorm backward, so F1 and K3 leave the moments
+  // and backward phase 4 writes dy as well (cg_tail_k45_kernel); phase 5 is replaced by the parameter epilogue, phase 6.
+  double* fmom[2];              // forward phase 1 -> backward phase 4: [CG_STAT_REPLICAS][C][CG_TAIL_FMOM] f64, zero before F1:
+                                // sums of q, q z, q yhat, q z yhat
+  double* red_q[2];             // backward phase 3 -> 4: [CG_STAT_REPLICAS][C][2] f64, zero on entry: sums of q g_p, q g_p (y - mean_t)
+  int rs_shared, pad2;          // r[0] == r[1] (identity residual) and the caller wants ONE gradient: phase 4 writes dr[0] = dr_0 + dr_1, dr[1] untouched
 };
+#define CG_TAIL_ROWSUMS 6
+#define CG_TAIL_FMOM 4

@@ -11,7 +11,8 @@
 //             F4  out = PReLU_c(BN_c(h0)) * gate + block residual, + sums of out for the next block's BatchNorm
 //   backward  K1  dgate[b,c] = sum_{t,v} dout * h                                              (reads dout, h0)
 //             --  SELayer excitation backward (cg_se_gate_bwd) -> dpooled
-//             K2  sums of g_c = (dout * gate + dpooled / P) * PReLU_c'  (and g_c * h0_hat, d alpha_c)
+//             K2  sums of g_c = (dout * gate + dpooled / P) * PReLU_c'  (and g_c * h0_hat, d alpha_c); with `rows_c` they are formed
+//                 from six row sums K1 leaves per (b, c) - they are linear in gate and dpooled - and K2 reads no tensor
 //             K3  dh0 = BN_c'(g_c) per tile; d[a] = Wc^T dh0 and dWc += dh0 a^T on the matrix cores; g_p = d a * PReLU_p'
 //                 -> HBM, + its BatchNorm sums
 //             K4  dz = BN_p'(g_p); dw = sum dz * x; g_d = w * dz * PReLU_d' -> HBM (= gradient of the residual addend),
@@ -26,6 +27,14 @@
 #include <stdlib.h>
 
 HIP_DYNAMIC_SHARED(unsigned char, cg_dyn_lds)
+
+// a per-lane value the compiler must form again where it is used: what is derived from it inside a loop is not hoisted out of the loop and
+// kept in registers (or scratch) across it
+#if defined(__HIP_DEVICE_COMPILE__)
+#define CG_REFORM(x) asm volatile("" : "+v"(x))
+#else
+#define CG_REFORM(x) do { } while (0)
+#endif
 
 // rows of one channel per workgroup, as rowops.hip
 static int cg_tail_rows(long long B, long long C, long long P) {
@@ -55,8 +64,11 @@ __device__ __forceinline__ void cg_tail_keep4(const CgDstdTail& t, int i, unsign
 // ======================================================================================================================
 // F1: channel sums of z_i = w_i * x_i     grid (C, batch chunks, 2)
 // ======================================================================================================================
+// MOM: also the four gradient-free moments the backward's last pass needs to form the tcn BatchNorm's sums without a pass of its own
+// (dstd_tail.h, `fmom`): with q = keep * PReLU_d'(u) * w the sums of q, q z, q yhat, q z yhat - f64 per element like the two sums.
+template <bool MOM>
 __global__ void cg_tail_f1_kernel(CgDstdTail t, int rb) {
-  __shared__ double red[32];
+  __shared__ double red[32 + 16 * CG_TAIL_FMOM];
   const int i = blockIdx.z, c = blockIdx.x, b0 = blockIdx.y * rb;
   if (b0 >= t.B) return;
   const int P = t.T * t.V, nb = min(rb, t.B - b0), C = t.C;
@@ -68,6 +80,7 @@ __global__ void cg_tail_f1_kernel(CgDstdTail t, int rb) {
   const float* __restrict__ y = t.y[i]; const float* __restrict__ r = t.r[i];
   float* const tap = t.tap_x[i];
   double s = 0.0, q = 0.0;
+  double mom[CG_TAIL_FMOM] = {0.0, 0.0, 0.0, 0.0};
   // a wave per row (b, c), four consecutive positions per lane and step: 16-byte loads, one dropout hash per quad (the first form of
   // this kernel walked the elements one by one, a division and a hash each: 3.2 TB/s against 5.2 for K4, which was written this way)
   for (int br = wave; br < nb; br += nw) {
@@ -87,7 +100,12 @@ __global__ void cg_tail_f1_kernel(CgDstdTail t, int rb) {
           xv[j] = cg_tail_x(at, ad, yv[j], rv[j], keep[j], u);
           const double z = (double)(wv * xv[j]);
           s += z; q += z * z;                              // f64 per element, as every BatchNorm sum of this library (a quad summed in f32 first
-        }                                                  // moved a cancelling bias gradient two layers down by 3e-3 of its size)
+                                                           // moved a cancelling bias gradient two layers down by 3e-3 of its size)
+          if (MOM) {
+            const double qd = (double)(keep[j] * (u > 0.f ? 1.f : ad) * wv), yh = (double)((yv[j] - at.mean) * at.rstd), qz = qd * z;
+            mom[0] += qd; mom[1] += qz; mom[2] += qd * yh; mom[3] += qz * yh;
+          }
+        }
         if (tap) *reinterpret_cast<float4*>(tap + base + p) = make_float4(xv[0], xv[1], xv[2], xv[3]);
       }
     } else {
@@ -105,6 +123,15 @@ __global__ void cg_tail_f1_kernel(CgDstdTail t, int rb) {
   if (threadIdx.x == 0) {
     double* rep = t.bn_p[i].stats + (long long)(blockIdx.y % CG_STAT_REPLICAS) * 2 * C;
     atomicAdd(&rep[2 * c], s); atomicAdd(&rep[2 * c + 1], q);
+  }
+  if (MOM) {
+#pragma unroll
+    for (int k = 0; k < CG_TAIL_FMOM; ++k) mom[k] = cg_block_sum(mom[k], red + 32 + 16 * k);
+    if (threadIdx.x == 0) {
+      double* rep = t.fmom[i] + ((long long)(blockIdx.y % CG_STAT_REPLICAS) * C + c) * CG_TAIL_FMOM;
+#pragma unroll
+      for (int k = 0; k < CG_TAIL_FMOM; ++k) atomicAdd(&rep[k], mom[k]);
+    }
   }
 }
 
@@ -202,9 +229,12 @@ __device__ __forceinline__ float cg_tail_pre_p(float z, float mean, float rstd, 
 
 template <int PT>
 __device__ __forceinline__ void cg_tail_act_finish(const CgTailHot& t, const float* sK, unsigned long long seed, int b, int p0, int np,
-                                                   const float4 yq[PT / 8], const float4 rq[PT / 8], const float wq[PT / 8], float* img, int what) {
+                                                   const float4 yq[PT / 8], const float4 rq[PT / 8], const float wq[PT / 8], float* img, int what,
+                                                   unsigned int* qbits = nullptr, bool want_bits = false) {
+  // qbits (PT = 32): per quad slot q and element j, bit 8 q + 2 j = the element was kept by the dropout, bit 8 q + 2 j + 1 = u > 0
   constexpr int PS = PT + 4;
   const int C = t.C, P = t.P;
+  unsigned int bits = 0;
 #pragma unroll
   for (int q = 0; q < PT / 8; ++q) {
     const int i = q / (PT / 16), e = threadIdx.x + (q - i * (PT / 16)) * CG_TAIL_THREADS;       // same slots as cg_tail_act_load
@@ -225,6 +255,7 @@ __device__ __forceinline__ void cg_tail_act_finish(const CgTailHot& t, const flo
         xv[j] = cg_prelu(u, k0.w);
         const float z = wv * xv[j];
         val[j] = what == 0 ? cg_prelu(cg_tail_pre_p(z, k1.x, k1.y, k1.z, k1.w), ap) : (z - k1.x) * k1.y;
+        if (PT == 32 && want_bits) bits |= ((keep[j] > 0.f ? 1u : 0u) | (u > 0.f ? 2u : 0u)) << ((8 * q + 2 * j) & 31);
       }
       if (what == 0) {
         if (t.tap_a[i]) *reinterpret_cast<float4*>(t.tap_a[i] + off) = make_float4(val[0], val[1], val[2], val[3]);
@@ -233,6 +264,7 @@ __device__ __forceinline__ void cg_tail_act_finish(const CgTailHot& t, const flo
     }
     *reinterpret_cast<float4*>(img + c2 * PS + pp) = make_float4(val[0], val[1], val[2], val[3]);
   }
+  if (PT == 32 && qbits) *qbits = bits;
 }
 
 template <int PT>
@@ -514,7 +546,13 @@ __global__ void cg_tail_f4_kernel(CgDstdTail t, int rb) {
 // ======================================================================================================================
 // backward
 // ======================================================================================================================
-// K1: dgate[b,c] = sum_p dout * h
+// K1: dgate[b,c] = sum_p dout * h.
+// ROWS: also the six row sums from which phase 2 forms the sums of g_c = (dout * gate + dpooled / P) * s, s = PReLU_c'(u): they are
+// linear in gate[b,c] and dpooled[b,c], which the SELayer backward delivers only after this kernel, so the part that needs the tensors
+// is summed here while dout and h0 are in registers (hhat = (h0 - mean) * rstd):
+//   0 sum dout s   1 sum s   2 sum dout s hhat   3 sum s hhat   4 sum_{u <= 0} dout u   5 sum_{u <= 0} u
+// Reduced as dgate is: f32 per lane (at most a few quads), f64 across the wave.
+template <bool ROWS>
 __global__ void cg_tail_k1_kernel(CgDstdTail t, int rb) {
   const int c = blockIdx.x, b0 = blockIdx.y * rb, P = t.T * t.V, C = t.C;
   if (b0 >= t.B) return;
@@ -525,18 +563,59 @@ __global__ void cg_tail_k1_kernel(CgDstdTail t, int rb) {
     const int b = b0 + br;
     const long long base = ((long long)b * C + c) * P;
     float s = 0.f;
+    float rs[CG_TAIL_ROWSUMS] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    auto rows = [&](float d, float h0v) {
+      const float u = cg_bn(ac, h0v), hh = (h0v - ac.mean) * ac.rstd;
+      const bool pos = u > 0.f;
+      const float sl = pos ? 1.f : alpha, ds = d * sl;
+      rs[0] += ds; rs[1] += sl; rs[2] += ds * hh; rs[3] += sl * hh;
+      rs[4] += pos ? 0.f : d * u; rs[5] += pos ? 0.f : u;
+    };
     if ((P & 3) == 0) {
       for (int p = 4 * lane; p < P; p += 256) {
         const float4 d4 = *reinterpret_cast<const float4*>(t.dout + base + p), h4 = *reinterpret_cast<const float4*>(t.h0 + base + p);
         s += (d4.x * cg_prelu(cg_bn(ac, h4.x), alpha) + d4.y * cg_prelu(cg_bn(ac, h4.y), alpha)) +
              (d4.z * cg_prelu(cg_bn(ac, h4.z), alpha) + d4.w * cg_prelu(cg_bn(ac, h4.w), alpha));
+        if (ROWS) { rows(d4.x, h4.x); rows(d4.y, h4.y); rows(d4.z, h4.z); rows(d4.w, h4.w); }
       }
     } else {
-      for (int p = lane; p < P; p += 64) s += t.dout[base + p] * cg_prelu(cg_bn(ac, t.h0[base + p]), alpha);
+      for (int p = lane; p < P; p += 64) {
+        s += t.dout[base + p] * cg_prelu(cg_bn(ac, t.h0[base + p]), alpha);
+        if (ROWS) rows(t.dout[base + p], t.h0[base + p]);
+      }
     }
     const double sd = cg_wave_sum((double)s);
     if (lane == 0) t.dgate[(long long)b * C + c] = (float)sd;
+    if (ROWS) {
+      double* dst = t.rows_c + ((long long)b * C + c) * CG_TAIL_ROWSUMS;
+#pragma unroll
+      for (int k = 0; k < CG_TAIL_ROWSUMS; ++k) {
+        const double v = cg_wave_sum((double)rs[k]);
+        if (lane == 0) dst[k] = v;
+      }
+    }
   }
+}
+
+// Phase 2 from the row sums of K1: red_c[2c] = sum_b gate R0 + dpooled / P R1, red_c[2c + 1] = sum_b gate R2 + dpooled / P R3, slope sum
+// = sum_b gate R4 + dpooled / P R5.  One workgroup per channel, f64, a fixed order (thread = samples tid, tid + 256, ..; shuffle tree; the
+// waves in turn) and plain stores: the same bits from run to run, nothing to zero.  The slope total of a channel goes to word c of the
+// CG_ALPHA_SLOTS spread words (channels c, c + 64 .. cannot occur: C <= 64), the words no channel owns are set to zero.
+__global__ void cg_tail_k2_rows_kernel(CgDstdTail t) {
+  __shared__ double red[48];
+  const int c = blockIdx.x, C = t.C;
+  const double invP = 1.0 / (double)(t.T * t.V);
+  double s1 = 0.0, s2 = 0.0, sa = 0.0;
+  for (int b = threadIdx.x; b < t.B; b += blockDim.x) {
+    const long long bc = (long long)b * C + c;
+    const double* r = t.rows_c + bc * CG_TAIL_ROWSUMS;
+    const double gate = (double)t.gate[bc], dp = (double)t.dpooled[bc] * invP;
+    s1 += gate * r[0] + dp * r[1]; s2 += gate * r[2] + dp * r[3]; sa += gate * r[4] + dp * r[5];
+  }
+  s1 = cg_block_sum(s1, red); s2 = cg_block_sum(s2, red + 16); sa = cg_block_sum(sa, red + 32);
+  if (threadIdx.x == 0) { t.red_c[2 * c] = s1; t.red_c[2 * c + 1] = s2; t.red_c[2 * C + c] = sa; }
+  if (c == 0)
+    for (int k = C + threadIdx.x; k < CG_ALPHA_SLOTS; k += blockDim.x) t.red_c[2 * C + k] = 0.0;
 }
 
 // gradient in front of the compressor's PReLU for one element: g_c = (dout * gate + dpooled / P) * PReLU_c'(u); returns g_c, u
@@ -650,15 +729,33 @@ __global__ __launch_bounds__(CG_TAIL_THREADS, 2) void cg_tail_k3_kernel(CgDstdTa
   // Loads of a tile travel while something else runs: y / r / h0 / dout / gate / dpooled of tile k+1 are issued in front of the
   // matrix phases of tile k (registers yq / rq / h4 / d4 / gt / dp)
   const bool vec = (P & 3) == 0;
+  // The q sums (dstd_tail.h, `red_q`): sums of q g_p and q g_p (y - mean_t), q = keep * PReLU_d'(u) * w.  The lanes that STAGE a quad of the
+  // tile hold its y, its gate and - two bits per element - its keep factor and PReLU_d branch; g_p of the same elements comes out of the
+  // epilogue in other lanes.  The epilogue therefore leaves g_p in the zhat image, in place (a lane overwrites the quad it has just read,
+  // and the d W products of a wave read the channel tiles of its own epilogue), and after a barrier the staging lanes add up.  No LDS
+  // beyond the images there are, no second read of y / r (a 16-byte load per quad in the epilogue lanes, issued in front of the matrix
+  // phases or not: + 40 .. 60 us on 200 at B = 256, C = 64, P = 1100 - more than K5 gives back).
+  const bool qsum = train && vec && t.red_q[0] != nullptr;
+  const float qkeep = (hot.train && hot.drop_p > 0.f) ? 1.0f / (1.0f - hot.drop_p) : 1.f;      // cg_drop_pick's factor of a kept element
+  const float alpha_d0 = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, t.alpha_d[0][0])));
+  const float alpha_d1 = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, t.alpha_d[1][0])));
+  float4 yk[CG_TAIL_PT3 / 8];                        // y of the quads this thread staged, kept past the next tile's prefetch
+  float wk[CG_TAIL_PT3 / 8];
+  unsigned int qbits = 0;                            // quad slot s, element j: bit 8 s + 2 j = kept, bit 8 s + 2 j + 1 = u > 0
+  float qacc[CG_TAIL_PT3 / 8][2];
+#pragma unroll
+  for (int i = 0; i < CG_TAIL_PT3 / 8; ++i) qacc[i][0] = qacc[i][1] = 0.f;
   constexpr int DQ = CG_TAIL_PT3 / 16;               // quads of the dh0 image per thread (C <= 64)
   float4 yq[CG_TAIL_PT3 / 8], rq[CG_TAIL_PT3 / 8];
   float wq[CG_TAIL_PT3 / 8];
   float4 h4[DQ], d4[DQ];
   float gt[DQ], dp[DQ];
   auto dh_load = [&](int b, int p0, int np) {            // h0 / dout quads and the per-row gate terms of a tile's dh0 image
+    int tidr = tid;
+    CG_REFORM(tidr);
 #pragma unroll
     for (int q = 0; q < DQ; ++q) {
-      const int e = tid + q * CG_TAIL_THREADS, c = e / (CG_TAIL_PT3 / 4), pp = 4 * (e - c * (CG_TAIL_PT3 / 4));
+      const int e = tidr + q * CG_TAIL_THREADS, c = e / (CG_TAIL_PT3 / 4), pp = 4 * (e - c * (CG_TAIL_PT3 / 4));
       h4[q] = make_float4(0.f, 0.f, 0.f, 0.f); d4[q] = h4[q]; gt[q] = 0.f; dp[q] = 0.f;
       if (c < C && pp < np) {
         const long long off = ((long long)b * C + c) * P + p0 + pp;
@@ -679,7 +776,13 @@ __global__ __launch_bounds__(CG_TAIL_THREADS, 2) void cg_tail_k3_kernel(CgDstdTa
     __syncthreads();
     CG_TSTAMP();
     if (vec) {
-      cg_tail_act_finish<CG_TAIL_PT3>(hot, sK, seed, b, p0, np, yq, rq, wq, sZ, 1);
+      unsigned int nbits = 0;                              // a local of its own: `qbits` itself stays in a register
+      cg_tail_act_finish<CG_TAIL_PT3>(hot, sK, seed, b, p0, np, yq, rq, wq, sZ, 1, &nbits, qsum);
+      if (qsum) {
+        qbits = nbits;
+#pragma unroll
+        for (int q = 0; q < CG_TAIL_PT3 / 8; ++q) { yk[q] = yq[q]; wk[q] = wq[q]; }
+      }
       CG_TSTAMP();
       // dh0 = gamma_c * rstd * (g_c - mean(g_c) - h0hat * mean(g_c h0hat)); per-channel constants from sKc
 #pragma unroll
@@ -789,6 +892,7 @@ __global__ __launch_bounds__(CG_TAIL_THREADS, 2) void cg_tail_k3_kernel(CgDstdTa
     // zhat comes as one 16-byte LDS read, g_p leaves as one 16-byte store, the channel constants are per lane, and the sums of a
     // channel are three registers per task over all tiles of the workgroup (a wave owns the same c2 tiles in every tile)
     static_assert(CG_TAIL_PT3 == 32, "one pair of position tiles per task: task w = channel tile w");
+    if (!MT_ && qsum) __syncthreads();                   // run-time widths: the d W tasks of a wave read zhat of any channel tile - all done before the epilogue overwrites it
     cg_f32x4 dacc[CG_TAIL_K3_TASKS][2];
     if (MT_) {
       // known widths: the tasks of a wave (channel tiles wave, wave + 4) share the dh0 fragments and advance through k together
@@ -835,7 +939,9 @@ __global__ __launch_bounds__(CG_TAIL_THREADS, 2) void cg_tail_k3_kernel(CgDstdTa
           }
         }
       }
-      const int c2 = 16 * mt + l15;
+      int l15e = l15, slote = slot;                       // formed again per tile: the row addresses below are not carried across the tile loop
+      CG_REFORM(l15e); CG_REFORM(slote);
+      const int c2 = 16 * mt + l15e;
       const bool cok = c2 < C2;
       const int i = c2 >= C ? 1 : 0, c = cok ? c2 - i * C : 0;
       const float gam = cok ? sK[8 * c2 + 6] : 0.f, bet = cok ? sK[8 * c2 + 7] : 0.f, alp = cok ? (i ? alpha_p1 : alpha_p0) : 0.f;
@@ -843,7 +949,7 @@ __global__ __launch_bounds__(CG_TAIL_THREADS, 2) void cg_tail_k3_kernel(CgDstdTa
                                                                                  // vector load from the argument block, and waiting for it waits for the whole prefetch
 #pragma unroll
       for (int h = 0; h < 2; ++h) {
-        const int pq = (h ? n1 : n0) + 4 * slot;
+        const int pq = (h ? n1 : n0) + 4 * slote;
         const cg_f32x4 cc = h ? c1 : c0;
         if (cok && pq < np) {
           const float4 z4 = *reinterpret_cast<const float4*>(sZ + c2 * CG_TAIL_PS3 + pq);
@@ -859,10 +965,33 @@ __global__ __launch_bounds__(CG_TAIL_THREADS, 2) void cg_tail_k3_kernel(CgDstdTa
               if (!(v > 0.f)) racc[ti][2] += da * v;
             }
           }
+          if (qsum) *reinterpret_cast<float4*>(sZ + c2 * CG_TAIL_PS3 + pq) = make_float4(gq[0], gq[1], gq[2], gq[3]);      // for the staging lanes, below
           if (vec) *reinterpret_cast<float4*>(gpr + pq) = make_float4(gq[0], gq[1], gq[2], gq[3]);      // np % 4 == 0: the quad is inside the row
           else {
 #pragma unroll
             for (int q = 0; q < 4; ++q) if (pq + q < np) gpr[pq + q] = gq[q];
+          }
+        }
+      }
+    }
+    if (qsum) {
+      __syncthreads();                                   // g_p of the tile stands in sZ
+#pragma unroll
+      for (int q = 0; q < CG_TAIL_PT3 / 8; ++q) {
+        constexpr int QH = CG_TAIL_PT3 / 16;
+        const int i = q / QH, e = tid + (q - i * QH) * CG_TAIL_THREADS;       // the slots of cg_tail_act_load
+        const int c = e / (CG_TAIL_PT3 / 4), pp = 4 * (e - c * (CG_TAIL_PT3 / 4)), c2 = i * C + c;
+        if (c < C && pp < np) {
+          const float4 g4 = *reinterpret_cast<const float4*>(sZ + c2 * CG_TAIL_PS3 + pp);
+          const float mt = sK[8 * c2];
+          const float fa = qkeep * wk[q], fb = fa * (i ? alpha_d1 : alpha_d0);
+          const float gv[4] = {g4.x, g4.y, g4.z, g4.w}, yv[4] = {yk[q].x, yk[q].y, yk[q].z, yk[q].w};
+#pragma unroll
+          for (int j = 0; j < 4; ++j) {
+            const unsigned int bj = qbits >> (8 * q + 2 * j);
+            const float f = (bj & 1u) ? ((bj & 2u) ? fa : fb) : 0.f;
+            const float fg = f * gv[j];
+            qacc[q][0] += fg; qacc[q][1] += fg * (yv[j] - mt);
           }
         }
       }
@@ -880,6 +1009,23 @@ __global__ __launch_bounds__(CG_TAIL_THREADS, 2) void cg_tail_k3_kernel(CgDstdTa
     s1 += __shfl_xor(s1, 32, 64); s2 += __shfl_xor(s2, 32, 64); sa += __shfl_xor(sa, 32, 64);
     if (slot == 0 && c2 < C2) {
       atomicAdd(&sRed[2 * c2], (double)s1); atomicAdd(&sRed[2 * c2 + 1], (double)s2); atomicAdd(&sRed[2 * C2M + (c2 >= C ? 1 : 0)], (double)sa);
+    }
+  }
+  if (qsum) {
+    // a row of the tile (one channel) is staged by PT3 / 4 = 8 consecutive lanes: three exchanges, then one atomic pair per channel and wave
+#pragma unroll
+    for (int q = 0; q < CG_TAIL_PT3 / 8; ++q) {
+      constexpr int QH = CG_TAIL_PT3 / 16;
+      const int i = q / QH, c = (tid + (q - i * QH) * CG_TAIL_THREADS) / (CG_TAIL_PT3 / 4);
+      float q1 = qacc[q][0], q2 = qacc[q][1];
+      q1 += __shfl_xor(q1, 1, 64); q2 += __shfl_xor(q2, 1, 64);
+      q1 += __shfl_xor(q1, 2, 64); q2 += __shfl_xor(q2, 2, 64);
+      q1 += __shfl_xor(q1, 4, 64); q2 += __shfl_xor(q2, 4, 64);
+      if ((tid & 7) == 0 && c < C) {
+        // replicated as the forward's statistics are: 512 workgroups on the few cache lines of one [C][2] table cost K3 25 us at C = 10
+        double* rq2 = (i ? t.red_q[1] : t.red_q[0]) + ((long long)(blockIdx.x % CG_STAT_REPLICAS) * C + c) * 2;
+        atomicAdd(&rq2[0], (double)q1); atomicAdd(&rq2[1], (double)q2);
+      }
     }
   }
   __syncthreads();
@@ -1030,6 +1176,124 @@ __global__ void cg_tail_k5_kernel(CgDstdTail t, int rb) {
   }
 }
 
+// K4 and K5 as one last pass (rows of whole quads; `red_q`, in train mode with `fmom`).  The tcn BatchNorm backward needs the channel sums of
+// g_t = q dz and of g_t yhat, q = keep * PReLU_d'(u) * w, before the first dy can be written - and dz = scale_p (g_p - m1 - zhat m2) is linear in
+// the two means m1, m2 that K3 finished:
+//   sum g_t      = scale_p (A1 - m1 A2 - m2 A3)      A1 = sum q g_p       A2 = sum q        A3 = sum q zhat      = rstd_p (Mz  - mean_p M1)
+//   sum g_t yhat = scale_p (B1 - m1 B2 - m2 B3)      B1 = sum q g_p yhat  B2 = sum q yhat   B3 = sum q zhat yhat = rstd_p (Mzy - mean_p My)
+// A1, B1 from K3's epilogue (red_q), M1, Mz, My, Mzy from F1 (fmom).  Every workgroup forms the two sums of its channel in f64 from the ROUNDED
+// m1, m2 its elements use, then walks its rows once: dz, dw, g_d, the slope terms, dy and the residual gradient.
+// SHARED (identity residual, r[0] == r[1]): a wave owns row (b, c) of BOTH branches, reads r once and writes dr[0] = g_d0 + g_d1.
+template <bool SHARED>
+__global__ void cg_tail_k45_kernel(CgDstdTail t, int rb) {
+  constexpr int ND = SHARED ? 2 : 1;
+  const int i0 = SHARED ? 0 : blockIdx.z, c = blockIdx.x, b0 = blockIdx.y * rb, P = t.T * t.V, C = t.C;
+  if (b0 >= t.B) return;
+  const int nb = min(rb, t.B - b0), lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), nw = blockDim.x >> 6;
+  const double cnt = (double)t.B * P;
+  const bool train = t.train != 0;
+  const unsigned long long seed = (t.train && t.drop_p > 0.f) ? *t.seed : 0ull;
+  CgAff at[ND], ap[ND];
+  float ad[ND], scale_p[ND], m1[ND], m2[ND], scale_t[ND], mt1[ND], rmt2[ND];
+  const float* __restrict__ yp[ND]; const float* __restrict__ gpp[ND]; float* __restrict__ dyp[ND];
+#pragma unroll
+  for (int d = 0; d < ND; ++d) {
+    const int i = i0 + d;
+    at[d] = cg_tail_aff(t.bn_t[i], c, C, 0.0, t.train, true, false);
+    ap[d] = cg_tail_aff(t.bn_p[i], c, C, 0.0, t.train, true, false);
+    ad[d] = t.alpha_d[i][0]; scale_p[d] = ap[d].gamma * ap[d].rstd; scale_t[d] = at[d].gamma * at[d].rstd;
+    m1[d] = m2[d] = mt1[d] = rmt2[d] = 0.f;
+    yp[d] = t.y[i]; gpp[d] = t.gp[i]; dyp[d] = t.dy[i];
+    if (train) {
+      m1[d] = (float)(t.red_p[i][2 * c] / cnt); m2[d] = (float)(t.red_p[i][2 * c + 1] / cnt);
+      double M[CG_TAIL_FMOM] = {0.0, 0.0, 0.0, 0.0};
+      for (int r = 0; r < CG_STAT_REPLICAS; ++r)
+#pragma unroll
+        for (int k = 0; k < CG_TAIL_FMOM; ++k) M[k] += t.fmom[i][((long long)r * C + c) * CG_TAIL_FMOM + k];
+      double A1 = 0.0, B1 = 0.0;
+      for (int r = 0; r < CG_STAT_REPLICAS; ++r) { A1 += t.red_q[i][((long long)r * C + c) * 2]; B1 += t.red_q[i][((long long)r * C + c) * 2 + 1]; }
+      B1 *= (double)at[d].rstd;
+      const double mp = (double)ap[d].mean, rp = (double)ap[d].rstd;
+      const double A3 = rp * (M[1] - mp * M[0]), B3 = rp * (M[3] - mp * M[2]);
+      const double St = (double)scale_p[d] * (A1 - (double)m1[d] * M[0] - (double)m2[d] * A3);
+      const double Sty = (double)scale_p[d] * (B1 - (double)m1[d] * M[2] - (double)m2[d] * B3);
+      mt1[d] = (float)(St / cnt); rmt2[d] = at[d].rstd * (float)(Sty / cnt);
+      if (blockIdx.y == 0 && threadIdx.x == 0) { t.red_t[i][2 * c] = St; t.red_t[i][2 * c + 1] = Sty; }      // where d beta_t / d gamma_t are read from
+    }
+  }
+  const float* __restrict__ r0p = t.r[i0]; float* __restrict__ dr0p = t.dr[i0];
+  double sa[ND], s1[ND], s2[ND];                         // s1, s2: eval mode only (dy needs no sums there; d beta_t / d gamma_t do), as K4 forms them
+#pragma unroll
+  for (int d = 0; d < ND; ++d) sa[d] = s1[d] = s2[d] = 0.0;
+  for (int br = wave; br < nb; br += nw) {
+    const int b = b0 + br;
+    const long long base = ((long long)b * C + c) * P;
+    float wv[ND], sw[ND];
+#pragma unroll
+    for (int d = 0; d < ND; ++d) { wv[d] = t.w[i0 + d][(long long)b * C + c]; sw[d] = 0.f; }
+    for (int p = 4 * lane; p < P; p += 256) {
+      const float4 r4 = *reinterpret_cast<const float4*>(r0p + base + p);
+      const float rv[4] = {r4.x, r4.y, r4.z, r4.w};
+      float gsum[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int d = 0; d < ND; ++d) {
+        float keep[4];
+        cg_tail_keep4(t, i0 + d, seed, (unsigned long long)(base + p), keep);
+        const float4 y4 = *reinterpret_cast<const float4*>(yp[d] + base + p), g4 = *reinterpret_cast<const float4*>(gpp[d] + base + p);
+        const float yv[4] = {y4.x, y4.y, y4.z, y4.w}, gv[4] = {g4.x, g4.y, g4.z, g4.w};
+        float o[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          float u;
+          const float x = cg_tail_x(at[d], ad[d], yv[j], rv[j], keep[j], u);
+          const float z = wv[d] * x;
+          const float dz = train ? scale_p[d] * (gv[j] - m1[d] - (z - ap[d].mean) * ap[d].rstd * m2[d]) : gv[j] * scale_p[d];
+          sw[d] += dz * x;
+          const float dx = wv[d] * dz;
+          const float gd = u > 0.f ? dx : ad[d] * dx;
+          if (!(u > 0.f)) sa[d] += (double)dx * (double)u;
+          gsum[j] = SHARED ? gsum[j] + gd : gd;
+          o[j] = train ? scale_t[d] * (gd * keep[j] - mt1[d] - (yv[j] - at[d].mean) * rmt2[d]) : gd * keep[j] * scale_t[d];
+          if (!train) { const float gt = gd * keep[j]; s1[d] += (double)gt; s2[d] += (double)gt * (double)((yv[j] - at[d].mean) * at[d].rstd); }
+        }
+        *reinterpret_cast<float4*>(dyp[d] + base + p) = make_float4(o[0], o[1], o[2], o[3]);
+      }
+      *reinterpret_cast<float4*>(dr0p + base + p) = make_float4(gsum[0], gsum[1], gsum[2], gsum[3]);
+    }
+#pragma unroll
+    for (int d = 0; d < ND; ++d) {
+      const double swd = cg_wave_sum((double)sw[d]);
+      if (lane == 0) t.dw[i0 + d][(long long)b * C + c] = (float)swd;
+    }
+  }
+#pragma unroll
+  for (int d = 0; d < ND; ++d) {
+    const double s = cg_wave_sum(sa[d]);
+    if (lane == 0) atomicAdd(&t.red_t[i0 + d][2 * C + ((c + 5 * (int)blockIdx.y + 17 * wave) & (CG_ALPHA_SLOTS - 1))], s);
+    if (!train) {
+      const double e1 = cg_wave_sum(s1[d]), e2 = cg_wave_sum(s2[d]);
+      if (lane == 0) { atomicAdd(&t.red_t[i0 + d][2 * c], e1); atomicAdd(&t.red_t[i0 + d][2 * c + 1], e2); }
+    }
+  }
+}
+
+// the per-channel parameter gradients of all three BatchNorm levels and the PReLU slopes from the finished sums (what K5 writes on its way):
+// phase 6, one workgroup, behind the last pass - its slope sums are complete only when it ends
+__global__ void cg_tail_params_kernel(CgDstdTail t) {
+  const int C = t.C;
+  for (int e = threadIdx.x; e < 2 * C; e += blockDim.x) {
+    const int i = e / C, c = e - i * C;
+    t.dgamma_t[i][c] = (float)t.red_t[i][2 * c + 1]; t.dbeta_t[i][c] = (float)t.red_t[i][2 * c];
+    t.dgamma_p[i][c] = (float)t.red_p[i][2 * c + 1]; t.dbeta_p[i][c] = (float)t.red_p[i][2 * c];
+    if (i == 0) { t.dgamma_c[c] = (float)t.red_c[2 * c + 1]; t.dbeta_c[c] = (float)t.red_c[2 * c]; }
+  }
+  if (threadIdx.x < 2) {
+    const int i = threadIdx.x;
+    t.dalpha_d[i][0] = (float)cg_alpha_sum(t.red_t[i] + 2 * C); t.dalpha_p[i][0] = (float)cg_alpha_sum(t.red_p[i] + 2 * C);
+  }
+  if (threadIdx.x == 64) t.dalpha_c[0] = (float)cg_alpha_sum(t.red_c + 2 * C);
+}
+
 __global__ void cg_tail_fold_kernel(const float* __restrict__ ws, int replicas, int n, float* __restrict__ dW) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
@@ -1088,7 +1352,7 @@ extern "C" int cg_dstd_tail_geometry(int B, int C, int T, int V, int* out) {
   return CG_OK;
 }
 
-// include/cistgcn_hip.h : cg_dstd_tail_fwd (phases 1..4) / cg_dstd_tail_bwd (phases 1..5)
+// include/cistgcn_hip.h : cg_dstd_tail_fwd (phases 1..4) / cg_dstd_tail_bwd (phases 1..5, or 1..4 and 6 with `red_q`)
 extern "C" int cg_dstd_tail_fwd(const CgDstdTail* t, int phase, void* stream_) {
   int st = cg_tail_check(t);
   if (st != CG_OK) return st;
@@ -1099,7 +1363,9 @@ extern "C" int cg_dstd_tail_fwd(const CgDstdTail* t, int phase, void* stream_) {
   if (phase == 1) {
     if (!t->train) return CG_OK;                      // eval: running statistics, nothing to reduce
     if (!t->bn_t[0].stats || !t->bn_t[1].stats || !t->bn_p[0].stats || !t->bn_p[1].stats) return CG_EARG;
-    hipLaunchKernelGGL(cg_tail_f1_kernel, dim3(rows.x, rows.y, 2), dim3(256), 0, stream, *t, rb);
+    if ((t->fmom[0] != nullptr) != (t->fmom[1] != nullptr)) return CG_EARG;
+    if (t->fmom[0] && (P & 3) == 0) hipLaunchKernelGGL(cg_tail_f1_kernel<true>, dim3(rows.x, rows.y, 2), dim3(256), 0, stream, *t, rb);
+    else hipLaunchKernelGGL(cg_tail_f1_kernel<false>, dim3(rows.x, rows.y, 2), dim3(256), 0, stream, *t, rb);
   } else if (phase == 2) {
     if (t->train && (!t->bn_p[0].stats || !t->bn_p[1].stats || !t->bn_c.stats)) return CG_EARG;
     const CgTailRanges rg = cg_tail_ranges(t->B, P, CG_TAIL_PT);
@@ -1128,20 +1394,28 @@ extern "C" int cg_dstd_tail_fwd(const CgDstdTail* t, int phase, void* stream_) {
   return cg_launch_status();
 }
 
+// backward phase 4 writes dy as well (cg_tail_k45_kernel): the caller gave `red_q` and the rows are whole quads
+static bool cg_tail_last_pass(const CgDstdTail* t) { return t->red_q[0] && t->red_q[1] && ((t->T * t->V) & 3) == 0; }
+
 extern "C" int cg_dstd_tail_bwd(const CgDstdTail* t, int phase, void* stream_) {
   int st = cg_tail_check(t);
   if (st != CG_OK) return st;
   if (!t->dout || !t->gate) return CG_EARG;
+  if ((t->red_q[0] != nullptr) != (t->red_q[1] != nullptr)) return CG_EARG;
+  if (t->rs_shared && (t->r[0] != t->r[1] || !cg_tail_last_pass(t))) return CG_EARG;
   hipStream_t stream = (hipStream_t)stream_;
   const int P = t->T * t->V, C = t->C;
   const int rb = cg_tail_rows(t->B, C, P);
   const dim3 rows = cg_tail_row_grid(t->B, C, rb);
   if (phase == 1) {
     if (!t->dgate) return CG_EARG;
-    hipLaunchKernelGGL(cg_tail_k1_kernel, rows, dim3(256), 0, stream, *t, rb);
+    if (t->rows_c) hipLaunchKernelGGL(cg_tail_k1_kernel<true>, rows, dim3(256), 0, stream, *t, rb);
+    else hipLaunchKernelGGL(cg_tail_k1_kernel<false>, rows, dim3(256), 0, stream, *t, rb);
   } else if (phase == 2) {
     if (!t->dpooled || !t->red_c) return CG_EARG;
-    hipLaunchKernelGGL(cg_tail_k2_kernel, rows, dim3(256), 0, stream, *t, rb);
+    static_assert(CG_ALPHA_SLOTS >= 64, "cg_tail_k2_rows_kernel: one slope word per channel, C <= 64");
+    if (t->rows_c) hipLaunchKernelGGL(cg_tail_k2_rows_kernel, dim3((unsigned)C), dim3(256), 0, stream, *t);      // no tensor pass: the row sums of phase 1
+    else hipLaunchKernelGGL(cg_tail_k2_kernel, rows, dim3(256), 0, stream, *t, rb);
   } else if (phase == 3) {
     if (!t->dpooled || !t->red_c || !t->gp[0] || !t->gp[1] || !t->red_p[0] || !t->red_p[1] || !t->dWc_ws || !t->dWc) return CG_EARG;
     const CgTailRanges rg = cg_tail_ranges(t->B, P, CG_TAIL_PT3);
@@ -1165,9 +1439,26 @@ extern "C" int cg_dstd_tail_bwd(const CgDstdTail* t, int phase, void* stream_) {
     const int n = C * 2 * C;
     hipLaunchKernelGGL(cg_tail_fold_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, t->dWc_ws, CG_TAIL_REPLICAS, n, t->dWc);
   } else if (phase == 4) {
-    if (!t->gp[0] || !t->gp[1] || !t->dr[0] || !t->dr[1] || !t->dw[0] || !t->dw[1] || !t->red_t[0] || !t->red_t[1] || !t->red_p[0]) return CG_EARG;
-    hipLaunchKernelGGL(cg_tail_k4_kernel, dim3(rows.x, rows.y, 2), dim3(256), 0, stream, *t, rb);
+    if (!t->gp[0] || !t->gp[1] || !t->dr[0] || !t->dw[0] || !t->dw[1] || !t->red_t[0] || !t->red_t[1] || !t->red_p[0] || !t->red_p[1]) return CG_EARG;
+    if (cg_tail_last_pass(t)) {            // K4 and K5 in one pass; the parameter epilogue is phase 6, phase 5 is not called
+      if (!t->dy[0] || !t->dy[1]) return CG_EARG;
+      if (t->train && (!t->fmom[0] || !t->fmom[1])) return CG_EARG;
+      if (t->rs_shared) hipLaunchKernelGGL(cg_tail_k45_kernel<true>, dim3(rows.x, rows.y, 1), dim3(256), 0, stream, *t, rb);
+      else {
+        if (!t->dr[1]) return CG_EARG;
+        hipLaunchKernelGGL(cg_tail_k45_kernel<false>, dim3(rows.x, rows.y, 2), dim3(256), 0, stream, *t, rb);
+      }
+    } else {
+      if (!t->dr[1]) return CG_EARG;
+      hipLaunchKernelGGL(cg_tail_k4_kernel, dim3(rows.x, rows.y, 2), dim3(256), 0, stream, *t, rb);
+    }
+  } else if (phase == 6) {
+    if (!t->red_c || !t->red_t[0] || !t->red_t[1] || !t->red_p[0] || !t->red_p[1] || !t->dgamma_t[0] || !t->dgamma_t[1] || !t->dbeta_t[0] || !t->dbeta_t[1] ||
+        !t->dgamma_p[0] || !t->dgamma_p[1] || !t->dbeta_p[0] || !t->dbeta_p[1] || !t->dalpha_d[0] || !t->dalpha_d[1] || !t->dalpha_p[0] || !t->dalpha_p[1] ||
+        !t->dgamma_c || !t->dbeta_c || !t->dalpha_c) return CG_EARG;
+    hipLaunchKernelGGL(cg_tail_params_kernel, dim3(1), dim3(128), 0, stream, *t);
   } else if (phase == 5) {
+    if (cg_tail_last_pass(t)) return CG_EARG;
     if (!t->dy[0] || !t->dy[1] || !t->dr[0] || !t->dr[1] || !t->red_t[0] || !t->red_t[1] || !t->dgamma_t[0] || !t->dgamma_p[0] || !t->dgamma_c) return CG_EARG;
     hipLaunchKernelGGL(cg_tail_k5_kernel, dim3(rows.x, rows.y, 2), dim3(256), 0, stream, *t, rb);
   } else return CG_EARG;

@@ -235,6 +235,7 @@ class CISTGCN(nn.Module):
         self.fused_maps = True       # the first-level maps of a block (towers, gates, residual maps) and of the context heads stacked
         self.fused_defer = True      # BatchNorm + PReLU of the first tower level applied by the collapsing kernels on load
         self.fused_mid = True        # the gates' and towers' BatchNorm -> Dropout -> map between the collapsing kernels and the fused tails (ops.block_mid)
+        self.fused_tail_sums = True  # the fused tail's backward forms the compressor BatchNorm's sums from row sums of its first phase (no pass of its own)
         self.stack_min_elements = 1 << 21      # block inputs smaller than this keep one contraction per first-level map
         # The reference edits the config lists in place (CISTGCN.py:514-517,548); copies are used here
         # so that one `opt` can build several models.
@@ -734,10 +735,12 @@ class CISTGCN(nn.Module):
             if self.drop_trace is not None:
                 self.drop_trace[doms[0].tcn[1]], self.drop_trace[doms[1].tcn[1]] = self._site - 1, self._site
             taps = [] if self.act_trace is not None else None
+            rs_shared = self.fused_tail_sums and not has_res and res[0].data_ptr() == res[1].data_ptr()      # identity residuals: one summed gradient
             out, ost = ops.dstd_tail([y[0] for y in ys], [y[1] for y in ys], res, (m.w1, m.w2),
                                      (doms[0].tcn[1], doms[1].tcn[1], m.prelu1[0], m.prelu2[0], c[1]),
                                      (doms[0].prelu, doms[1].prelu, m.prelu1[1], m.prelu2[1], c[2]), c[0].weight, c[3], bres, tr,
-                                     drop_p=self.dropout, salts=(self._site - 1, self._site), emit_stats=tr, taps=taps)
+                                     drop_p=self.dropout, salts=(self._site - 1, self._site), emit_stats=tr, taps=taps,
+                                     tail_sums=self.fused_tail_sums, rs_shared=rs_shared)
             if taps is not None:
                 for mod, tap in zip((doms[0].prelu, doms[1].prelu, m.prelu1[1], m.prelu2[1], c[2]), taps):
                     self.act_trace[mod] = (tap, None)

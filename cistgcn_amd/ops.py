@@ -1796,6 +1796,14 @@ class _DstdTail(torch.autograd.Function):
                 taps.append(torch.empty(B, C, T, V, dtype=f32, device=dev))
             t.tap_x[0], t.tap_x[1], t.tap_a[0], t.tap_a[1], t.tap_h = (v.data_ptr() for v in taps[-5:])
         stream = _stream(y1)
+        # the backward's last pass forms the tcn BatchNorm's sums from moments F1 leaves here (rows of whole quads; eval mode needs none)
+        last_pass = bool(cfg.get("tail_sums", True)) and (T * V) % 4 == 0
+        fmom = None
+        if cfg.get("rs_shared") and r1.data_ptr() != r2.data_ptr():
+            raise ValueError("dstd_tail: rs_shared needs r1 and r2 to be the same tensor")
+        if last_pass and train:
+            fmom = arena.take(2 * _lib.STAT_REPLICAS * C * 4).view(2, -1)
+            t.fmom[0], t.fmom[1] = fmom[0].data_ptr(), fmom[1].data_ptr()
         for phase in (1, 2, 3):
             _lib.call("cg_dstd_tail_fwd", ctypes.byref(t), phase, stream)
         gate = torch.empty(B, C, dtype=f32, device=dev)
@@ -1804,8 +1812,9 @@ class _DstdTail(torch.autograd.Function):
         t.gate = gate.data_ptr()
         _lib.call("cg_dstd_tail_fwd", ctypes.byref(t), 4, stream)
         ctx.cfg, ctx.p = cfg, p
+        ctx.last_pass, ctx.has_fmom = last_pass, fmom is not None
         ctx.seed_epoch = seed_epoch(dev) if p > 0.0 else None
-        ctx.save_for_backward(*ts, h0, pooled, gate, saves)
+        ctx.save_for_backward(*ts, h0, pooled, gate, saves, *([fmom] if fmom is not None else []))
         if ostats is not None:
             ctx.mark_non_differentiable(ostats)
         return out, ostats
@@ -1814,7 +1823,8 @@ class _DstdTail(torch.autograd.Function):
     def backward(ctx, dout, _=None):
         sv = ctx.saved_tensors
         (y1, y2, r1, r2, w1, w2, gt1, bt1, ad1, gt2, bt2, ad2, gp1, bp1, ap1, gp2, bp2, ap2, wc, gc, bc, ac, sw1, sw2, bres) = sv[:25]
-        h0, pooled, gate, saves = sv[25:]
+        h0, pooled, gate, saves = sv[25:29]
+        fmom = sv[29] if ctx.has_fmom else None
         cfg = ctx.cfg
         _check_seed_epoch(ctx, y1.device, "dstd_tail")
         B, C, T, V = y1.shape
@@ -1836,6 +1846,9 @@ class _DstdTail(torch.autograd.Function):
         stream = _stream(y1)
         dgate = torch.empty(B, C, dtype=f32, device=dev)
         t.dgate = dgate.data_ptr()
+        if cfg.get("tail_sums", True):                                 # K1 leaves six row sums per (b, c); phase 2 forms red_c from them and reads no tensor
+            rows_c = torch.empty(B, C, 6, dtype=torch.float64, device=dev)
+            t.rows_c = rows_c.data_ptr()
         _lib.call("cg_dstd_tail_bwd", ctypes.byref(t), 1, stream)
         H = sw1.shape[0]
         dpooled = torch.empty(B, C, dtype=f32, device=dev)
@@ -1848,21 +1861,32 @@ class _DstdTail(torch.autograd.Function):
         red_c = arena.take(2 * C + _lib.ALPHA_SLOTS)
         red_p = [arena.take(2 * C + _lib.ALPHA_SLOTS) for _ in range(2)]
         red_t = [arena.take(2 * C + _lib.ALPHA_SLOTS) for _ in range(2)]
-        big = [torch.empty(B, C, T, V, dtype=f32, device=dev) for _ in range(6)]            # gp x2, dr x2, dy x2
+        shared = ctx.last_pass and bool(cfg.get("rs_shared"))          # identity residual: one summed gradient, written once
+        big = [None if (k == 3 and shared) else torch.empty(B, C, T, V, dtype=f32, device=dev) for k in range(6)]      # gp x2, dr x2, dy x2
         dws = [torch.empty(B, C, dtype=f32, device=dev) for _ in range(2)]
         small = torch.empty(15, C, dtype=f32, device=dev)   # dgamma/dbeta of tcn1,2 prelu1,2 compressor (10 rows) + 5 slope gradients
         dwc = torch.empty(C, 2 * C, dtype=f32, device=dev)
         t.dpooled, t.red_c = dpooled.data_ptr(), red_c.data_ptr()
         for i in range(2):
-            t.gp[i], t.red_p[i], t.dr[i], t.dw[i], t.red_t[i], t.dy[i] = (big[i].data_ptr(), red_p[i].data_ptr(), big[2 + i].data_ptr(),
+            t.gp[i], t.red_p[i], t.dr[i], t.dw[i], t.red_t[i], t.dy[i] = (big[i].data_ptr(), red_p[i].data_ptr(), _ptr(big[2 + i]),
                                                                           dws[i].data_ptr(), red_t[i].data_ptr(), big[4 + i].data_ptr())
             t.dgamma_t[i], t.dbeta_t[i], t.dgamma_p[i], t.dbeta_p[i] = (small[2 * i].data_ptr(), small[2 * i + 1].data_ptr(),
                                                                         small[4 + 2 * i].data_ptr(), small[5 + 2 * i].data_ptr())
             t.dalpha_d[i], t.dalpha_p[i] = small[10 + i].data_ptr(), small[12 + i].data_ptr()
         t.dgamma_c, t.dbeta_c, t.dalpha_c = small[8].data_ptr(), small[9].data_ptr(), small[14].data_ptr()
         t.dWc_ws, t.dWc = zb[2 * C * H:].data_ptr(), dwc.data_ptr()
-        for phase in (2, 3, 4, 5):
+        if ctx.last_pass:                                              # K3 leaves the gradient-side sums, phase 4 writes dy as well, phase 6 the parameters
+            red_q = arena.take(2 * _lib.STAT_REPLICAS * 2 * C).view(2, -1)
+            t.red_q[0], t.red_q[1] = red_q[0].data_ptr(), red_q[1].data_ptr()
+            if fmom is not None:
+                t.fmom[0], t.fmom[1] = fmom[0].data_ptr(), fmom[1].data_ptr()
+            t.rs_shared = 1 if shared else 0
+        for phase in ((2, 3, 4, 6) if ctx.last_pass else (2, 3, 4, 5)):
             _lib.call("cg_dstd_tail_bwd", ctypes.byref(t), phase, stream)
+        sums_tap = cfg.get("sums_tap")
+        if sums_tap is not None:                                       # tests: the f64 sums as the phases left them
+            sums_tap.update(red_c=red_c.clone(), red_t=[r.clone() for r in red_t], red_p=[r.clone() for r in red_p],
+                            dr1=big[3], last_pass=ctx.last_pass, shared=shared)
         al = lambda k: small[k, :1].reshape(1)
         grads = (big[4], big[5], big[2], big[3], dws[0], dws[1],
                  small[0], small[1], al(10), small[2], small[3], al(11),
@@ -1871,14 +1895,21 @@ class _DstdTail(torch.autograd.Function):
         return (None,) + tuple(g if ctx.needs_input_grad[1 + k] else None for k, g in enumerate(grads))
 
 
-def dstd_tail(ys, ystats, rs, ws, bns, alphas, wc, se, bres, train, drop_p=0.0, salts=(0, 0), emit_stats=False, taps=None):
+def dstd_tail(ys, ystats, rs, ws, bns, alphas, wc, se, bres, train, drop_p=0.0, salts=(0, 0), emit_stats=False, taps=None, tail_sums=True,
+              rs_shared=False, sums_tap=None):
     """Fused tail of a DSTD_GC block.  ys / ystats: tcn outputs of the two Domain_GCNN layers and their f64 channel sums;
     rs: their residual addends; ws: gates (B,C); bns: (tcn1.1, tcn2.1, prelu1.0, prelu2.0, compressor.1) BatchNorm holders;
     alphas: (layer1.prelu, layer2.prelu, prelu1.1, prelu2.1, compressor.2) PReLU holders; wc: compressor conv weight
-    (C,2C,1,1); se: SELayer2d holder; bres: block residual.  Returns (out, f64 channel sums of out or None)."""
+    (C,2C,1,1); se: SELayer2d holder; bres: block residual.  tail_sums: the backward forms the compressor BatchNorm's sums from row sums
+    of its first phase and, where T * V % 4 == 0, the tcn BatchNorms' sums from moments the forward and the matrix phase leave, so that
+    its last two passes are one (False: a pass each, as before).  rs_shared: rs[0] and rs[1] are the same tensor (identity residual) and
+    the backward returns ONE gradient for it, the sum, as the gradient of rs[0] and None for rs[1] (where the last pass is not merged:
+    the two gradients as before).  sums_tap: a dict that receives the f64 sums of the backward (tests).
+    Returns (out, f64 channel sums of out or None)."""
     C = ys[0].shape[1]
     cfg = {"train": bool(train), "drop_p": float(drop_p), "salts": tuple(int(s) for s in salts), "ystats": tuple(ystats), "bn": tuple(bns),
-           "emit_stats": bool(emit_stats), "taps": taps}
+           "emit_stats": bool(emit_stats), "taps": taps, "tail_sums": bool(tail_sums),
+           "rs_shared": bool(rs_shared), "sums_tap": sums_tap}
     ts = (ys[0], ys[1], rs[0], rs[1], ws[0], ws[1],
           bns[0].weight, bns[0].bias, alphas[0].weight, bns[1].weight, bns[1].bias, alphas[1].weight,
           bns[2].weight, bns[2].bias, alphas[2].weight, bns[3].weight, bns[3].bias, alphas[3].weight,

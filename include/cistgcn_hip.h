@@ -205,7 +205,7 @@ int cg_stgcn_domain_bwd(const float* x, const float* adj, const float* W, const 
  *            + block residual (+ sums of out for the next block's BatchNorm);
  *   backward phase 1: dgate | (cg_se_gate_bwd) | 2: sums at the compressor BatchNorm | 3: dh0, d a = Wc^T dh0, dWc on the matrix
  *            cores, gradient in front of prelu1/2 + its sums | 4: gate gradients dw, gradient of the residual addends, sums of
- *            the tcn BatchNorm | 5: dy_i and every per-channel parameter gradient.
+ *            the tcn BatchNorm | 5: dy_i and every per-channel parameter gradient (with `red_q`: 4 does both passes, 6 the parameters).
  * All tensors contiguous (B,C,T,V) / (B,C); C <= 64.  `stats` / `red_*` / `dWc_ws` are zeroed by the caller (slices of the
  * per-step arenas); BatchNorm bookkeeping (save mean / rstd, running statistics) as cg_norm_act. */
 typedef struct CgTailBN {
@@ -233,6 +233,14 @@ typedef struct CgDstdTail {
   float* dgamma_t[2]; float* dbeta_t[2]; float* dalpha_d[2];
   float* dgamma_p[2]; float* dbeta_p[2]; float* dalpha_p[2];
   float* dgamma_c; float* dbeta_c; float* dalpha_c;
+  double* rows_c;                /* optional, backward phases 1 and 2 together: [B][C][6] f64 scratch (nothing to zero).  Phase 1 leaves six row
+                                  * sums per (b, c) in it and phase 2 forms red_c from them and gate / dpooled with plain stores in a fixed
+                                  * order - no pass over dout and h0, red_c need not be zero, the same bits from run to run */
+  /* optional: the tcn BatchNorm's backward sums a phase early.  With `red_q` and T * V % 4 == 0 backward phase 4 writes dy as well and phase
+   * 5 is replaced by phase 6 (the per-channel parameter gradients, one small launch); train mode then needs `fmom` from forward phase 1. */
+  double* fmom[2];               /* [CG_STAT_REPLICAS][C][4] f64, zero before forward phase 1 (train): moments of q = keep PReLU_d'(u) w */
+  double* red_q[2];              /* [CG_STAT_REPLICAS][C][2] f64, zero before backward phase 3 */
+  int rs_shared, pad2;           /* with the above and r[0] == r[1] (else -1): phase 4 writes dr[0] = the sum of both residual gradients, dr[1] untouched */
 } CgDstdTail;
 int cg_dstd_tail_fwd(const CgDstdTail* t, int phase, void* stream);
 int cg_dstd_tail_bwd(const CgDstdTail* t, int phase, void* stream);
