@@ -12,6 +12,8 @@ seq_joints_n,seq_joints_dims}`).
 The torch leaf modules below (`nn.Conv2d`, `nn.BatchNorm2d`, ...) are parameter holders only; their
 `forward` is never called.  There is no CPU path: tensors must live on the HIP device.
 """
+from types import SimpleNamespace
+
 import torch
 import torch.nn as nn
 
@@ -234,8 +236,6 @@ class CISTGCN(nn.Module):
         self.fused_adj = True        # seed, expansor and adjacency of both Map2Adj towers as phase kernels (ops.map2adj_tail)
         self.fused_maps = True       # the first-level maps of a block (towers, gates, residual maps) and of the context heads stacked
         self.fused_defer = True      # BatchNorm + PReLU of the first tower level applied by the collapsing kernels on load
-        self.fused_mid = True        # the gates' and towers' BatchNorm -> Dropout -> map between the collapsing kernels and the fused tails (ops.block_mid)
-        self.fused_tail_sums = True  # the fused tail's backward forms the compressor BatchNorm's sums from row sums of its first phase (no pass of its own)
         self.stack_min_elements = 1 << 21      # block inputs smaller than this keep one contraction per first-level map
         # The reference edits the config lists in place (CISTGCN.py:514-517,548); copies are used here
         # so that one `opt` can build several models.
@@ -371,15 +371,18 @@ class CISTGCN(nn.Module):
 
     # ---- the same block with horizontal fusion ---------------------------------------------------------
     def _na_many(self, calls):
-        """calls: dicts for ops.norm_act (x may be a (tensor, sums) pair); adds train flag, dropout and site ids."""
+        """calls: dicts for ops.norm_act (x may be a (tensor, sums) pair); adds train flag, dropout and site ids.  A call numbers its
+        site here, from the counter, unless it brings its `salt` (the staged block: ids from `_block_sites`, which traced them)."""
         out = []
         for kw in calls:
             kw = dict(kw)
-            self._site += 1
             drop = kw.pop("drop", False)
-            kw.update(train=self.training, drop_p=self.dropout if drop else 0.0, salt=self._site)
-            if drop and self.drop_trace is not None:
-                self.drop_trace[kw.get("bn") if kw.get("bn") is not None else kw.get("prelu")] = self._site
+            if kw.get("salt") is None:
+                self._site += 1
+                kw["salt"] = self._site
+                if drop and self.drop_trace is not None:
+                    self.drop_trace[kw.get("bn") if kw.get("bn") is not None else kw.get("prelu")] = self._site
+            kw.update(train=self.training, drop_p=self.dropout if drop else 0.0)
             out.append(kw)
         ys = ops.norm_act_many(out)
         if self.act_trace is not None:
@@ -394,14 +397,16 @@ class CISTGCN(nn.Module):
 
     @staticmethod
     def _map_groups(x, ws):
-        """index groups of the 1x1 maps `ws` of x that `ops.pointwise_maps` takes in one launch each (at most four maps and 128
-        stacked rows, every map rounded up to 16 rows); None when one of them does not fit the kernel at all"""
+        """index groups of the 1x1 maps `ws` of x that `ops.pointwise_maps` takes in one launch each; None when one of them does not
+        fit the kernel at all.  The limits are the kernel's (csrc/tower_maps.hip, restated by `ops.pointwise_maps_ok`): at most four
+        maps and 128 stacked output rows per launch, every map rounded up to its 16-row tiles."""
+        max_maps, max_rows, tile = 4, 128, 16
         groups, rows = [], 0
         for i, w in enumerate(ws):
             if not ops.pointwise_maps_ok(x, [w]):
                 return None
-            r = (w.shape[0] + 15) // 16 * 16
-            if not groups or rows + r > 128 or len(groups[-1]) == 4:
+            r = (w.shape[0] + tile - 1) // tile * tile
+            if not groups or rows + r > max_rows or len(groups[-1]) == max_maps:
                 groups.append([])
                 rows = 0
             groups[-1].append(i)
@@ -411,349 +416,388 @@ class CISTGCN(nn.Module):
     def _block_staged(self, m, x):
         """DSTD_GC.forward (CISTGCN.py:373-390) with the gate paths (:378-384), the four Map2Adj towers (:183-189) and
         the two domain layers (:259-269) advanced in lock-step: every stage is one contraction launch or one row-kernel
-        launch for all branches instead of one launch per branch and op."""
-        tr = self.training
-        doms = (m.dsgn, m.tsgn)
-        if not all(d.interpretable for d in doms):
+        launch for all branches instead of one launch per branch and op.  Which kernels a stage launches is decided once,
+        in `_plan_block`; which dropout site each of them draws from, in `_block_sites`."""
+        if not (m.dsgn.interpretable and m.tsgn.interpretable):
             return self._block(m, x)
-        x_in, x_sums = x if isinstance(x, tuple) else (x, None)       # (tensor, f64 channel sums) from the previous block's tail in train mode
-        fused_in = ops.block_input_ok(x_in)
-        xn0 = None if fused_in else self._na(x, bn=m.global_norm)
+        x_in = x[0] if isinstance(x, tuple) else x       # (tensor, f64 channel sums) from the previous block's tail in train mode
+        p = self._plan_block(m, x_in)
+        s = self._block_sites(m)
+        br = self._branches(m, p)
+        xs = self._stage_input(m, p, s, x)
+        self._stage_maps(p, br, xs)                      # 1. every first-level map of xn
+        self._stage_map_tails(p, s, br, xs)              # 2. their BatchNorm / PReLU tails
+        self._stage_collapse(p, br)                      # 3. collapsing convolutions
+        if p.gate_fused:                                 # 4. BatchNorm tails, 5. gate Linear + last tower maps
+            self._stage_mid(m, p, s, br, xs)
+        else:
+            self._stage_mid_chain(p, s, br, xs)
+        adj = self._stage_adjacency(m, p, s, br)         # 6. rank-1 products, 7. gate output Linear + expansor
+        return self._stage_graph_tail(m, p, s, br, xs, adj)      # 8. graph product + channel mix, then BN + residual + PReLU
+
+    def _plan_block(self, m, x_in):
+        """Every route decision of one call of the staged block, taken before its first launch from the block's modules, the shape and
+        contiguity of its input, the model switches and the mode.  Every tensor a predicate is asked about further down is a fresh
+        contiguous output of a kernel, or an alias of the normalised input (contiguous wherever a stacked kernel is chosen for it), so
+        its shape says all the predicate reads: a `meta` probe stands in for it.  Left to the tail stage: whether the tcn outputs came
+        with their channel sums (a generic contraction that splits K has none) and whether the two residual aliases are one tensor."""
+        p = SimpleNamespace(tr=self.training)
         B, _, T, V = x_in.shape
-        has_res = not isinstance(m.dsgn.residual, nn.Identity)
-        has_bres = not isinstance(m.residual, nn.Identity)
-        # the normalised input feeds the statistics, the first-level maps, both graph stages and the identity residuals:
-        # one alias per consumer, so that backward sums their gradients in one launch (ops.fanout)
-        maps = [d.map_to_adj for d in doms]
-        tower_in = [c for a in maps for c in (a.time_compress[0], a.joint_compress[0])]
-        tower_w = [c.weight.view(c.out_channels, c.in_channels) for c in tower_in]
+        p.B, p.T, p.V = B, T, V
+        p.has_res = not isinstance(m.dsgn.residual, nn.Identity)
+        p.has_bres = not isinstance(m.residual, nn.Identity)
+        p.fused_in = ops.block_input_ok(x_in)
+        towers = [t for d in (m.dsgn, m.tsgn) for t in (d.map_to_adj.time_compress, d.map_to_adj.joint_compress)]
+        p.tower_w = [t[0].weight.view(t[0].out_channels, t[0].in_channels) for t in towers]
         # the four tower convolutions read the block input in one pass, forward and backward (csrc/tower_maps.hip)
         # (both stackings below pay off once the block input is worth the two or three extra small launches: measured break-even
         # between the B=16 / C=8 and the B=256 / C=64 workloads)
         big = x_in.numel() >= self.stack_min_elements
-        stacked = big and self.fused_maps and all(c.bias is None for c in tower_in) and ops.pointwise_maps_ok(x_in, tower_w)
-        cs, ct = m.conv_s[0], m.conv_t[0]
-        gates = big and self.fused_maps and cs.weight.shape == ct.weight.shape and cs.bias is None and ct.bias is None
-        rows_gate = gates and 2 * cs.out_channels <= 64 and ops.collapse_rows_ok(x_in, cs.weight.view(cs.out_channels, cs.in_channels, -1))
-        # the residual maps of a block that changes its width (1x1 convolutions WITH bias, CISTGCN.py:246-254 / :357-365) read the block
-        # input in one pass per group as well (a group: up to 128 stacked output rows)
-        res_convs = ([d.residual[0] for d in doms] if has_res else []) + ([m.residual[0]] if has_bres else [])
-        res_w = [c.weight.view(c.out_channels, c.in_channels) for c in res_convs]
-        res_groups = self._map_groups(x_in, res_w) if (big and self.fused_maps and res_convs) else None
-        n_alias = 4 + (1 if stacked else 0) + (1 if rows_gate else 0) + (len(res_groups) if res_groups else 0) + (0 if has_res else 2) + (0 if has_bres else 1)
-        if fused_in:
-            # global_norm and the block statistics from one pass over the block input; in backward the gradients of all the consumers below,
-            # the statistics' gradient and the BatchNorm backward are two streaming passes (csrc/block_input.hip)
-            self._site += 1          # the row kernel of global_norm numbers a (dropout-free) site: later layers draw the same masks on either path
-            xa, (stats_s, stats_t) = ops.block_input(x_in, m.global_norm, tr, n_alias - 1, stats=x_sums if tr else None)
-            xa = [None] + xa
-        else:
-            xa = list(ops.fanout(xn0, n_alias))
-        x_stats, xn, x_dom = xa[0], xa[1], xa[2:4]
-        k = 4
-        x_maps = x_gates = None
-        if stacked:
-            x_maps, k = xa[4], 5
-        if rows_gate:
-            x_gates, k = xa[k], k + 1
-        x_resmaps = []
-        if res_groups:
-            x_resmaps, k = xa[k:k + len(res_groups)], k + len(res_groups)
-        x_res = xa[k:k + 2] if not has_res else None
-        x_bres = xa[-1] if not has_bres else None
-        if not fused_in:
-            stats_s, stats_t = ops.fanout(ops.dstd_stats(x_stats), 2)    # one alias per gate path
-        # 1. every first-level map of xn
+        p.stacked = big and self.fused_maps and all(t[0].bias is None for t in towers) and ops.pointwise_maps_ok(x_in, p.tower_w)
         # the two gate paths start with the same (T,1) convolution shape on the same input: one convolution of the stacked weights
         # (the block input travels once instead of twice, forward and in both gradients)
-        gate_rows = gate_sums = None
+        cs, ct = m.conv_s[0], m.conv_t[0]
+        p.gates = big and self.fused_maps and cs.weight.shape == ct.weight.shape and cs.bias is None and ct.bias is None
+        p.rows_gate = p.gates and 2 * cs.out_channels <= 64 and ops.collapse_rows_ok(x_in, cs.weight.view(cs.out_channels, cs.in_channels, -1))
+        # the residual maps of a block that changes its width (1x1 convolutions WITH bias, CISTGCN.py:246-254 / :357-365) read the block
+        # input in one pass per group as well (a group: up to 128 stacked output rows)
+        res = ([d.residual for d in (m.dsgn, m.tsgn)] if p.has_res else []) + ([m.residual] if p.has_bres else [])
+        p.res_convs, p.res_bns = [r[0] for r in res], [r[1] for r in res]
+        p.res_w = [c.weight.view(c.out_channels, c.in_channels) for c in p.res_convs]
+        p.res_groups = self._map_groups(x_in, p.res_w) if (big and self.fused_maps and res) else None
+        # the residual maps with their BatchNorm as one operator per group, like the towers: backward is one reduction pass and the
+        # pointwise backward undoing the BatchNorm on load (as two operators: 229 us of cg_norm_act_bwd on the 10 -> 64 block)
+        p.res_fused = p.res_groups is not None and all(ops.tower_maps_ok(x_in, [p.res_w[i] for i in grp], [None] * len(grp)) for grp in p.res_groups)
+        # first level of the four towers with its BatchNorm + PReLU as one operator: backward never stores the gradient in front of
+        # the BatchNorm (the pointwise backward undoes BatchNorm and PReLU while loading)
+        p.tower_fused = p.stacked and ops.tower_maps_ok(x_in, p.tower_w, [t[2] for t in towers])
+
+        def collapse_ok(k, t):       # tower k's (T,1) or (1,V) convolution as a whole-sample kernel (csrc/collapse_rows.hip)
+            probe = torch.empty((B, t[0].out_channels, T, V), device="meta")      # the shape of its first-level map, nothing allocated
+            w = t[3].weight.view(t[3].out_channels, t[3].in_channels, -1)
+            return big and t[3].bias is None and (ops.collapse_rows_ok(probe, w) if k % 2 == 0 else ops.collapse_cols_ok(probe, w))
+        p.collapse = [collapse_ok(k, t) for k, t in enumerate(towers)]
+        # ... and, when every map goes into a whole-sample collapsing kernel, the BatchNorm + PReLU themselves move into that
+        # kernel's load path: the four activated (B, C/2, T, V) maps are never stored (unless branch records are asked for: `want_tap`)
+        p.defer = p.tower_fused and self.fused_defer and all(p.collapse)
+        p.adj_fused = self.fused_adj and T <= 64 and V <= 64
         # the middle of the block as one operator (csrc/block_mid.hip): only between the whole-sample collapsing kernels and the two fused tails
-        adj_fused = self.fused_adj and T <= 64 and V <= 64
-        mid_on = self.fused_mid and big and adj_fused
+        mid_on = big and p.adj_fused
         g4s, g4t = m.conv_s[4], m.conv_t[4]
-        mid_g = (mid_on and gates and x_gates is not None and g4s.bias is None and g4t.bias is None
-                 and tuple(g4s.kernel_size) == (1, V) and tuple(g4t.kernel_size) == (1, V) and g4s.out_channels == g4t.out_channels
-                 and ops.gate_head_ok(B, g4s.out_channels, 2 + 2 * T, (m.conv_s[7], m.conv_t[7], m.map_s[3], m.map_t[3]))
-                 and ops.block_mid_ok(B, [(0, cs.out_channels, V, g4s.out_channels, m.conv_s[3]), (0, cs.out_channels, V, g4t.out_channels, m.conv_t[3])]))
-        if gates:
+        heads = (m.conv_s[7], m.conv_t[7], m.map_s[3], m.map_t[3])
+        p.mid_g = (mid_on and p.rows_gate and g4s.bias is None and g4t.bias is None
+                   and tuple(g4s.kernel_size) == (1, V) and tuple(g4t.kernel_size) == (1, V) and g4s.out_channels == g4t.out_channels
+                   and ops.gate_head_ok(B, g4s.out_channels, 2 + 2 * T, heads)
+                   and ops.block_mid_ok(B, [(0, cs.out_channels, V, g4s.out_channels, m.conv_s[3]), (0, cs.out_channels, V, g4t.out_channels, m.conv_t[3])]))
+        # the (1,V) convolution leaves (B, Cg, 1, 1): everything of the two gate paths behind it in ONE launch (csrc/gate_head.hip)
+        p.gate_fused = p.mid_g or (tuple(g4s.kernel_size) == (1, V) and ops.gate_head_ok(B, g4s.out_channels, 2 + 2 * T, heads))
+        # a collapsed tower map is (B, O, 1, V) behind the (T,1) convolution and (B, O, T, 1) behind the (1,V) one
+        p.mid_t = (mid_on and p.gate_fused and all(p.collapse) and all(t[6].bias is None for t in towers)
+                   and ops.block_mid_ok(B, [(1, t[3].out_channels, T if k % 2 else V, t[6].out_channels, None) for k, t in enumerate(towers)]))
+        p.stage_fused = [self._fused_stage_ok(d.tcn[0]) for d in (m.dsgn, m.tsgn)]
+        # everything behind the two tcn convolutions in five phase launches (csrc/dstd_tail.hip)
+        p.tail_fused = self.fused_tail and m.compressor[0].out_channels <= 64
+        return p
+
+    def _block_sites(self, m):
+        """The dropout-site ids of one block by name, counted from `self._site` in the order the row-kernel chain numbers them, which
+        `self._site` is advanced past.  The ids belong to the block's modules, not to the route: a fused kernel draws its masks from
+        the ids of the row kernels it replaces (dropout-free ones included), so later layers draw the same masks on every route
+        (checks.check_block_sites_are_route_independent).  `drop_trace` gets the fourteen sites that do drop."""
+        def take(n):
+            ids = tuple(range(self._site + 1, self._site + 1 + n))
+            self._site += n
+            return ids
+        doms = (m.dsgn, m.tsgn)
+        s = SimpleNamespace()
+        s.global_norm, = take(1)
+        s.gate1 = take(2)                 # conv_s.1, conv_t.1
+        s.tower1 = take(4)                # first tower level (dropout-free)
+        s.res = take((0 if isinstance(m.dsgn.residual, nn.Identity) else 2) + (0 if isinstance(m.residual, nn.Identity) else 1))
+        s.gate5 = take(2)                 # conv_s.5, conv_t.5
+        s.tower4 = take(4)                # time_compress.4, joint_compress.4 of either Map2Adj
+        s.gate_map = take(2)              # map_s.1, map_t.1
+        s.expansor = take(2)
+        s.tcn = take(2)
+        s.tail = take(4)                  # prelu1.0, prelu2.0, compressor.1, the gated output (dropout-free)
+        if self.drop_trace is not None:
+            towers4 = [t[4] for d in doms for t in (d.map_to_adj.time_compress, d.map_to_adj.joint_compress)]
+            for mods, ids in (((m.conv_s[1], m.conv_t[1]), s.gate1), ((m.conv_s[5], m.conv_t[5]), s.gate5), (towers4, s.tower4),
+                              ((m.map_s[1], m.map_t[1]), s.gate_map), ([d.map_to_adj.expansor[1] for d in doms], s.expansor),
+                              ([d.tcn[1] for d in doms], s.tcn)):
+                self.drop_trace.update(zip(mods, ids))
+        return s
+
+    @staticmethod
+    def _branches(m, p):
+        """One record per branch of the block; each stage adds its result under the stage's name.
+        gate[i] (space, time): rows -> act -> cols (-> hidden on the row-kernel chain); tower[k] (time, joint of dsgn, then of tsgn):
+        map -> act (with `transform` when deferred) -> col -> norm -> out; res: maps -> dom[0..1], block."""
+        gate = [SimpleNamespace(conv=c, lin=l) for c, l in ((m.conv_s, m.map_s), (m.conv_t, m.map_t))]
+        pairs = [tuple(SimpleNamespace(net=t, rows=rows, transform=None) for t, rows in ((d.map_to_adj.time_compress, True), (d.map_to_adj.joint_compress, False)))
+                 for d in (m.dsgn, m.tsgn)]
+        tower = [tw for pair in pairs for tw in pair]
+        for tw, ok in zip(tower, p.collapse):
+            tw.collapse = ok
+        return SimpleNamespace(gate=gate, tower=tower, pairs=pairs, res=SimpleNamespace())
+
+    def _stage_input(self, m, p, s, x):
+        """global_norm, the block statistics and one alias of the normalised input per consumer - the statistics, the first-level maps,
+        both graph stages and the identity residuals -, so that backward sums their gradients in one launch (ops.fanout)"""
+        n_alias = 4 + int(p.stacked) + int(p.rows_gate) + len(p.res_groups or ()) + (0 if p.has_res else 2) + (0 if p.has_bres else 1)
+        if p.fused_in:
+            # global_norm and the block statistics from one pass over the block input; in backward the gradients of all the consumers below,
+            # the statistics' gradient and the BatchNorm backward are two streaming passes (csrc/block_input.hip)
+            x_in, x_sums = x if isinstance(x, tuple) else (x, None)
+            xa, gate_stats = ops.block_input(x_in, m.global_norm, p.tr, n_alias - 1, stats=x_sums if p.tr else None)
+            xa = iter([None] + list(xa))
+        else:
+            xa = iter(ops.fanout(self._na(x, bn=m.global_norm, salt=s.global_norm), n_alias))
+        xs = SimpleNamespace(stats=next(xa), norm=next(xa), dom=(next(xa), next(xa)))
+        xs.maps = next(xa) if p.stacked else None
+        xs.gates = next(xa) if p.rows_gate else None
+        xs.resmaps = [next(xa) for _ in p.res_groups or ()]
+        xs.res = None if p.has_res else (next(xa), next(xa))
+        xs.bres = None if p.has_bres else next(xa)
+        if not p.fused_in:
+            gate_stats = ops.fanout(ops.dstd_stats(xs.stats), 2)      # one alias per gate path
+        xs.gate_stats = tuple(gate_stats)
+        return xs
+
+    def _stage_maps(self, p, br, xs):
+        """1. every first-level map of xn: contraction items in the order gates | towers | residual maps, less what a stacked kernel takes"""
+        tr, xn = p.tr, xs.norm
+        cs, ct = br.gate[0].conv[0], br.gate[1].conv[0]
+        items, gate_rows = [], None
+        if p.gates:
             O = cs.out_channels
             w2 = ops.cat_channels([cs.weight.view(1, O, -1), ct.weight.view(1, O, -1)]).view(2 * O, cs.in_channels, xn.shape[2])
-            if x_gates is not None:
-                gate_rows, gate_sums = ops.collapse_rows(x_gates, w2, mid_g and tr)      # whole-sample kernel (csrc/collapse_rows.hip)
-                items = []
+            if p.rows_gate:
+                gate_rows, br.gate_sums = ops.collapse_rows(xs.gates, w2, p.mid_g and tr)      # whole-sample kernel (csrc/collapse_rows.hip)
             else:
                 items = [(("och,bchw->bow", w2, xn, None, None, None), None)]
         else:
             items = [_rows_item(xn, cs, tr), _rows_item(xn, ct, tr)]
-        if not stacked:
-            for a in maps:
-                items += [_pw_item(xn, a.time_compress[0], tr), _pw_item(xn, a.joint_compress[0], tr)]
-        if res_groups is None:
-            items += [_pw_item(xn, c, tr) for c in res_convs]
-        o = _run_items(items) if items else []
+        if not p.stacked:
+            items += [_pw_item(xn, tw.net[0], tr) for tw in br.tower]
+        if p.res_groups is None:
+            items += [_pw_item(xn, c, tr) for c in p.res_convs]
+        out = iter(_run_items(items) if items else [])
+        if p.gates:
+            yg = gate_rows if p.rows_gate else next(out)[0]
+            for g, y in zip(br.gate, ops.split_channels(yg, (O, O))):
+                g.rows = (y.unsqueeze(2), None)
+        else:
+            for g in br.gate:
+                g.rows = next(out)
+        bns, prelus = [tw.net[1] for tw in br.tower], [tw.net[2] for tw in br.tower]
+        if p.defer:
+            raw, transforms = ops.tower_maps(xs.maps, p.tower_w, bns, prelus, tr, defer=True)
+            for tw, y, t in zip(br.tower, raw, transforms):
+                tw.act, tw.transform = y, t              # the raw map: its collapsing kernel normalises and activates on load
+                if self.act_trace is not None:           # branch records: the collapsing kernels write the activated maps out as well
+                    t["want_tap"] = True
+        elif p.tower_fused:
+            for tw, h in zip(br.tower, ops.tower_maps(xs.maps, p.tower_w, bns, prelus, tr)):
+                tw.act = h
+                if self.act_trace is not None:
+                    self.act_trace[tw.net[2]] = (h.detach(), None)
+        else:
+            ys = ops.pointwise_maps(xs.maps, p.tower_w, tr) if p.stacked else [next(out) for _ in br.tower]
+            for tw, y in zip(br.tower, ys):
+                tw.map = y
+        res_biases = [c.bias for c in p.res_convs]
+        if p.res_groups is None:
+            br.res.maps = list(out)
+        else:
+            # per group; `maps` holds the finished residuals when the group operator applies the BatchNorm too (p.res_fused)
+            br.res.maps = [None] * len(p.res_convs)
+            for xg, grp in zip(xs.resmaps, p.res_groups):
+                ws, bs = [p.res_w[i] for i in grp], [res_biases[i] for i in grp]
+                ys = (ops.tower_maps(xg, ws, [p.res_bns[i] for i in grp], [None] * len(grp), tr, biases=bs) if p.res_fused
+                      else ops.pointwise_maps(xg, ws, tr, biases=bs))
+                for i, y in zip(grp, ys):
+                    br.res.maps[i] = y
+
+    def _stage_map_tails(self, p, s, br, xs):
+        """2. BatchNorm / PReLU tails of the first-level maps, for the branches whose kernel has not applied them already.  (The gates'
+        conv_s.1 / conv_t.1 with their Dropout and PReLU run inside ops.block_mid when `p.mid_g`.)"""
+        gates = [] if p.mid_g else [dict(x=g.rows, bn=g.conv[1], drop=True, prelu=g.conv[3], salt=sid) for g, sid in zip(br.gate, s.gate1)]
+        towers = [] if p.tower_fused else [dict(x=tw.map, bn=tw.net[1], prelu=tw.net[2], salt=sid) for tw, sid in zip(br.tower, s.tower1)]
+        res = [] if p.res_fused else [dict(x=y, bn=bn, salt=sid) for y, bn, sid in zip(br.res.maps, p.res_bns, s.res)]
+        if p.tower_fused:                # the towers' operator ran between the gates' maps and the residual ones: a launch on either side
+            out = iter((self._na_many(gates) if gates else []) + (self._na_many(res) if res else []))
+        else:
+            out = iter(self._na_many(gates + towers + res))
         if gates:
-            yg = gate_rows if gate_rows is not None else o.pop(0)[0]
-            o = [(g.unsqueeze(2), None) for g in ops.split_channels(yg, (O, O))] + o
-        towers_done, tower_tr = None, None
-        if stacked:
-            tb = [b for a in maps for b in (a.time_compress[1], a.joint_compress[1])]
-            tp = [b for a in maps for b in (a.time_compress[2], a.joint_compress[2])]
-            if ops.tower_maps_ok(x_maps, tower_w, tp):
-                # first level of the four towers with its BatchNorm + PReLU as one operator: backward never stores the gradient in front of
-                # the BatchNorm (the pointwise backward undoes BatchNorm and PReLU while loading)
-                # ... and, when every map goes into a whole-sample collapsing kernel, the BatchNorm + PReLU themselves move into that
-                # kernel's load path: the four activated (B, C/2, T, V) maps are never stored (unless branch records are asked for: `in_tap`)
-                def _collapse_ok(k, wmap):
-                    c_ = (maps[k // 2].time_compress if k % 2 == 0 else maps[k // 2].joint_compress)[3]
-                    if c_.bias is not None:
-                        return False
-                    probe = torch.empty((B, wmap.shape[0], T, V), device="meta")      # the shape of the raw map, nothing allocated
-                    wv = c_.weight.view(c_.out_channels, c_.in_channels, -1)
-                    return ops.collapse_rows_ok(probe, wv) if k % 2 == 0 else ops.collapse_cols_ok(probe, wv)
-                defer = self.fused_defer and big and all(_collapse_ok(k, wmap) for k, wmap in enumerate(tower_w))
-                if defer:
-                    towers_done, tower_tr = ops.tower_maps(x_maps, tower_w, tb, tp, tr, defer=True)
-                    if self.act_trace is not None:                       # branch records: the collapsing kernels write the activated maps out as well
-                        for tr_ in tower_tr:
-                            tr_["want_tap"] = True
+            for g in br.gate:
+                g.act = next(out)
+        if towers:
+            for tw in br.tower:
+                tw.act = next(out)
+        done = iter(br.res.maps if p.res_fused else out)
+        br.res.dom = (next(done), next(done)) if p.has_res else xs.res
+        br.res.block = next(done) if p.has_bres else xs.bres
+
+    def _stage_collapse(self, p, br):
+        """3. collapsing convolutions: the gates' (1,V) ones and the towers' (T,1) / (1,V) ones; a tower inside the limits of the
+        whole-sample kernels takes its own launch, the rest share one contraction launch (order gates | towers)"""
+        tr = p.tr
+        items = [] if p.mid_g else [_cols_item(g.act, g.conv[4], tr) for g in br.gate]
+        for tw in br.tower:
+            c = tw.net[3]
+            if tw.collapse:
+                x3 = tw.act[0] if isinstance(tw.act, tuple) else tw.act
+                w3 = c.weight.view(c.out_channels, c.in_channels, -1)
+                if tw.rows:
+                    y, st = ops.collapse_rows(x3, w3, tr, transform=tw.transform)      # whole-sample kernel (csrc/collapse_rows.hip)
                 else:
-                    towers_done = ops.tower_maps(x_maps, tower_w, tb, tp, tr)
-                    if self.act_trace is not None:
-                        for mod, h in zip(tp, towers_done):
-                            self.act_trace[mod] = (h.detach(), None)
-                o = o[:2] + [None] * 4 + o[2:]
+                    y, st = ops.collapse_cols(x3, w3, tr, transform=tw.transform)      # whole-sample kernel for the joint axis
+                tw.col = (y.unsqueeze(2 if tw.rows else 3), st)
             else:
-                o = o[:2] + ops.pointwise_maps(x_maps, tower_w, tr) + o[2:]
-        res_done = None
-        if res_groups:
-            res_bns = ([d.residual[1] for d in doms] if has_res else []) + ([m.residual[1]] if has_bres else [])
-            if all(ops.tower_maps_ok(xg, [res_w[i] for i in grp], [None] * len(grp)) for xg, grp in zip(x_resmaps, res_groups)):
-                # the residual maps with their BatchNorm as one operator per group, like the towers: backward is one reduction pass and the
-                # pointwise backward undoing the BatchNorm on load (as two operators: 229 us of cg_norm_act_bwd on the 10 -> 64 block)
-                res_done = [None] * len(res_convs)
-                for xg, grp in zip(x_resmaps, res_groups):
-                    hs = ops.tower_maps(xg, [res_w[i] for i in grp], [res_bns[i] for i in grp], [None] * len(grp), tr, biases=[res_convs[i].bias for i in grp])
-                    for i, h in zip(grp, hs):
-                        res_done[i] = h
-                o = o + [None] * len(res_convs)
-            else:
-                ro = [None] * len(res_convs)
-                for xg, grp in zip(x_resmaps, res_groups):
-                    for i, y in zip(grp, ops.pointwise_maps(xg, [res_w[i] for i in grp], tr, biases=[res_convs[i].bias for i in grp])):
-                        ro[i] = y
-                o = o + ro
-        gs, gt, tc = o[0], o[1], o[2:6]
-        # 2. their BatchNorm / PReLU tails
-        calls = [dict(x=gs, bn=m.conv_s[1], drop=True, prelu=m.conv_s[3]), dict(x=gt, bn=m.conv_t[1], drop=True, prelu=m.conv_t[3])]
-        if towers_done is None:
-            for i, a in enumerate(maps):
-                calls += [dict(x=tc[2 * i], bn=a.time_compress[1], prelu=a.time_compress[2]),
-                          dict(x=tc[2 * i + 1], bn=a.joint_compress[1], prelu=a.joint_compress[2])]
-        k = 6
-        n_tower_calls = len(calls) - 2
-        if res_done is None:
-            if has_res:
-                calls += [dict(x=o[k + i], bn=d.residual[1]) for i, d in enumerate(doms)]
-                k += 2
-            if has_bres:
-                calls.append(dict(x=o[k], bn=m.residual[1]))
-        # site numbers as on the row-kernel path in every case: gates, four (dropout-free) tower sites, residual maps
-        mid_x = mid_salts = None
-        if mid_g:
-            # conv_s.1 / conv_t.1 with their Dropout and PReLU run inside ops.block_mid below; their sites are numbered here
-            mid_x, mid_salts = [gs[0].squeeze(2), gt[0].squeeze(2)], (self._site + 1, self._site + 2)
-            self._site += 2
-            if self.drop_trace is not None:
-                self.drop_trace[m.conv_s[1]], self.drop_trace[m.conv_t[1]] = mid_salts
-        if towers_done is None:
-            r = [None, None] + (self._na_many(calls[2:]) if len(calls) > 2 else []) if mid_g else self._na_many(calls)
-        else:
-            r = [None, None] if mid_g else self._na_many(calls[:2])
-            self._site += 4
-            r = r + towers_done + (self._na_many(calls[2 + n_tower_calls:]) if len(calls) > 2 + n_tower_calls else [])
-        if res_done is not None:
-            self._site += len(res_done)
-            r = r + res_done
-        gs, gt, t1 = r[0], r[1], r[2:6]
-        res = r[6:8] if has_res else x_res
-        bres = r[-1] if has_bres else x_bres
-        # 3. collapsing convolutions
-        items = [] if mid_g else [_cols_item(gs, m.conv_s[4], tr), _cols_item(gt, m.conv_t[4], tr)]
-        rows3, cols3 = {}, {}
-        for i, a in enumerate(maps):
-            c3 = a.time_compress[3]
-            x3 = t1[2 * i][0] if isinstance(t1[2 * i], tuple) else t1[2 * i]
-            w3 = c3.weight.view(c3.out_channels, c3.in_channels, -1)
-            if big and c3.bias is None and ops.collapse_rows_ok(x3, w3):
-                y3, st3 = ops.collapse_rows(x3, w3, tr, transform=tower_tr[2 * i] if tower_tr else None)      # whole-sample kernel (csrc/collapse_rows.hip)
-                rows3[i] = (y3.unsqueeze(2), st3)
-            else:
-                assert tower_tr is None, "a deferred tower map needs its collapsing kernel"
-                items.append(_rows_item(t1[2 * i], c3, tr))
-            c4 = a.joint_compress[3]
-            x4 = t1[2 * i + 1][0] if isinstance(t1[2 * i + 1], tuple) else t1[2 * i + 1]
-            w4 = c4.weight.view(c4.out_channels, c4.in_channels, -1)
-            if big and c4.bias is None and ops.collapse_cols_ok(x4, w4):
-                y4, st4 = ops.collapse_cols(x4, w4, tr, transform=tower_tr[2 * i + 1] if tower_tr else None)  # whole-sample kernel for the joint axis
-                cols3[i] = (y4.unsqueeze(3), st4)
-            else:
-                assert tower_tr is None, "a deferred tower map needs its collapsing kernel"
-                items.append(_cols_item(t1[2 * i + 1], c4, tr))
-        if tower_tr and self.act_trace is not None:
-            tp_ = [b_ for a_ in maps for b_ in (a_.time_compress[2], a_.joint_compress[2])]
-            for mod, tr_ in zip(tp_, tower_tr):
-                self.act_trace[mod] = (tr_["tap"].detach(), None)
-        o = ([None, None] if mid_g else []) + (_run_items(items) if items else [])
-        if rows3 or cols3:                                               # back into the order gates | (time, joint) per tower
-            rest, o = o[2:], o[:2]
-            for i in range(len(maps)):
-                o.append(rows3[i] if i in rows3 else rest.pop(0))
-                o.append(cols3[i] if i in cols3 else rest.pop(0))
-        # 4. BatchNorm tails
+                items.append((_rows_item if tw.rows else _cols_item)(tw.act, c, tr))
+        if p.defer and self.act_trace is not None:
+            for tw in br.tower:
+                self.act_trace[tw.net[2]] = (tw.transform["tap"].detach(), None)
+        out = iter(_run_items(items) if items else [])
+        for g in [] if p.mid_g else br.gate:
+            g.cols = next(out)
+        for tw in br.tower:
+            if not tw.collapse:
+                tw.col = next(out)
+
+    def _stage_mid_chain(self, p, s, br, xs):
+        """4. / 5. on the row-kernel chain (a gate path outside ops.gate_head_ok): BatchNorm tails of gates and towers in one launch, the
+        gates' first Linear and the last tower maps in one contraction launch, then map_s.1 / map_t.1; `hidden` waits for its last Linear"""
+        tr = p.tr
+        calls = [dict(x=g.cols, bn=g.conv[5], drop=True, prelu=g.conv[7], salt=sid) for g, sid in zip(br.gate, s.gate5)]
+        calls += [dict(x=tw.col, bn=tw.net[4], drop=True, salt=sid) for tw, sid in zip(br.tower, s.tower4)]
+        r = iter(self._na_many(calls))
+        items = [_lin_item(ops.cat_channels([next(r).view(p.B, -1), st]), g.lin[0], tr) for g, st in zip(br.gate, xs.gate_stats)]
+        for tw in br.tower:
+            tw.norm = next(r)
+        items += [_pw_item(tw.norm, tw.net[6], False) for tw in br.tower]
+        out = iter(_run_items(items))
+        lin = [next(out) for _ in br.gate]
+        for tw in br.tower:
+            tw.out = next(out)
+        hidden = self._na_many([dict(x=y, bn=g.lin[1], drop=True, prelu=g.lin[3], salt=sid) for y, g, sid in zip(lin, br.gate, s.gate_map)])
+        for g, h in zip(br.gate, hidden):
+            g.hidden = h
+
+    def _stage_mid(self, m, p, s, br, xs):
+        """4. / 5. with the gate head: the towers' BatchNorm tails, then everything of the two gate paths behind their (1,V) convolutions
+        in one launch (csrc/gate_head.hip), then the last tower maps.  ops.block_mid (csrc/block_mid.hip) takes the gates' mid-section
+        (`p.mid_g`) and the towers' tails with their last maps (`p.mid_t`) into one launch in front of the gate head."""
+        tr, B, V = p.tr, p.B, p.V
         Cg = m.conv_s[4].out_channels
-        gate_fused = mid_g or (o[0][0].shape[1] == Cg and o[0][0].numel() == B * Cg and
-                               ops.gate_head_ok(B, Cg, stats_s.shape[1], (m.conv_s[7], m.conv_t[7], m.map_s[3], m.map_t[3])))
-        tower_calls = []
-        for i, a in enumerate(maps):
-            tower_calls += [dict(x=o[2 + 2 * i], bn=a.time_compress[4], drop=True), dict(x=o[3 + 2 * i], bn=a.joint_compress[4], drop=True)]
-        tower_mid = [(a.time_compress, a.joint_compress)[k] for a in maps for k in (0, 1)]
-        mid_t = (mid_on and gate_fused and len(rows3) == len(maps) and len(cols3) == len(maps) and all(c[6].bias is None for c in tower_mid)
-                 and ops.block_mid_ok(B, [(1, o[2 + k][0].shape[1], o[2 + k][0].numel() // (B * o[2 + k][0].shape[1]), c[6].out_channels, None)
-                                          for k, c in enumerate(tower_mid)]))
-        if gate_fused:
-            # everything of the two gate paths behind their (1,V) convolutions in ONE launch (csrc/gate_head.hip); the site ids are the ones
-            # the row-kernel chain numbers: conv_s.5 / conv_t.5 in front of the four tower sites, map_s.1 / map_t.1 behind them
-            s2 = (self._site + 1, self._site + 2)
-            self._site += 2
-            if mid_t:
-                tower_salts = tuple(self._site + 1 + k for k in range(len(tower_mid)))
-                self._site += len(tower_mid)
-                if self.drop_trace is not None:
-                    for c, salt in zip(tower_mid, tower_salts):
-                        self.drop_trace[c[4]] = salt
-                r = [None] * (2 + len(tower_mid))
-            else:
-                r = [None, None] + self._na_many(tower_calls)
-            s3 = (self._site + 1, self._site + 2)
-            self._site += 2
-            if self.drop_trace is not None:
-                self.drop_trace[m.conv_s[5]], self.drop_trace[m.conv_t[5]], self.drop_trace[m.map_s[1]], self.drop_trace[m.map_t[1]] = s2[0], s2[1], s3[0], s3[1]
-            mid_out = []
-            if mid_g or mid_t:
-                # gates: BatchNorm -> Dropout -> PReLU -> (1,V) convolution; towers: BatchNorm -> Dropout -> last 1x1 map: one launch, two backward
-                mitems = []
-                if mid_g:
-                    for i, cv in enumerate((m.conv_s, m.conv_t)):
-                        mitems.append(dict(kind=0, x=mid_x[i], bn=cv[1], prelu=cv[3], weight=cv[4].weight.view(Cg, -1, V), salt=mid_salts[i],
-                                           stats=(gate_sums, i * mid_x[i].shape[1], 2 * mid_x[i].shape[1]) if tr else None))
-                if mid_t:
-                    for k, c in enumerate(tower_mid):
-                        y, st = o[2 + k]
-                        mitems.append(dict(kind=1, x=y.view(B, y.shape[1], -1), bn=c[4], prelu=None, weight=c[6].weight.view(c[6].out_channels, y.shape[1]),
-                                           salt=tower_salts[k], stats=(st, 0, y.shape[1]) if tr else None))
-                mtaps = [] if self.act_trace is not None else None
-                mid_out = ops.block_mid(mitems, tr, drop_p=self.dropout, taps=mtaps)
-                if mid_g:
-                    o[0], o[1] = (mid_out[0], None), (mid_out[1], None)
-                    mid_out = mid_out[2:]
-                    if mtaps is not None:
-                        self.act_trace[m.conv_s[3]], self.act_trace[m.conv_t[3]] = (mtaps[0].unsqueeze(2), None), (mtaps[1].unsqueeze(2), None)
+        if not p.mid_t:
+            norms = self._na_many([dict(x=tw.col, bn=tw.net[4], drop=True, salt=sid) for tw, sid in zip(br.tower, s.tower4)])
+            for tw, h in zip(br.tower, norms):
+                tw.norm = h
+        if p.mid_g or p.mid_t:
+            # gates: BatchNorm -> Dropout -> PReLU -> (1,V) convolution; towers: BatchNorm -> Dropout -> last 1x1 map: one launch, two backward
+            items = []
+            if p.mid_g:
+                for i, (g, sid) in enumerate(zip(br.gate, s.gate1)):
+                    x1 = g.rows[0].squeeze(2)
+                    items.append(dict(kind=0, x=x1, bn=g.conv[1], prelu=g.conv[3], weight=g.conv[4].weight.view(Cg, -1, V), salt=sid,
+                                      stats=(br.gate_sums, i * x1.shape[1], 2 * x1.shape[1]) if tr else None))
+            if p.mid_t:
+                for tw, sid in zip(br.tower, s.tower4):
+                    (y, st), c = tw.col, tw.net[6]
+                    items.append(dict(kind=1, x=y.view(B, y.shape[1], -1), bn=tw.net[4], prelu=None, weight=c.weight.view(c.out_channels, y.shape[1]),
+                                      salt=sid, stats=(st, 0, y.shape[1]) if tr else None))
             taps = [] if self.act_trace is not None else None
-            m.w1, m.w2 = ops.gate_head([o[0][0].view(B, Cg), o[1][0].view(B, Cg)], [stats_s, stats_t], [m.conv_s, m.conv_t], [m.map_s, m.map_t], tr,
-                                       drop_p=self.dropout, salts=((s2[0], s3[0]), (s2[1], s3[1])), taps=taps)
-            if taps is not None:
-                self.act_trace[m.conv_s[7]], self.act_trace[m.map_s[3]] = (taps[0], None), (taps[1], None)
-                self.act_trace[m.conv_t[7]], self.act_trace[m.map_t[3]] = (taps[2], None), (taps[3], None)
-            items, g = [], None
-        else:
-            calls = [dict(x=o[0], bn=m.conv_s[5], drop=True, prelu=m.conv_s[7]), dict(x=o[1], bn=m.conv_t[5], drop=True, prelu=m.conv_t[7])]
-            r = self._na_many(calls + tower_calls)
-            hs = ops.cat_channels([r[0].view(B, -1), stats_s])
-            ht = ops.cat_channels([r[1].view(B, -1), stats_t])
-            items = [_lin_item(hs, m.map_s[0], tr), _lin_item(ht, m.map_t[0], tr)]
-        # 5. gate Linear + last tower maps
-        if mid_t:
-            o = [(y, None) for y in mid_out]
-        else:
-            for i, a in enumerate(maps):
-                items += [_pw_item(r[2 + 2 * i], a.time_compress[6], False), _pw_item(r[3 + 2 * i], a.joint_compress[6], False)]
-            o = _run_items(items)
-        if gate_fused:
-            o = [None, None] + o
-        else:
-            g = self._na_many([dict(x=o[0], bn=m.map_s[1], drop=True, prelu=m.map_s[3]), dict(x=o[1], bn=m.map_t[1], drop=True, prelu=m.map_t[3])])
-        # 6. rank-1 products  o[b,v,t,tau] = s[b,v,t] q[b,tau,v]  |  o[b,t,v,w] = s[b,v,t] q[b,t,w]
-        seeds = []
-        for i, d in enumerate(doms):
-            q, s = o[2 + 2 * i][0].view(B, T, V), o[3 + 2 * i][0].view(B, V, T)
-            seeds.append((0 if d.domain == "space" else 1, s, q))
-        if adj_fused:
+            out = iter(ops.block_mid(items, tr, drop_p=self.dropout, taps=taps))
+            if p.mid_g:
+                for g in br.gate:
+                    g.cols = (next(out), None)
+                if taps is not None:
+                    self.act_trace[m.conv_s[3]], self.act_trace[m.conv_t[3]] = (taps[0].unsqueeze(2), None), (taps[1].unsqueeze(2), None)
+            if p.mid_t:
+                for tw in br.tower:
+                    tw.out = (next(out), None)
+        # the site ids are the ones the row-kernel chain numbers: conv_s.5 / conv_t.5 in front of the four tower sites, map_s.1 / map_t.1 behind them
+        taps = [] if self.act_trace is not None else None
+        m.w1, m.w2 = ops.gate_head([g.cols[0].view(B, Cg) for g in br.gate], list(xs.gate_stats), [m.conv_s, m.conv_t], [m.map_s, m.map_t], tr,
+                                   drop_p=self.dropout, salts=tuple(zip(s.gate5, s.gate_map)), taps=taps)
+        if taps is not None:
+            self.act_trace[m.conv_s[7]], self.act_trace[m.map_s[3]] = (taps[0], None), (taps[1], None)
+            self.act_trace[m.conv_t[7]], self.act_trace[m.map_t[3]] = (taps[2], None), (taps[3], None)
+        if not p.mid_t:
+            for tw, y in zip(br.tower, _run_items([_pw_item(tw.norm, tw.net[6], False) for tw in br.tower])):
+                tw.out = y
+
+    def _stage_adjacency(self, m, p, s, br):
+        """6. / 7. the Map2Adj seeds  o[b,v,t,tau] = s[b,v,t] q[b,tau,v]  |  o[b,t,v,w] = s[b,v,t] q[b,t,w]  of the tower pairs and
+        their expansors -> [Adj of dsgn, Adj of tsgn]; a gate path on the row-kernel chain gets its output Linear here (m.w1, m.w2)"""
+        tr, B, T, V = p.tr, p.B, p.T, p.V
+        doms = (m.dsgn, m.tsgn)
+        expansors = [d.map_to_adj.expansor for d in doms]
+        seeds = [(0 if d.domain == "space" else 1, joint.out[0].view(B, V, T), time.out[0].view(B, T, V)) for d, (time, joint) in zip(doms, br.pairs)]
+        last = [] if p.gate_fused else [_lin_item(g.hidden, g.lin[4], False) for g in br.gate]
+        if p.adj_fused:
             # seed, expansor and adjacency of both towers in two phase launches (csrc/map2adj_tail.hip); the seed is never stored
-            if not gate_fused:
-                o = _run_items([_lin_item(g[0], m.map_s[4], False), _lin_item(g[1], m.map_t[4], False)])
-                m.w1, m.w2 = o[0][0], o[1][0]
-            self._site += 2
-            if self.drop_trace is not None:
-                self.drop_trace[maps[0].expansor[1]], self.drop_trace[maps[1].expansor[1]] = self._site - 1, self._site
+            if last:
+                (m.w1, _), (m.w2, _) = _run_items(last)
             taps = [] if self.act_trace is not None else None
-            adj = ops.map2adj_tail(seeds, [a.expansor for a in maps], tr, drop_p=self.dropout, salts=(self._site - 1, self._site), taps=taps)
-            adj = [(a, None) for a in adj]
+            adj = ops.map2adj_tail(seeds, expansors, tr, drop_p=self.dropout, salts=s.expansor, taps=taps)
             if taps is not None:
-                for a, tap in zip(maps, taps):
-                    self.act_trace[a.expansor[3]] = (tap, None)
+                for e, tap in zip(expansors, taps):
+                    self.act_trace[e[3]] = (tap, None)
+            return list(adj)
+        if T <= 64 and V <= 64:
+            oo = ops.rank1_adj(seeds)                        # both towers in one launch; backward reads each d o once
         else:
-            if T <= 64 and V <= 64:
-                oo = ops.rank1_adj(seeds)                        # both towers in one launch; backward reads each d o once
-            else:
-                oo = [y for y, _ in ops.contract_many([("bvt,bxv->bvtx" if dom == 0 else "bvt,btw->btvw", s, q, None, None, None)
-                                                       for dom, s, q in seeds])]
-            # 7. gate output Linear + expansor first map
-            items = [] if gate_fused else [_lin_item(g[0], m.map_s[4], False), _lin_item(g[1], m.map_t[4], False)]
-            items += [_pw_item(oo[i], a.expansor[0], tr) for i, a in enumerate(maps)]
-            o = _run_items(items)
-            if gate_fused:
-                o = [None, None] + o
-            else:
-                m.w1, m.w2 = o[0][0], o[1][0]
-            e = self._na_many([dict(x=o[2 + i], bn=a.expansor[1], drop=True, prelu=a.expansor[3]) for i, a in enumerate(maps)])
-            adj = _run_items([_pw_item(e[i], a.expansor[4], False) for i, a in enumerate(maps)])
-        # 8. graph product + channel mix, then BN + residual + PReLU
+            oo = [y for y, _ in ops.contract_many([("bvt,bxv->bvtx" if dom == 0 else "bvt,btw->btvw", sv, q, None, None, None) for dom, sv, q in seeds])]
+        # 7. gate output Linear + expansor first map
+        out = iter(_run_items(last + [_pw_item(o, e[0], tr) for o, e in zip(oo, expansors)]))
+        if last:
+            m.w1, m.w2 = next(out)[0], next(out)[0]
+        h = self._na_many([dict(x=next(out), bn=e[1], drop=True, prelu=e[3], salt=sid) for e, sid in zip(expansors, s.expansor)])
+        return [y for y, _ in _run_items([_pw_item(hi, e[4], False) for hi, e in zip(h, expansors)])]
+
+    def _stage_graph_tail(self, m, p, s, br, xs, adj):
+        """8. graph product + channel mix of both domain layers, then everything behind them: BatchNorm + residual + PReLU, gates,
+        compressor, squeeze-excite, block residual.  Returns the block output, in train mode with its f64 channel sums."""
+        tr = p.tr
+        doms = (m.dsgn, m.tsgn)
+        res, bres = br.res.dom, br.res.block
         ys = []
-        for i, d in enumerate(doms):
-            d.Adj = adj[i][0]
+        for d, x_dom, a, fused in zip(doms, xs.dom, adj, p.stage_fused):
+            d.Adj = a
             conv = d.tcn[0]
-            if self._fused_stage_ok(conv):
+            if fused:
                 wmat = conv.weight.view(conv.out_channels, conv.in_channels)
-                ys.append(ops.stgcn_domain(x_dom[i], d.Adj, wmat, conv.bias, 0 if d.domain == "space" else 1, tr))
+                ys.append(ops.stgcn_domain(x_dom, d.Adj, wmat, conv.bias, 0 if d.domain == "space" else 1, tr))
             else:
                 spec = "bctv,bvtq->bcqv" if d.domain == "space" else "bctv,btvw->bctw"
-                ys.append(self._lin(_pointwise, ops.contract(spec, x_dom[i], d.Adj), conv))
+                ys.append(self._lin(_pointwise, ops.contract(spec, x_dom, d.Adj), conv))
         c = m.compressor
-        if self.fused_tail and c[0].out_channels <= 64 and all(isinstance(y, tuple) and (y[1] is not None or not tr) for y in ys):
-            # everything behind the two tcn convolutions in five phase launches (csrc/dstd_tail.hip)
-            self._site += 2
-            if self.drop_trace is not None:
-                self.drop_trace[doms[0].tcn[1]], self.drop_trace[doms[1].tcn[1]] = self._site - 1, self._site
+        # (a generic contraction that had to split K comes without channel sums: only the call itself tells)
+        if p.tail_fused and all(st is not None or not tr for _, st in ys):
+            # everything behind the two tcn convolutions in five phase launches (csrc/dstd_tail.hip); the four (dropout-free) sites of
+            # the row-kernel chain below stay unused
             taps = [] if self.act_trace is not None else None
-            rs_shared = self.fused_tail_sums and not has_res and res[0].data_ptr() == res[1].data_ptr()      # identity residuals: one summed gradient
-            out, ost = ops.dstd_tail([y[0] for y in ys], [y[1] for y in ys], res, (m.w1, m.w2),
-                                     (doms[0].tcn[1], doms[1].tcn[1], m.prelu1[0], m.prelu2[0], c[1]),
-                                     (doms[0].prelu, doms[1].prelu, m.prelu1[1], m.prelu2[1], c[2]), c[0].weight, c[3], bres, tr,
-                                     drop_p=self.dropout, salts=(self._site - 1, self._site), emit_stats=tr, taps=taps,
-                                     tail_sums=self.fused_tail_sums, rs_shared=rs_shared)
+            rs_shared = not p.has_res and res[0].data_ptr() == res[1].data_ptr()      # identity residuals: one summed gradient
+            alphas = (doms[0].prelu, doms[1].prelu, m.prelu1[1], m.prelu2[1], c[2])
+            out, ost = ops.dstd_tail([y for y, _ in ys], [st for _, st in ys], res, (m.w1, m.w2),
+                                     (doms[0].tcn[1], doms[1].tcn[1], m.prelu1[0], m.prelu2[0], c[1]), alphas, c[0].weight, c[3], bres, tr,
+                                     drop_p=self.dropout, salts=s.tcn, emit_stats=tr, taps=taps, rs_shared=rs_shared)
             if taps is not None:
-                for mod, tap in zip((doms[0].prelu, doms[1].prelu, m.prelu1[1], m.prelu2[1], c[2]), taps):
+                for mod, tap in zip(alphas, taps):
                     self.act_trace[mod] = (tap, None)
-            self._site += 4          # the row-kernel chain below numbers four more (dropout-free) sites: later blocks draw the same masks on either path
             return (out, ost) if tr else out
-        x12 = self._na_many([dict(x=ys[i], bn=d.tcn[1], drop=True, add=res[i], prelu=d.prelu) for i, d in enumerate(doms)])
-        ab = self._na_many([dict(x=x12[0], pre=m.w1, bn=m.prelu1[0], prelu=m.prelu1[1]),
-                            dict(x=x12[1], pre=m.w2, bn=m.prelu2[0], prelu=m.prelu2[1])])
-        h = self._na(self._lin(_pointwise, ops.cat_channels(ab), c[0]), bn=c[1], prelu=c[2])
+        s_prelu1, s_prelu2, s_compressor, s_out = s.tail
+        x12 = self._na_many([dict(x=y, bn=d.tcn[1], drop=True, add=r, prelu=d.prelu, salt=sid) for y, d, r, sid in zip(ys, doms, res, s.tcn)])
+        ab = self._na_many([dict(x=x12[0], pre=m.w1, bn=m.prelu1[0], prelu=m.prelu1[1], salt=s_prelu1),
+                            dict(x=x12[1], pre=m.w2, bn=m.prelu2[0], prelu=m.prelu2[1], salt=s_prelu2)])
+        h = self._na(self._lin(_pointwise, ops.cat_channels(ab), c[0]), bn=c[1], prelu=c[2], salt=s_compressor)
         h_pool, h = ops.fanout(h, 2)                                     # squeeze | excite
         gate = ops.se_gate(ops.mean_bc(h_pool), c[3].w1, c[3].w2)
         # the next block starts with a BatchNorm of this output: let the kernel emit its channel sums (train mode)
-        return self._na(h, pre=gate, add=bres, add_post=True, emit_stats=tr)
+        return self._na(h, pre=gate, add=bres, add_post=True, emit_stats=tr, salt=s_out)
 
     # ---- FPN.forward, CISTGCN.py:74-79 -------------------------------------------------------------
     def _fpn(self, m, x, x_pool=None):

@@ -1066,6 +1066,50 @@ def check_model_plan(device, entry, mode, stack_all=False, **cfg_kw):
     return r
 
 
+SITE_SHAPES = ((8, 10, 22, 8), (72, 10, 22, 8), (8, 70, 6, 8))          # (C, T, V, B): every fused route | past the tail and gate-head limits | past the adjacency limit
+SITE_SWITCHES = ("fused_tail", "fused_adj", "fused_maps", "fused_defer")
+
+
+def check_block_sites_are_route_independent(device):
+    """The dropout-site ids of a DSTD_GC block are a property of its modules, not of the kernel route the staged block takes: one train-mode
+    forward (dropout 0.1, blocks=1, txc=1) per route - everything on, each model switch off alone, `ops.block_mid_ok` saying no, all of
+    them together - must leave the same `drop_trace` (module name -> site id) and the same final `_site`.  Later blocks and the context
+    branch draw their masks from those ids, so a route that counted differently would silently change them.  The absolute numbers of the
+    first shape (49 named sites, the counter at 95) are the ones every route of the one-method staged block produced."""
+    routes = [("everything on", (), False)] + [(k + " off", (k,), False) for k in SITE_SWITCHES] + \
+             [("block_mid_ok False", (), True), ("all off", SITE_SWITCHES, True)]
+    for C, T, V, B in SITE_SHAPES:
+        for stack_all in (False, True):
+            net, _ = build_pair(C, T, V, device, stack_all=stack_all, dropout=0.1, blocks=1, txc=1)
+            net.train()
+            names = {m: n for n, m in net.named_modules()}
+            x = (50 + 350.0 * torch.randn(B, T, V, 3, generator=_gen(7))).to(device)
+            first = None
+            for what, off, no_mid in routes:
+                saved = ops.block_mid_ok
+                for k in SITE_SWITCHES:
+                    setattr(net, k, k not in off)
+                if no_mid:
+                    ops.block_mid_ok = lambda B_, items: False
+                net.drop_trace = {}
+                try:
+                    with torch.no_grad():
+                        net(x)
+                    got = ({names[m]: s for m, s in net.drop_trace.items()}, net._site)
+                finally:
+                    ops.block_mid_ok = saved
+                    net.drop_trace = None
+                where = "(C, T, V, B) = %s stack_all=%s, route '%s'" % ((C, T, V, B), stack_all, what)
+                print("%s: %d named sites, counter at %d" % (where, len(got[0]), got[1]))
+                if first is None:
+                    first = got
+                    if (C, T, V, B) == SITE_SHAPES[0] and not stack_all:
+                        assert (len(got[0]), got[1]) == (49, 95), "%s: %d sites, counter at %d" % (where, len(got[0]), got[1])
+                assert got[1] == first[1], "%s: the site counter ends at %d, with everything on at %d" % (where, got[1], first[1])
+                assert got[0] == first[0], "%s: sites differ from the first route: %s" % (
+                    where, sorted((k, first[0].get(k), got[0].get(k)) for k in set(first[0]) | set(got[0]) if first[0].get(k) != got[0].get(k)))
+
+
 # every shape predicate the launch plan asks, at its limit and one step past it: (family, operator check, its shape AT the limit)
 LIMIT_SHAPES = (
     ("collapse_rows V = 32, O = 64", "check_collapse_rows", (2, 6, 4, 32, 64)),

@@ -107,6 +107,11 @@ def test_model_launch_plans_with_dropout(name):
     assert r["dropout_sites"] == 14 * 3 + 7, r["dropout_sites"]              # blocks = 1: two input blocks and the output block
 
 
+def test_block_sites_are_route_independent():
+    """the dropout-site ids of a block do not depend on the kernel route the staged block takes (checks.check_block_sites_are_route_independent)"""
+    checks.check_block_sites_are_route_independent("cpu")
+
+
 @pytest.mark.skipif(os.environ.get("HIPEMU_SANITIZE", "0") == "1", reason="torch's tracer ends an interpreter that runs under libasan")
 def test_model_survives_jit_trace():
     """`writer.add_graph(model, batch)` (train.py:137) = `torch.jit.trace` with its default self-check: the hot path appears as one

@@ -306,6 +306,11 @@ def test_model_launch_plans_with_dropout(name):
     assert r["dropout_sites"] == 14 * 3 + 7, r["dropout_sites"]
 
 
+def test_block_sites_are_route_independent():
+    """the dropout-site ids of a block do not depend on the kernel route the staged block takes, on the device's own predicates"""
+    checks.check_block_sites_are_route_independent("cuda")
+
+
 @pytest.mark.parametrize("cfg", [(8, 10, 22, 8), (32, 50, 25, 64)], ids=str)
 def test_dropout_step_matches_oracle_on_the_same_masks(cfg):
     """The configuration the benchmark times - train mode WITH dropout 0.1 (train_h36m.yaml) - against the oracle: the oracle applies,
