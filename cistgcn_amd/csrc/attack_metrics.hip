@@ -105,12 +105,6 @@ __device__ __forceinline__ int cg_am_bin(float x, float mx, float per_mx) {
   return k;
 }
 
-__device__ __forceinline__ double cg_am_wave_max(double v) {
-#pragma unroll
-  for (int off = CG_WAVE / 2; off > 0; off >>= 1) v = fmax(v, __shfl_xor(v, off, CG_WAVE));
-  return v;
-}
-
 // ---------------------------------------------------------------------------------------------
 // frame pass: wave w of workgroup g takes frames g * CG_AM_WAVES + w, + gridDim.x * CG_AM_WAVES, ...
 // ---------------------------------------------------------------------------------------------
@@ -153,9 +147,9 @@ __global__ __launch_bounds__(CG_AM_THREADS) void cg_am_frame_kernel(CgAttackMetr
     }
     double r[CG_AM_SUMS - 1] = {on ? e : 0.0, on ? en : 0.0, on ? epa : 0.0, se, h, P[0] * X[0] + P[1] * X[1] + P[2] * X[2],
                                 P[0] * P[0] + P[1] * P[1] + P[2] * P[2], X[0] * X[0] + X[1] * X[1] + X[2] * X[2]};
-    cg_em_wave_sum(r);
-    const double hmax = cg_am_wave_max(h);
-    const float fm = cg_em_wave_max(on ? rm : 0.f);
+    cg_wave_allsum(r);
+    const double hmax = cg_wave_allmax(h);
+    const float fm = cg_wave_allmax(on ? rm : 0.f);
     if (lane < CG_AM_SUMS) {
       double v = hmax;
 #pragma unroll
@@ -198,8 +192,8 @@ __global__ __launch_bounds__(CG_AM_TILE) void cg_am_cross_kernel(CgAttackMetrics
   }
   const double h = on ? sqrt(h2) : 0.0;
   double r[CG_AM_CROSS - 1] = {h, P[0] * X[0], P[1] * X[1], P[2] * X[2], P[0] * P[0], P[1] * P[1], P[2] * P[2], X[0] * X[0], X[1] * X[1], X[2] * X[2]};
-  cg_em_wave_sum(r);
-  const double hmax = cg_am_wave_max(h);
+  cg_wave_allsum(r);
+  const double hmax = cg_wave_allmax(h);
   if (lane < CG_AM_CROSS) {
     double v = hmax;
 #pragma unroll
@@ -226,7 +220,7 @@ __global__ __launch_bounds__(CG_AM_THREADS) void cg_am_range_kernel(CgAttackMetr
     } else {
       for (long long f = lane; f < F; f += CG_WAVE) m = fmaxf(m, w.rowmax[f * J + (g - B - T)]);
     }
-    m = cg_em_wave_max(m);
+    m = cg_wave_allmax(m);
     if (lane == 0) a.gmax[g] = m;
   }
 }
@@ -304,8 +298,8 @@ __global__ __launch_bounds__(CG_AM_HIST_THREADS) void cg_am_hist_kernel(CgAttack
 // sums over the workgroup in a fixed order (the butterfly of each wave, then the waves in turn), result in every thread
 __device__ __forceinline__ void cg_am_block_reduce(double (&s)[CG_AM_NS], double& m, double* red) {
   const int lane = threadIdx.x & (CG_WAVE - 1), wave = threadIdx.x / CG_WAVE;
-  cg_em_wave_sum(s);
-  m = cg_am_wave_max(m);
+  cg_wave_allsum(s);
+  m = cg_wave_allmax(m);
   __syncthreads();
   if (lane == 0) {
 #pragma unroll
@@ -410,13 +404,13 @@ __global__ __launch_bounds__(CG_AM_THREADS) void cg_am_finish_kernel(CgAttackMet
     const double width = (double)mx / CG_AM_BINS, eps = 1e-8;
     const double p = (double)ca / (double)hist_n / width, q = (double)co / (double)hist_n / width, mid = (p + q) / 2.0;
     double r[3] = {p * (log(p + eps) - log(q + eps)), p * (log(p + eps) - log(mid + eps)), q * (log(q + eps) - log(mid + eps))};
-    cg_em_wave_sum(r);
+    cg_wave_allsum(r);
     int cum = ca - co;      // the cumulated counts are exact
     for (int off = 1; off < CG_WAVE; off <<= 1) {
       const int up = __shfl_up(cum, off, CG_WAVE);
       if (lane >= off) cum += up;
     }
-    const double ks = cg_am_wave_max(fabs((double)cum) / (double)hist_n / width);
+    const double ks = cg_wave_allmax(fabs((double)cum) / (double)hist_n / width);
     if (lane == 0) {
       const bool flat = !(mx > 0.f);      // every joint of the group coincides: the 65 edges are all 0, the densities undefined
       a.out[ob + CG_AM_Q_KLD][g] = flat ? NAN : (float)r[0];

@@ -1,6 +1,6 @@
 // Argument block of the block-input kernels (block_input.hip); mirrored by include/cistgcn_hip.h and cistgcn_amd/_lib.py.
 #pragma once
-#include "dstd_tail.h"        // CgTailBN
+#include "cg_bn.h"            // CgTailBN
 
 // Head of DSTD_GC.forward (reference CISTGCN.py:375-379): xn = global_norm(x) and _get_stats_(xn) (:360-371) from ONE pass over the block
 // input; backward: the gradients of every consumer of xn (up to CG_BIN_MAXG tensors), the gradient of the statistics and the BatchNorm

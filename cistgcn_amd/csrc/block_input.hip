@@ -22,20 +22,6 @@ HIP_DYNAMIC_SHARED(unsigned char, cg_dyn_lds)
 #define CG_BIN_SPAN 4608                     // floats of a workgroup's span (whole channel planes)
 
 struct CgBinGeom { int TV, NPL, cps, L; unsigned magicTV, magicV; };      // plane size, planes per span, spans per sample, floats of a full span
-__device__ __forceinline__ int cg_bin_div(int n, unsigned magic) { return (int)(((unsigned long long)(unsigned)n * magic) >> 32); }
-
-template <int VW>
-__device__ __forceinline__ void cg_bin_ld(const float* p, float v[4]) {
-  if (VW == 4) { const float4 t = *reinterpret_cast<const float4*>(p); v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w; }
-  else if (VW == 2) { const float2 t = *reinterpret_cast<const float2*>(p); v[0] = t.x; v[1] = t.y; }
-  else v[0] = *p;
-}
-template <int VW>
-__device__ __forceinline__ void cg_bin_st(float* p, const float v[4]) {
-  if (VW == 4) *reinterpret_cast<float4*>(p) = make_float4(v[0], v[1], v[2], v[3]);
-  else if (VW == 2) *reinterpret_cast<float2*>(p) = make_float2(v[0], v[1]);
-  else *p = v[0];
-}
 
 // ======================================================================================================================
 // forward A
@@ -57,14 +43,14 @@ __global__ __launch_bounds__(CG_BIN_THREADS) void cg_bin_fwd_kernel(CgBlockInput
   float* __restrict__ yp = t.xn + base;
   for (int e = tid * VW; e < L; e += CG_BIN_THREADS * VW) {
     float v[4];
-    cg_bin_ld<VW>(xp + e, v);
-    const float* a = sAff + 4 * cg_bin_div(e, g.magicTV);      // TV % VW == 0: a vector never straddles two planes
+    cg_ldv<VW>(xp + e, v);
+    const float* a = sAff + 4 * (int)cg_div_ge2((unsigned)e, g.magicTV);      // TV % VW == 0: a vector never straddles two planes
 #pragma unroll
     for (int j = 0; j < VW; ++j) {
       v[j] = (v[j] - a[0]) * a[1] + a[2];                       // mean first, as cg_norm_act
       sXn[e + j] = v[j];
     }
-    cg_bin_st<VW>(yp + e, v);
+    cg_stv<VW>(yp + e, v);
   }
   __syncthreads();
   const long long rbase = ((long long)b * t.C + c0) * t.T;
@@ -210,13 +196,13 @@ __global__ __launch_bounds__(CG_BIN_THREADS) void cg_bin_bwd_sum_kernel(CgBlockI
   for (int i = 0; i < CG_BIN_MAXG; ++i) gsrc[i] = (i < t.ng && t.g[i]) ? t.g[i] + base : nullptr;
   for (int e = tid * VW; e < L; e += CG_BIN_THREADS * VW) {
     float x[4], acc[4] = {0.f, 0.f, 0.f, 0.f};
-    cg_bin_ld<VW>(xp + e, x);
+    cg_ldv<VW>(xp + e, x);
     // every gradient's vector is REQUESTED before the first one is added: with the add right behind its load the kernel made up to eight
     // memory round trips one after the other per vector (load - wait - add, found in the ISA in round 4)
     float gv[CG_BIN_MAXG][4];
 #pragma unroll
     for (int i = 0; i < CG_BIN_MAXG; ++i)
-      if (gsrc[i]) cg_bin_ld<VW>(gsrc[i] + e, gv[i]);
+      if (gsrc[i]) cg_ldv<VW>(gsrc[i] + e, gv[i]);
 #pragma unroll
     for (int i = 0; i < CG_BIN_MAXG; ++i) {
       if (gsrc[i]) {
@@ -224,7 +210,7 @@ __global__ __launch_bounds__(CG_BIN_THREADS) void cg_bin_bwd_sum_kernel(CgBlockI
         for (int j = 0; j < VW; ++j) acc[j] += gv[i][j];
       }
     }
-    const int pl = cg_bin_div(e, g.magicTV);                    // TV % VW == 0: a vector never straddles two planes
+    const int pl = (int)cg_div_ge2((unsigned)e, g.magicTV);                    // TV % VW == 0: a vector never straddles two planes
     const float* a = sAff + 4 * pl;
     if (pl != cur) {
       if (cur >= 0) { atomicAdd(&sRed[2 * cur], s1); atomicAdd(&sRed[2 * cur + 1], s2); }
@@ -232,14 +218,14 @@ __global__ __launch_bounds__(CG_BIN_THREADS) void cg_bin_bwd_sum_kernel(CgBlockI
     }
 #pragma unroll
     for (int j = 0; j < VW; ++j) {
-      const int r = cg_bin_div(e + j, g.magicV);
+      const int r = (int)cg_div_ge2((unsigned)(e + j), g.magicV);
       const float d = x[j] - a[0];
       const float xn = d * a[2] + a[3];                          // the forward's expression: the same xn bit for bit
       const float G = acc[j] + xn * sPQ[2 * r] + sPQ[2 * r + 1];
       acc[j] = G;
       s1 += (double)G; s2 += (double)G * (double)(d * a[1]);
     }
-    cg_bin_st<VW>(gp + e, acc);
+    cg_stv<VW>(gp + e, acc);
   }
   if (cur >= 0) { atomicAdd(&sRed[2 * cur], s1); atomicAdd(&sRed[2 * cur + 1], s2); }
   __syncthreads();
@@ -258,8 +244,8 @@ __global__ __launch_bounds__(CG_BIN_THREADS) void cg_bin_bwd_apply_kernel(CgBloc
   if (tid < npl) {
     const int c = c0 + tid;
     const CgAff a = cg_tail_aff(t.bn, c, t.C, 0.0, 0, true, false);
-    double s1 = 0.0, s2 = 0.0;
-    for (int r = 0; r < CG_STAT_REPLICAS; ++r) { s1 += t.red[((long long)r * t.C + c) * 2]; s2 += t.red[((long long)r * t.C + c) * 2 + 1]; }
+    double s1, s2;
+    cg_bn_sums(t.red, t.C, c, s1, s2);
     const double cnt = (double)t.B * (double)g.TV;
     float* k = sAff + 6 * tid;
     k[0] = a.mean; k[1] = a.rstd; k[2] = a.gamma * a.rstd;
@@ -274,18 +260,16 @@ __global__ __launch_bounds__(CG_BIN_THREADS) void cg_bin_bwd_apply_kernel(CgBloc
   float* __restrict__ dp = t.dx + base;
   for (int e = tid * VW; e < L; e += CG_BIN_THREADS * VW) {
     float x[4], G[4];
-    cg_bin_ld<VW>(xp + e, x);
-    cg_bin_ld<VW>(gp + e, G);
-    const float* k = sAff + 6 * cg_bin_div(e, g.magicTV);
+    cg_ldv<VW>(xp + e, x);
+    cg_ldv<VW>(gp + e, G);
+    const float* k = sAff + 6 * (int)cg_div_ge2((unsigned)e, g.magicTV);
 #pragma unroll
     for (int j = 0; j < VW; ++j) G[j] = k[2] * (G[j] - k[3] - (x[j] - k[0]) * k[1] * k[4]);
-    cg_bin_st<VW>(dp + e, G);
+    cg_stv<VW>(dp + e, G);
   }
 }
 
 // ---- host side ---------------------------------------------------------------------------------------------------
-static unsigned cg_bin_magic(int d) { return (unsigned)((0x100000000ULL + (unsigned)d - 1) / (unsigned)d); }
-
 static int cg_bin_geometry(const CgBlockInput* t, CgBinGeom* g) {
   if (!t) return CG_EARG;
   if (t->B <= 0 || t->C < 2 || t->T <= 0 || t->V < 2) return CG_ESHAPE;
@@ -296,7 +280,7 @@ static int cg_bin_geometry(const CgBlockInput* t, CgBinGeom* g) {
   if (g->NPL > t->C) g->NPL = t->C;
   g->cps = (t->C + g->NPL - 1) / g->NPL;
   g->L = g->NPL * g->TV;
-  g->magicTV = cg_bin_magic(g->TV); g->magicV = cg_bin_magic(t->V);
+  g->magicTV = cg_div_magic(g->TV); g->magicV = cg_div_magic(t->V);
   if ((long long)t->B * g->cps > 2147483647LL) return CG_ESHAPE;
   return CG_OK;
 }

@@ -1,6 +1,6 @@
 // Argument block of the block mid-section kernels (block_mid.hip); mirrored by include/cistgcn_hip.h and cistgcn_amd/_lib.py.
 #pragma once
-#include "dstd_tail.h"        // CgTailBN
+#include "cg_bn.h"            // CgTailBN
 
 // Middle of a DSTD_GC block, between the collapsing convolutions and the fused tails (gate_head.hip, map2adj_tail.hip).  Up to six items,
 // each  x (B,C,L) -> BatchNorm2d over C -> Dropout [-> PReLU] -> a bias-free map:

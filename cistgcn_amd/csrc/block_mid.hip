@@ -33,31 +33,24 @@ static inline int cg_mid_sb(int kind, int C, int L, int O) {
 }
 
 // BatchNorm constants of channel c: {mean, rstd, gamma * rstd, beta}.  Forward, train: from the producer's replicated f64 sums (the owner
-// records save / running statistics exactly like nn.BatchNorm, as cg_tail_aff); eval: running statistics; backward: the saved pair.
+// records save / running statistics, cg_bn_record); eval: running statistics; backward: the saved pair.
 __device__ __forceinline__ void cg_mid_aff(const CgMidItem& it, int c, double cnt, int train, bool backward, bool owner, float* k) {
   const CgTailBN& bn = it.bn;
   const int C = it.C;
   float mean, rstd;
   if (backward) { mean = bn.save[c]; rstd = bn.save[C + c]; }
   else if (train) {
-    double s1 = 0.0, s2 = 0.0;
-    for (int r = 0; r < CG_STAT_REPLICAS; ++r) { s1 += bn.stats[((long long)r * it.stats_ld + c) * 2]; s2 += bn.stats[((long long)r * it.stats_ld + c) * 2 + 1]; }
-    const double m = s1 / cnt;
-    double var = s2 / cnt - m * m;
-    if (var < 0.0) var = 0.0;
+    double s1, s2, m, var;
+    cg_bn_sums(bn.stats, it.stats_ld, c, s1, s2);
+    cg_bn_moments(s1, s2, cnt, m, var);
     mean = (float)m;
-    rstd = (float)(1.0 / sqrt(var + (double)bn.eps));
-    if (owner && bn.running_mean) {
-      const double unb = cnt > 1.0 ? var * cnt / (cnt - 1.0) : var;
-      bn.running_mean[c] = (1.f - bn.momentum) * bn.running_mean[c] + bn.momentum * (float)m;
-      bn.running_var[c] = (1.f - bn.momentum) * bn.running_var[c] + bn.momentum * (float)unb;
-      if (c == 0 && bn.num_batches_tracked) *bn.num_batches_tracked += 1;
-    }
+    rstd = cg_bn_rstd(var, bn.eps);
+    if (owner) cg_bn_record(bn, c, C, mean, rstd, var, cnt);
   } else {
     mean = bn.running_mean[c];
-    rstd = 1.0f / sqrtf(bn.running_var[c] + bn.eps);
+    rstd = cg_bn_rstd_eval(bn.running_var[c], bn.eps);
+    if (owner) cg_bn_save(bn, c, C, mean, rstd);
   }
-  if (!backward && owner) { bn.save[c] = mean; bn.save[C + c] = rstd; }
   k[0] = mean; k[1] = rstd; k[2] = bn.gamma[c] * rstd; k[3] = bn.beta[c];
 }
 

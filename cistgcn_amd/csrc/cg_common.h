@@ -1,4 +1,6 @@
-// Shared device helpers for the CIST-GCN gfx950 kernels.
+// Included by every source of the kernel library: status codes, launcher limits, and the small device helpers more than one file
+// needs - wave / block reductions, row-of-16 DPP exchange, fixed-width vector load / store, division by a run-time constant, the
+// dropout hash.  (BatchNorm constants: cg_bn.h; fragment reads of the phase kernels: cg_phase.h.)
 // Wavefront = 64 lanes (CDNA4); every reduction below is written for that width.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -20,7 +22,7 @@
 
 // BatchNorm channel sums are accumulated with f64 atomics by every workgroup of the producing kernel; with
 // thousands of workgroups per channel one address serialises (~tens of microseconds).  Producers therefore add
-// into replica (block id mod CG_STAT_REPLICAS) of a [CG_STAT_REPLICAS][C][2] buffer, the consumer sums the replicas.
+// into replica (block id mod CG_STAT_REPLICAS) of a [CG_STAT_REPLICAS][C][2] buffer, the consumer sums the replicas (cg_bn_sums, cg_bn.h).
 #define CG_STAT_REPLICAS 16
 
 // 4-D strided view: dims n[0..3] (n[0] = batch rows, n[1] = channel), element strides s[0..3].
@@ -76,11 +78,32 @@ static inline int cg_launch_status() {
 }
 
 // ---- wave / block reductions -------------------------------------------------------------------
+// sum over the wavefront, result valid in lane 0
 template <typename T>
 __device__ __forceinline__ T cg_wave_sum(T v) {
 #pragma unroll
   for (int off = CG_WAVE / 2; off > 0; off >>= 1) v += __shfl_down(v, off, CG_WAVE);
   return v;
+}
+// maximum over the wavefront in every lane, T = float or double (a butterfly: every lane combines the same pairs)
+template <typename T>
+__device__ __forceinline__ T cg_wave_allmax(T v) {
+#pragma unroll
+  for (int off = CG_WAVE / 2; off > 0; off >>= 1) {
+    if constexpr (sizeof(T) == sizeof(float)) v = fmaxf(v, __shfl_xor(v, off, CG_WAVE));
+    else v = fmax(v, __shfl_xor(v, off, CG_WAVE));
+  }
+  return v;
+}
+// sum over the wavefront of N values at once, result in every lane (the same butterfly, so all lanes hold the same bits); the N
+// exchanges of a level are independent
+template <int N>
+__device__ __forceinline__ void cg_wave_allsum(double (&v)[N]) {
+#pragma unroll
+  for (int off = CG_WAVE / 2; off > 0; off >>= 1) {
+#pragma unroll
+    for (int i = 0; i < N; ++i) v[i] += __shfl_xor(v[i], off, CG_WAVE);
+  }
 }
 
 // Sum over the whole workgroup; result valid in thread 0. `scratch` holds >= 16 T's in LDS.
@@ -100,18 +123,30 @@ __device__ __forceinline__ T cg_block_sum(T v, T* scratch) {
   return r;
 }
 
-// ---- counter-based RNG for dropout: splitmix64 of (seed, site salt, element index) ---------------
-__device__ __forceinline__ uint32_t cg_rand_u32(unsigned long long seed, unsigned int salt, unsigned long long idx) {
-  unsigned long long z = idx + seed * 0x9E3779B97F4A7C15ull + ((unsigned long long)salt << 40) + 0x632BE59BD9B4E019ull;
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  z = z ^ (z >> 31);
-  return (uint32_t)(z >> 32);
+// ---- VW consecutive floats (VW = 1, 2, 4; 4 * VW bytes aligned) memory <-> registers, unconditional ----------------
+template <int VW>
+__device__ __forceinline__ void cg_ldv(const float* p, float* v) {
+  if constexpr (VW == 4) { const float4 t = *reinterpret_cast<const float4*>(p); v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w; }
+  else if constexpr (VW == 2) { const float2 t = *reinterpret_cast<const float2*>(p); v[0] = t.x; v[1] = t.y; }
+  else v[0] = *p;
+}
+template <int VW>
+__device__ __forceinline__ void cg_stv(float* p, const float* v) {
+  if constexpr (VW == 4) *reinterpret_cast<float4*>(p) = make_float4(v[0], v[1], v[2], v[3]);
+  else if constexpr (VW == 2) *reinterpret_cast<float2*>(p) = make_float2(v[0], v[1]);
+  else *p = v[0];
 }
 
-// Dropout keep-scale: 0 (dropped) or 1/(1-p).  One 64-bit hash serves four consecutive elements (16 bits each), so
-// the vectorised row kernels draw once per float4; the scalar path derives the same bits from (idx >> 2, idx & 3).
-// The drop probability is therefore quantised to 1/65536.
+// ---- n / d for a divisor known on the host, without the ~40-instruction 32-bit division -----------------------------
+// magic = ceil(2^32 / d) (0 stands for d = 1), quotient = (n * magic) >> 32.  Exact while n * d < 2^32:
+// magic * d = 2^32 + e with 0 <= e < d, so n * magic / 2^32 = n / d + n * e / (d * 2^32); the fractional part of n / d is at most
+// (d - 1) / d, the floor is therefore the quotient as long as n * e / (d * 2^32) < 1 / d, i.e. n * e < 2^32 - and e < d.
+// Every launcher that hands a magic number to a kernel bounds n and d by its geometry limits (DESIGN.md section 4 lists them).
+static inline unsigned cg_div_magic(int d) { return d > 1 ? (unsigned)((0x100000000ULL + d - 1) / d) : 0u; }
+__device__ __forceinline__ unsigned cg_div(unsigned n, unsigned magic) { return magic ? (unsigned)(((unsigned long long)n * magic) >> 32) : n; }
+// the same without the d = 1 case, for divisors the launcher guarantees to be >= 2 (magic != 0): no select in a streaming loop
+__device__ __forceinline__ unsigned cg_div_ge2(unsigned n, unsigned magic) { return (unsigned)(((unsigned long long)n * magic) >> 32); }
+
 // ---- lane exchange inside a row of 16 lanes on the VALU (DPP), no LDS round trip -----------------------------------------------
 // CTRL: 0x100 + n row_shl (lane i takes lane i + n), 0x110 + n row_shr (lane i takes lane i - n), 0x120 + n row_ror (rotation).
 // A lane whose source falls outside its row keeps `old`.
@@ -149,6 +184,10 @@ __device__ __forceinline__ double cg_alpha_sum(const double* slots) {
   return s;
 }
 
+// ---- counter-based RNG for dropout: splitmix64 of (seed, site salt, index of a quad of elements) ---------------
+// Dropout keep-scale: 0 (dropped) or 1/(1-p).  One 64-bit hash serves four consecutive elements (16 bits each), so
+// the vectorised row kernels draw once per float4; the scalar path derives the same bits from (idx >> 2, idx & 3).
+// The drop probability is therefore quantised to 1/65536.
 __device__ __forceinline__ unsigned long long cg_drop_bits(unsigned long long seed, unsigned int salt, unsigned long long quad) {
   unsigned long long z = quad + seed * 0x9E3779B97F4A7C15ull + ((unsigned long long)salt << 40) + 0x632BE59BD9B4E019ull;
   z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;

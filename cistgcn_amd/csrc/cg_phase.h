@@ -1,48 +1,11 @@
-// Helpers shared by the phase kernels (dstd_tail.hip, map2adj_tail.hip): BatchNorm constants of a chain, PReLU, matrix-core
-// fragment reads.
+// Helpers of the kernels that walk (B,C,T,V) tensors in phases or tiles - dstd_tail.hip, map2adj_tail.hip, block_input.hip,
+// collapse_rows.hip, tower_maps.hip, fpn_conv.hip, gate_head.hip, block_mid.hip: the BatchNorm constants of a chain (cg_bn.h),
+// matrix-core fragment reads, the dropout factors of a quad.
 #pragma once
 #include "cg_common.h"
-#include "dstd_tail.h"
+#include "cg_bn.h"
 
 typedef float cg_f32x4 __attribute__((vector_size(16)));
-
-// ---- per-channel constants -------------------------------------------------------------------------------------------
-struct CgAff { float mean, rstd, gamma, beta; };
-
-// train: batch statistics from the replicated f64 sums (and, by the block that owns channel bookkeeping, save + running
-// statistics exactly like nn.BatchNorm); eval: running statistics.  backward: the saved pair.
-static __device__ __forceinline__ CgAff cg_tail_aff(const CgTailBN& bn, int c, int C, double cnt, int train, bool backward, bool owner) {
-  CgAff a;
-  a.gamma = bn.gamma[c]; a.beta = bn.beta[c];
-  if (backward) { a.mean = bn.save[c]; a.rstd = bn.save[C + c]; return a; }
-  if (train) {
-    double s1 = 0.0, s2 = 0.0;
-    for (int r = 0; r < CG_STAT_REPLICAS; ++r) { s1 += bn.stats[((long long)r * C + c) * 2]; s2 += bn.stats[((long long)r * C + c) * 2 + 1]; }
-    const double mean = s1 / cnt;
-    double var = s2 / cnt - mean * mean;
-    if (var < 0.0) var = 0.0;
-    a.mean = (float)mean;
-    a.rstd = (float)(1.0 / sqrt(var + (double)bn.eps));
-    if (owner) {
-      bn.save[c] = a.mean; bn.save[C + c] = a.rstd;
-      if (bn.running_mean) {
-        const double unb = cnt > 1.0 ? var * cnt / (cnt - 1.0) : var;
-        bn.running_mean[c] = (1.f - bn.momentum) * bn.running_mean[c] + bn.momentum * (float)mean;
-        bn.running_var[c] = (1.f - bn.momentum) * bn.running_var[c] + bn.momentum * (float)unb;
-        if (c == 0 && bn.num_batches_tracked) *bn.num_batches_tracked += 1;
-      }
-    }
-  } else {
-    a.mean = bn.running_mean[c];
-    a.rstd = 1.0f / sqrtf(bn.running_var[c] + bn.eps);
-    if (owner) { bn.save[c] = a.mean; bn.save[C + c] = a.rstd; }
-  }
-  return a;
-}
-
-static __device__ __forceinline__ float cg_bn(const CgAff& a, float v) { return (v - a.mean) * (a.gamma * a.rstd) + a.beta; }
-static __device__ __forceinline__ float cg_prelu(float u, float alpha) { return u > 0.f ? u : alpha * u; }
-
 
 // ======================================================================================================================
 // matrix-core helpers (same fragment scheme as stgcn_domain_mfma.hip: inside a 16-wide k chunk step s takes k = 4*slot + s)

@@ -1,6 +1,6 @@
 // Argument block of the frame-collapsing convolution (collapse_rows.hip); mirrored by include/cistgcn_hip.h and cistgcn_amd/_lib.py.
 #pragma once
-#include "dstd_tail.h"        // CgTailBN
+#include "cg_bn.h"            // CgTailBN
 
 // y[b,o,v] = sum_{c,t} W[o,c,t] x[b,c,t,v]: nn.Conv2d(C, O, (T, 1)) without bias.  x (B,C,T,V) contiguous, W (O, C*T), y (B,O,V);
 // V <= 32, O <= 64, C*T % 4 == 0.

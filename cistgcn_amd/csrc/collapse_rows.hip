@@ -73,7 +73,7 @@ __global__ __launch_bounds__(CG_ROWS_FWD_THREADS) void cg_rows_fwd_kernel(CgRows
     if (tr) {                                               // PReLU(BatchNorm(x)) of the four rows k = (c, t) of this lane, constants of channel c from LDS
 #pragma unroll
       for (int s = 0; s < 4; ++s) {
-        const int c = (int)(magicT ? (unsigned)(((unsigned long long)(unsigned)(f.kc + s) * magicT) >> 32) : (unsigned)(f.kc + s));
+        const int c = (int)cg_div((unsigned)(f.kc + s), magicT);
         const float4 k4 = *reinterpret_cast<const float4*>(sTab + 4 * c);
         f.x0[s] = cg_prelu((f.x0[s] - k4.x) * k4.y + k4.z, in_alpha);
         f.x1[s] = cg_prelu((f.x1[s] - k4.x) * k4.y + k4.z, in_alpha);
@@ -161,7 +161,8 @@ __device__ __forceinline__ void cg_rows_put_dw(float* sT, const cg_f32x4 (&wacc)
   }
 }
 
-// VW consecutive floats (VW * 4 bytes aligned) global <-> registers, no condition: the callers clamp the address
+// VW consecutive floats (VW * 4 bytes aligned) global <-> registers, no condition: the callers clamp the address.  Not cg_ldv / cg_stv of
+// cg_common.h: through their float4 form cg_rows_bwd_kernel<4, false> takes 120 VGPRs instead of 116 (profiles/device_helpers_isa.txt).
 template <int VW>
 __device__ __forceinline__ void cg_rows_ldv(const float* __restrict__ p, float* v) {
   if constexpr (VW == 4) {
@@ -466,8 +467,6 @@ __global__ __launch_bounds__(CG_ROWS_BWD_THREADS) void cg_rows_fold_kernel(CgRow
 //   backward  a workgroup owns 64 rows k for a slice of the samples (dx[b,k,t] from W^T dy, dW[o,k] in registers over the slice)
 // T <= 64 (NT tiles of 16 frames), O <= 64, C * V % 4 == 0.
 // ======================================================================================================================
-__device__ __forceinline__ unsigned cg_cols_div(unsigned n, unsigned magic) { return magic ? (unsigned)(((unsigned long long)n * magic) >> 32) : n; }
-
 template <int OT, int NT>
 __global__ __launch_bounds__(CG_ROWS_FWD_THREADS) void cg_cols_fwd_kernel(CgRowsArgs a, unsigned magicV) {
   const CgRowsConv& t = a.t; const CgRowsGeom& g = a.g;
@@ -509,7 +508,7 @@ __global__ __launch_bounds__(CG_ROWS_FWD_THREADS) void cg_cols_fwd_kernel(CgRows
     for (int i = 0; i < OT; ++i) f.w[i] = *reinterpret_cast<const float4*>(wrow[i] + kc);
 #pragma unroll
     for (int s = 0; s < 4; ++s) {
-      const int kk = kc + s, c = (int)cg_cols_div((unsigned)kk, magicV), v = kk - c * V;
+      const int kk = kc + s, c = (int)cg_div((unsigned)kk, magicV), v = kk - c * V;
       const float* xr = xb + c * TV + v;
 #pragma unroll
       for (int j = 0; j < NT; ++j) f.x[j][s] = xr[toff[j]];
@@ -519,7 +518,7 @@ __global__ __launch_bounds__(CG_ROWS_FWD_THREADS) void cg_cols_fwd_kernel(CgRows
     if (tr) {                                               // PReLU(BatchNorm(x)) of the rows k = (c, v) of this lane
 #pragma unroll
       for (int s = 0; s < 4; ++s) {
-        const int c = (int)cg_cols_div((unsigned)(f.kc + s), magicV);
+        const int c = (int)cg_div((unsigned)(f.kc + s), magicV);
         const float4 k4 = *reinterpret_cast<const float4*>(sTab + 4 * c);
 #pragma unroll
         for (int j = 0; j < NT; ++j) f.x[j][s] = cg_prelu((f.x[j][s] - k4.x) * k4.y + k4.z, in_alpha);
@@ -638,7 +637,7 @@ __global__ __launch_bounds__(CG_ROWS_BWD_THREADS, (SUMS && OT <= 2) ? 2 : 1) voi
   for (int i = 0; i < OT; ++i) wacc[i] = cg_f32x4{0.f, 0.f, 0.f, 0.f};
   const int kw = k0 + 16 * wave;
   // row k = (c, v) of this lane as the B operand of the dW product (x[b][c][t][v], t = 16 tt + 4 slot + s), clamped: rows k >= K are never stored
-  const int kl = min(kw + l15, K - 1), cl = (int)cg_cols_div((unsigned)kl, magicV);
+  const int kl = min(kw + l15, K - 1), cl = (int)cg_div((unsigned)kl, magicV);
   const int xoff = cl * TV + (kl - cl * V);
   int tx[NT][4];
 #pragma unroll
@@ -649,7 +648,7 @@ __global__ __launch_bounds__(CG_ROWS_BWD_THREADS, (SUMS && OT <= 2) ? 2 : 1) voi
   int doff[4]; bool dok[4];
 #pragma unroll
   for (int q = 0; q < 4; ++q) {
-    const int k = kw + 4 * slot + q, kc = min(k, K - 1), c = (int)cg_cols_div((unsigned)kc, magicV);
+    const int k = kw + 4 * slot + q, kc = min(k, K - 1), c = (int)cg_div((unsigned)kc, magicV);
     doff[q] = c * TV + (kc - c * V); dok[q] = k < K;
   }
   auto load_x = [&](int b, float xv[NT][4]) {
@@ -758,7 +757,7 @@ static int cg_rows_geometry(const CgRowsConv* t, CgRowsGeom* g) {
   if (!t || !t->x || !t->W) return CG_EARG;
   if (t->B <= 0 || t->C <= 0 || t->T <= 0 || t->V <= 0 || t->V > 32 || t->O <= 0 || t->O > 64) return CG_ESHAPE;
   const long long K = (long long)t->C * t->T;
-  if (K > (1 << 20) || (K & 3)) return CG_ESHAPE;
+  if (K > (1 << 20) || (K & 3) || K * t->T >= (1ll << 32)) return CG_ESHAPE;      // K * T: the channel of row k = (c, t) is cg_div(k, T)
   g->K = (int)K; g->OT = (t->O + 15) / 16;
   g->kranges = (g->K + CG_ROWS_KB - 1) / CG_ROWS_KB;
   int slices = 768 / g->kranges;                        // ~768 backward workgroups (1024-1536: 53 us against 46 us on the tower tensors, round 4)
@@ -804,7 +803,7 @@ extern "C" int cg_collapse_rows_fwd(const CgRowsConv* t, void* stream_) {
   const size_t lds = ((size_t)(CG_ROWS_FWD_THREADS / 64) * 16 * a.g.OT * 33 + (size_t)4 * t->C) * sizeof(float);
   const dim3 grid((unsigned)t->B), block(CG_ROWS_FWD_THREADS);
   hipStream_t stream = (hipStream_t)stream_;
-  const unsigned magicT = t->T > 1 ? (unsigned)((0x100000000ULL + t->T - 1) / t->T) : 0u;
+  const unsigned magicT = cg_div_magic(t->T);
 #define CG_ROWS_FWD_LAUNCH(N)                                                                   \
   {                                                                                            \
     hipError_t e = cg_lds_limit((const void*)cg_rows_fwd_kernel<N>, lds);                       \
@@ -848,12 +847,11 @@ extern "C" int cg_collapse_rows_bwd(const CgRowsConv* t, void* stream_) {
 }
 
 // ---- joint axis ----
-static unsigned cg_cols_magic(int d) { return d > 1 ? (unsigned)((0x100000000ULL + d - 1) / d) : 0u; }
 static int cg_cols_geometry(const CgRowsConv* t, CgRowsGeom* g) {
   if (!t || !t->x || !t->W) return CG_EARG;
   if (t->B <= 0 || t->C <= 0 || t->T <= 0 || t->V <= 0 || t->T > 64 || t->O <= 0 || t->O > 64) return CG_ESHAPE;
   const long long K = (long long)t->C * t->V;
-  if (K > (1 << 20) || (K & 3) || K * t->T >= (1ll << 31)) return CG_ESHAPE;
+  if (K > (1 << 20) || (K & 3) || K * t->T >= (1ll << 31) || K * t->V >= (1ll << 32)) return CG_ESHAPE;      // K * V: cg_div(k, V)
   g->K = (int)K; g->OT = (t->O + 15) / 16;
   g->kranges = (g->K + CG_ROWS_KB - 1) / CG_ROWS_KB;
   int slices = 768 / g->kranges;
@@ -901,7 +899,7 @@ extern "C" int cg_collapse_cols_fwd(const CgRowsConv* t, void* stream_) {
   const size_t lds = ((size_t)(CG_ROWS_FWD_THREADS / 64) * 16 * a.g.OT * (16 * nt + 1) + (size_t)4 * t->C + 4) * sizeof(float);
   const dim3 grid((unsigned)t->B), block(CG_ROWS_FWD_THREADS);
   hipStream_t stream = (hipStream_t)stream_;
-  const unsigned magic = cg_cols_magic(t->V);
+  const unsigned magic = cg_div_magic(t->V);
 #define CG_COLS_FWD_LAUNCH(N, M)                                                                \
   {                                                                                            \
     hipError_t e = cg_lds_limit((const void*)cg_cols_fwd_kernel<N, M>, lds);                    \
@@ -927,7 +925,7 @@ extern "C" int cg_collapse_cols_bwd(const CgRowsConv* t, void* stream_) {
                       (sums ? (size_t)(CG_ROWS_BWD_THREADS / 64) * 16 * (16 * nt + 4) : 0)) * sizeof(float);
   const dim3 grid((unsigned)a.g.kranges, (unsigned)a.g.slices), block(CG_ROWS_BWD_THREADS);
   hipStream_t stream = (hipStream_t)stream_;
-  const unsigned magic = cg_cols_magic(t->V);
+  const unsigned magic = cg_div_magic(t->V);
 #define CG_COLS_BWD_LAUNCH_S(N, M, S)                                                           \
   {                                                                                            \
     hipError_t e = cg_lds_limit((const void*)cg_cols_bwd_kernel<N, M, S>, lds);                 \

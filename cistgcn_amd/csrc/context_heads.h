@@ -1,6 +1,6 @@
 // Argument block of the context-head kernels (context_heads.hip); mirrored by include/cistgcn_hip.h and cistgcn_amd/_lib.py.
 #pragma once
-#include "dstd_tail.h"        // CgTailBN
+#include "cg_bn.h"            // CgTailBN
 
 // ContextLayer heads 1 and 3 (reference CISTGCN.py:408-418 with :465 / :467):
 //   head 0: y[b,c] = max_p  PReLU(BN(w0[c] * x[b,p]))   (context_conv1, `.max(-1)[0].max(-1)[0]`, first arg-max)

@@ -21,8 +21,8 @@ HIP_DYNAMIC_SHARED(unsigned char, cg_dyn_lds)
 
 struct CgCtxChan { float w, m, r, s, beta, alpha; };      // s = gamma * r
 
-// constants of channel c of head h.  Forward, train mode: batch statistics derived from the moments of x; workgroup 0 records them
-// (save, running statistics exactly like nn.BatchNorm2d: unbiased variance into running_var).
+// constants of channel c of head h.  Forward, train mode: batch statistics derived from the moments of x (mean = w mean_x,
+// var = w^2 var_x); workgroup 0 records them (cg_bn_record).
 __device__ __forceinline__ CgCtxChan cg_ctx_chan(const CgCtxHeads& t, int h, int c, bool backward, float mean_x, float var_x, bool owner) {
   CgCtxChan k;
   const CgTailBN& bn = t.bn[h];
@@ -32,33 +32,23 @@ __device__ __forceinline__ CgCtxChan cg_ctx_chan(const CgCtxHeads& t, int h, int
   else if (t.train) {
     const double var = (double)k.w * (double)k.w * (double)var_x;
     k.m = k.w * mean_x;
-    k.r = (float)(1.0 / sqrt(var + (double)bn.eps));
-    if (owner) {
-      bn.save[c] = k.m; bn.save[t.C + c] = k.r;
-      if (bn.running_mean) {
-        const double cnt = (double)t.B * (double)t.P;
-        const double unb = cnt > 1.0 ? var * cnt / (cnt - 1.0) : var;
-        bn.running_mean[c] = (1.f - bn.momentum) * bn.running_mean[c] + bn.momentum * k.m;
-        bn.running_var[c] = (1.f - bn.momentum) * bn.running_var[c] + bn.momentum * (float)unb;
-        if (c == 0 && bn.num_batches_tracked) *bn.num_batches_tracked += 1;
-      }
-    }
+    k.r = cg_bn_rstd(var, bn.eps);
+    if (owner) cg_bn_record(bn, c, t.C, k.m, k.r, var, (double)t.B * (double)t.P);
   } else {
     k.m = bn.running_mean[c];
-    k.r = 1.0f / sqrtf(bn.running_var[c] + bn.eps);
-    if (owner) { bn.save[c] = k.m; bn.save[t.C + c] = k.r; }
+    k.r = cg_bn_rstd_eval(bn.running_var[c], bn.eps);
+    if (owner) cg_bn_save(bn, c, t.C, k.m, k.r);
   }
   k.s = gamma * k.r;
   return k;
 }
 __device__ __forceinline__ float cg_ctx_u(const CgCtxChan& k, float x) { return (k.w * x - k.m) * k.s + k.beta; }      // mean first, as nn.BatchNorm
 
+// moments of the one-channel input x: the sums of a [CG_STAT_REPLICAS][1][2] buffer
 __device__ __forceinline__ void cg_ctx_moments(const CgCtxHeads& t, float& mean_x, float& var_x) {
-  double s1 = 0.0, s2 = 0.0;
-  for (int r = 0; r < CG_STAT_REPLICAS; ++r) { s1 += t.xstats[2 * r]; s2 += t.xstats[2 * r + 1]; }
-  const double cnt = (double)t.B * (double)t.P, mean = s1 / cnt;
-  double var = s2 / cnt - mean * mean;
-  if (var < 0.0) var = 0.0;
+  double s1, s2, mean, var;
+  cg_bn_sums(t.xstats, 1, 0, s1, s2);
+  cg_bn_moments(s1, s2, (double)t.B * (double)t.P, mean, var);
   mean_x = (float)mean; var_x = (float)var;
 }
 

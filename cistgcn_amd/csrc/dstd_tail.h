@@ -1,18 +1,8 @@
 // Argument block of the DSTD_GC tail kernels (dstd_tail.hip); mirrored by include/cistgcn_hip.h and cistgcn_amd/_lib.py.
 #pragma once
+#include "cg_bn.h"           // CgTailBN
 
 #define CG_TAIL_MAXW 8       // dWc register tiles per wave: (C/16) * (2C/16) / 4 waves, C <= 64
-
-// one BatchNorm of the chain.  `stats`: replicated f64 {sum, sum of squares} of ITS INPUT over batch and positions
-// ([CG_STAT_REPLICAS][C][2], zero before the producing phase; train mode only).  `save`: [2][C] mean / rstd actually used
-// by the forward (written by the first phase that needs them, read by the later phases and the backward).
-struct CgTailBN {
-  double* stats;
-  const float* gamma; const float* beta;
-  float* running_mean; float* running_var; long long* num_batches_tracked;
-  float momentum, eps;
-  float* save;
-};
 
 struct CgDstdTail {
   int B, C, T, V, train, pad0;

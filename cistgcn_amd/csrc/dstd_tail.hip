@@ -1210,8 +1210,8 @@ __global__ void cg_tail_k45_kernel(CgDstdTail t, int rb) {
       for (int r = 0; r < CG_STAT_REPLICAS; ++r)
 #pragma unroll
         for (int k = 0; k < CG_TAIL_FMOM; ++k) M[k] += t.fmom[i][((long long)r * C + c) * CG_TAIL_FMOM + k];
-      double A1 = 0.0, B1 = 0.0;
-      for (int r = 0; r < CG_STAT_REPLICAS; ++r) { A1 += t.red_q[i][((long long)r * C + c) * 2]; B1 += t.red_q[i][((long long)r * C + c) * 2 + 1]; }
+      double A1, B1;
+      cg_bn_sums(t.red_q[i], C, c, A1, B1);
       B1 *= (double)at[d].rstd;
       const double mp = (double)ap[d].mean, rp = (double)ap[d].rstd;
       const double A3 = rp * (M[1] - mp * M[0]), B3 = rp * (M[3] - mp * M[2]);

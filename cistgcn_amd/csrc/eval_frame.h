@@ -5,23 +5,6 @@
 
 #include <math.h>
 
-// sum over the wavefront of N values at once, result in every lane (a butterfly: every lane adds the same pairs, so all lanes hold
-// the same bits); the N exchanges of a level are independent
-template <int N>
-__device__ __forceinline__ void cg_em_wave_sum(double (&v)[N]) {
-#pragma unroll
-  for (int off = CG_WAVE / 2; off > 0; off >>= 1) {
-#pragma unroll
-    for (int i = 0; i < N; ++i) v[i] += __shfl_xor(v[i], off, CG_WAVE);
-  }
-}
-
-__device__ __forceinline__ float cg_em_wave_max(float v) {
-#pragma unroll
-  for (int off = CG_WAVE / 2; off > 0; off >>= 1) v = fmaxf(v, __shfl_xor(v, off, CG_WAVE));
-  return v;
-}
-
 // ---------------------------------------------------------------------------------------------
 // 3x3 Procrustes rotation.  H = U diag(s) V^T; the reference forms R = V' U^T with the last ROW of V scaled by sigma = sign det(V U^T)
 // (losses.py:106-119), i.e. R = diag(1,1,sigma) V U^T, and V U^T is the transposed polar factor of H: it does not depend on the signs
@@ -118,7 +101,7 @@ __device__ __forceinline__ void cg_em_frame_errors(const double (&P)[3], const d
 
   // sums over the joints, first round: centroids and the two means of n_mpjpe (lanes past J hold zeros)
   double r1[8] = {X[0], X[1], X[2], P[0], P[1], P[2], X[0] * P[0] + X[1] * P[1] + X[2] * P[2], P[0] * P[0] + P[1] * P[1] + P[2] * P[2]};
-  cg_em_wave_sum(r1);
+  cg_wave_allsum(r1);
   const double scale = (r1[6] / J) / (r1[7] / J);
   en = cg_em_norm3(scale * P[0] - X[0], scale * P[1] - X[1], scale * P[2] - X[2]);
 
@@ -139,7 +122,7 @@ __device__ __forceinline__ void cg_em_frame_errors(const double (&P)[3], const d
     for (int j = 0; j < 3; ++j) r2[3 * i + j] = X0[i] * Y0[j];
   r2[9] = X0[0] * X0[0] + X0[1] * X0[1] + X0[2] * X0[2];
   r2[10] = Y0[0] * Y0[0] + Y0[1] * Y0[1] + Y0[2] * Y0[2];
-  cg_em_wave_sum(r2);
+  cg_wave_allsum(r2);
   const double normX = fmax(sqrt(r2[9]), 1e-3), normY = sqrt(r2[10]);
   double H[3][3], R[3][3], sv[3];
 #pragma unroll

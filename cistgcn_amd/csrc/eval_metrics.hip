@@ -52,7 +52,7 @@ __global__ __launch_bounds__(CG_EM_PRE_THREADS) void cg_em_batch_max_kernel(cons
     double m = -INFINITY;
     for (int b = wave; b < B; b += CG_EM_PRE_WAVES) {       // wave-uniform trip count: the shuffle below has all 64 lanes
       const float s = lane < J ? speeds[((long long)b * To + t) * J + lane] : -INFINITY;
-      const float mx = cg_em_wave_max(s);
+      const float mx = cg_wave_allmax(s);
       m = fmax(m, cg_em_sn(s, mx) + wt);
     }
     red[wave][lane] = m;
@@ -99,7 +99,7 @@ __global__ __launch_bounds__(CG_EM_THREADS) void cg_eval_metrics_kernel(CgEvalMe
     cg_em_frame_errors(P, X, on, J, e, en, epa);
 
     // the speed weights
-    const float smax = cg_em_wave_max(sp);
+    const float smax = cg_wave_allmax(sp);
     double wj = 0.0, wjt = 0.0;
     if (on) {
       const double sn = cg_em_sn(sp, smax);
@@ -126,7 +126,7 @@ __global__ __launch_bounds__(CG_EM_THREADS) void cg_eval_metrics_kernel(CgEvalMe
 
     if (a.frames) {
       double r3[CG_EM_SUMS] = {on ? e : 0.0, on ? epa : 0.0, on ? en : 0.0, mve, bsum, wj, wjt};
-      cg_em_wave_sum(r3);
+      cg_wave_allsum(r3);
       if (lane < CG_EM_SUMS) {
         double v = r3[0];
 #pragma unroll

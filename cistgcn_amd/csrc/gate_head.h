@@ -1,6 +1,6 @@
 // Argument block of the gate-head kernels (gate_head.hip); mirrored by include/cistgcn_hip.h and cistgcn_amd/_lib.py.
 #pragma once
-#include "dstd_tail.h"        // CgTailBN
+#include "cg_bn.h"            // CgTailBN
 
 // Tail of the two gate paths of a DSTD_GC block (reference CISTGCN.py:337-352 applied by :378-384), for path p in {s, t}:
 //   h2 = PReLU(Dropout(BN2d(z_p)))           z_p (B,C): output of the joint-collapsing convolution conv_p[4], BatchNorm conv_p[5] over the batch

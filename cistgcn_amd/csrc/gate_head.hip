@@ -24,28 +24,22 @@ HIP_DYNAMIC_SHARED(unsigned char, cg_dyn_lds)
 struct CgGateAff { float mean, rstd, scale, beta; };
 
 // BatchNorm constants of column c from the workgroup's own batch sums (train) or the running statistics (eval); thread c of wave 0
-// calls this (forward); the workgroup of the first chunk (`owner`) records save / running statistics exactly like nn.BatchNorm
+// calls this (forward); the workgroup of the first chunk (`owner`) records save / running statistics (cg_bn_record)
 __device__ __forceinline__ CgGateAff cg_gate_aff_fwd(const CgTailBN& bn, int c, int C, int B, int train, double s1, double s2, bool owner) {
   CgGateAff a;
   const float gamma = bn.gamma[c];
   a.beta = bn.beta[c];
   if (train) {
-    const double cnt = (double)B, mean = s1 / cnt;
-    double var = s2 / cnt - mean * mean;
-    if (var < 0.0) var = 0.0;
+    double mean, var;
+    cg_bn_moments(s1, s2, (double)B, mean, var);
     a.mean = (float)mean;
-    a.rstd = (float)(1.0 / sqrt(var + (double)bn.eps));
-    if (owner && bn.running_mean) {
-      const double unb = cnt > 1.0 ? var * cnt / (cnt - 1.0) : var;
-      bn.running_mean[c] = (1.f - bn.momentum) * bn.running_mean[c] + bn.momentum * (float)mean;
-      bn.running_var[c] = (1.f - bn.momentum) * bn.running_var[c] + bn.momentum * (float)unb;
-      if (c == 0 && bn.num_batches_tracked) *bn.num_batches_tracked += 1;
-    }
+    a.rstd = cg_bn_rstd(var, bn.eps);
+    if (owner) cg_bn_record(bn, c, C, a.mean, a.rstd, var, (double)B);
   } else {
     a.mean = bn.running_mean[c];
-    a.rstd = 1.0f / sqrtf(bn.running_var[c] + bn.eps);
+    a.rstd = cg_bn_rstd_eval(bn.running_var[c], bn.eps);
+    if (owner) cg_bn_save(bn, c, C, a.mean, a.rstd);
   }
-  if (owner) { bn.save[c] = a.mean; bn.save[C + c] = a.rstd; }
   a.scale = gamma * a.rstd;
   return a;
 }

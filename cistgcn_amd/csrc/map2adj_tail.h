@@ -1,6 +1,6 @@
 // Argument block of the Map2Adj tail kernels (map2adj_tail.hip); mirrored by include/cistgcn_hip.h and cistgcn_amd/_lib.py.
 #pragma once
-#include "dstd_tail.h"
+#include "cg_bn.h"            // CgTailBN
 
 #define CG_ADJ_MAXW 4        // weight-gradient register tiles per wave: (Kc/16)^2 / 4 waves, Kc <= 64
 

@@ -33,7 +33,6 @@ template <int KCM> struct CgAdjK {
 
 // geometry of a tower (host side, cg_adj_geometry): handed to the kernels next to the argument block
 __device__ __forceinline__ const CgAdjGeom& cg_adj_geom(const CgAdjTailPair& pr, int i) { return pr.g[i]; }
-__device__ __forceinline__ unsigned cg_adj_div(unsigned n, unsigned magic) { return magic ? (unsigned)(((unsigned long long)n * magic) >> 32) : n; }
 
 // Staging loops: the global loads of four strides are issued together, then their LDS stores.
 // S[k][a], Q[k][b'] of sample b: [KcM][JS] tables, rows >= Kc zero
@@ -47,7 +46,7 @@ __device__ __forceinline__ void cg_adj_tables(const CgAdjTail& t, const CgAdjGeo
     float sv[4], qv[4];
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
-      const int i = i0 + CG_ADJ_THREADS * j, k = (int)cg_adj_div((unsigned)i, g.magicJ), a = i - k * t.J;
+      const int i = i0 + CG_ADJ_THREADS * j, k = (int)cg_div((unsigned)i, g.magicJ), a = i - k * t.J;
       sv[j] = qv[j] = 0.f;
       if (i < KJ) {
         if (t.domain == 0) { sv[j] = sb[k * T + a]; qv[j] = qb[a * V + k]; }       // k = joint: S = s[v][t], Q = q[tau][v]
@@ -56,7 +55,7 @@ __device__ __forceinline__ void cg_adj_tables(const CgAdjTail& t, const CgAdjGeo
     }
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
-      const int i = i0 + CG_ADJ_THREADS * j, k = (int)cg_adj_div((unsigned)i, g.magicJ), a = i - k * t.J;
+      const int i = i0 + CG_ADJ_THREADS * j, k = (int)cg_div((unsigned)i, g.magicJ), a = i - k * t.J;
       if (i < KJ) { sS[k * g.JS + a] = sv[j]; sQ[k * g.JS + a] = qv[j]; }
     }
   }
@@ -75,12 +74,12 @@ __device__ __forceinline__ void cg_adj_weight(const float* __restrict__ W, const
     for (int j = 0; j < 4; ++j) { const int i = i0 + CG_ADJ_THREADS * j; v[j] = i < n ? W[i] : 0.f; }
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
-      const int i = i0 + CG_ADJ_THREADS * j, r = (int)cg_adj_div((unsigned)i, g.magicKc);
+      const int i = i0 + CG_ADJ_THREADS * j, r = (int)cg_div((unsigned)i, g.magicKc);
       if (i < n) sW[r * K::WS + i - r * t.Kc] = v[j];
     }
   }
   for (int i = threadIdx.x; i < t.Kc * padw; i += CG_ADJ_THREADS) {            // columns Kc .. WS - 1 of the rows < Kc
-    const int r = (int)cg_adj_div((unsigned)i, g.magicPad);
+    const int r = (int)cg_div((unsigned)i, g.magicPad);
     sW[r * K::WS + t.Kc + i - r * padw] = 0.f;
   }
   for (int e = t.Kc * K::WS + threadIdx.x; e < K::KcM * K::WS; e += CG_ADJ_THREADS) sW[e] = 0.f;
@@ -132,7 +131,7 @@ __device__ __forceinline__ void cg_adj_m1_body(const CgAdjTail& t, const CgAdjGe
   for (int w = wave; w < ngroups * MT; w += CG_ADJ_THREADS / 64) {       // (group of 32 positions, u tile)
     const int grp = w / MT, p0 = P0 + 32 * grp;
     const int pa = p0 + l15, pb = p0 + 16 + l15;
-    const int aa = (int)cg_adj_div((unsigned)pa, g.magicJ), ab = (int)cg_adj_div((unsigned)pb, g.magicJ);
+    const int aa = (int)cg_div((unsigned)pa, g.magicJ), ab = (int)cg_div((unsigned)pb, g.magicJ);
     const bool oka = pa < g.Pn, okb = pb < g.Pn;
     cg_f32x4 c0 = cg_f32x4{0.f, 0.f, 0.f, 0.f}, c1 = c0;
     for (int k0 = 0; k0 < K::KcM; k0 += 16) {
@@ -632,7 +631,7 @@ __device__ __forceinline__ void cg_adj_n2_body(const CgAdjTail& t, const CgAdjGe
     {
       constexpr int per_row = K::PT >> 4;
       const int k = tid / per_row, pp0 = 16 * (tid - k * per_row), p = p0 + pp0;
-      const int a = (int)cg_adj_div((unsigned)p, magicJ), bp = p - a * J;
+      const int a = (int)cg_div((unsigned)p, magicJ), bp = p - a * J;
       const float* srow = sS + k * JS; const float* qrow = sQ + k * JS;
       float* dst = sDO + k * K::PS + pp0;
       if (J >= 16) {
@@ -741,9 +740,9 @@ __device__ __forceinline__ void cg_adj_n2_body(const CgAdjTail& t, const CgAdjGe
     // Measured alternatives (profiles/r04_stamps.txt): LDS float atomics straight from the result registers (24 ds_add_f32 per wave and
     // tile: 25 000 cycles, against 6 000 for this pass); four lanes per dS cell with a DPP sum, register-resident dQ cells: no gain -
     // the pass is bound by the index arithmetic in front of each term, not by its LDS reads.
-    const int a0 = (int)cg_adj_div((unsigned)p0, magicJ), r0 = p0 - a0 * J;
+    const int a0 = (int)cg_div((unsigned)p0, magicJ), r0 = p0 - a0 * J;
     for (int cell = tid; cell < KJ; cell += CG_ADJ_THREADS) {
-      const int k = (int)cg_adj_div((unsigned)cell, magicJ), bq = cell - k * J;
+      const int k = (int)cg_div((unsigned)cell, magicJ), bq = cell - k * J;
       const float* img = sDO + k * K::PS; const float* srow = sS + k * JS + a0;
       float acc = 0.f;
       int m = bq < r0 ? 1 : 0;
@@ -757,7 +756,7 @@ __device__ __forceinline__ void cg_adj_n2_body(const CgAdjTail& t, const CgAdjGe
       // executed in order, the wave barrier keeps the compiler from merging the phases
       constexpr int per_row = K::PT >> 4;
       const int k = tid / per_row, sub = tid - k * per_row, pp0 = 16 * sub, p = p0 + pp0;
-      const int a = (int)cg_adj_div((unsigned)p, magicJ), bp = p - a * J;
+      const int a = (int)cg_div((unsigned)p, magicJ), bp = p - a * J;
       const float* img = sDO + k * K::PS + pp0; const float* qrow = sQ + k * JS;
       float s0 = 0.f, s1 = 0.f;
 #pragma unroll
@@ -799,7 +798,7 @@ __device__ __forceinline__ void cg_adj_n2_body(const CgAdjTail& t, const CgAdjGe
   // this chunk's share of dS / dQ: [b][chunk][2][Kc * J], summed over the chunks by cg_adj_finish_kernel
   float* part = t.part + ((long long)b * g.nch + ch) * 2 * KJ;
   for (int cell = tid; cell < KJ; cell += CG_ADJ_THREADS) {
-    const int k = (int)cg_adj_div((unsigned)cell, g.magicJ), a = cell - k * t.J;
+    const int k = (int)cg_div((unsigned)cell, g.magicJ), a = cell - k * t.J;
     part[cell] = sDS[k * g.JS + a];
     part[KJ + cell] = sDQ[k * g.JS + a];
   }
@@ -860,7 +859,6 @@ __global__ void cg_adj_finish_kernel(CgAdjTailPair pr) {
 }
 
 // ---- host side ---------------------------------------------------------------------------------------------------
-static unsigned cg_adj_magic(int d) { return d > 1 ? (unsigned)((0x100000000ULL + d - 1) / d) : 0u; }
 // tiles per workgroup: long workgroups amortise their prologue (weights, tables) when the batch alone fills the chip
 static int cg_adj_tpw(int B) { return B >= 128 ? CG_ADJ_TPW_MAX : B >= 64 ? 4 : B >= 32 ? 2 : 1; }
 // padded slab count of a tile: 16 / 32 / 64.  The staging code hands every thread 16 floats of a [KcM][PT] tile
@@ -879,7 +877,7 @@ static CgAdjGeom cg_adj_geometry(int B, int Kc, int J) {
   g.ntiles = (g.Pn + g.PT - 1) / g.PT;
   g.tpw = cg_adj_tpw(B);
   g.nch = (g.ntiles + g.tpw - 1) / g.tpw;
-  g.magicJ = cg_adj_magic(J); g.magicKc = cg_adj_magic(Kc); g.magicPad = cg_adj_magic(g.WS - Kc);
+  g.magicJ = cg_div_magic(J); g.magicKc = cg_div_magic(Kc); g.magicPad = cg_div_magic(g.WS - Kc);
   return g;
 }
 static int cg_adj_tile(int Kc) { const int KcM = cg_adj_kcm(Kc); return KcM > 32 ? 64 : KcM > 16 ? 128 : 256; }

@@ -9,6 +9,7 @@
 // nn.PReLU (shared or per-channel alpha) as used throughout CISTGCN.py (e.g. :138-153, :229-237,
 // :305-358), SELayer scale (SE.py:20,41).
 #include "cg_common.h"
+#include "cg_bn.h"
 
 // Row loop: p runs over the n2*n3 positions of one (batch, channel) row; (i2, i3) are derived once per
 // element with one 32-bit division and shared by every view of the kernel (all views have the same dims).
@@ -49,11 +50,11 @@ extern "C" int cg_norm_act_rows_per_block(const CgView4* xv) { return xv ? cg_ro
 // Vector width of the contiguous-row paths: 4 (rows 16-byte aligned, P % 4 == 0) or 2 (rows 8-byte aligned, P % 2 == 0: the
 // (T,V) planes of the 25-joint skeletons, P = 1250, and the (25, 66) planes of the output block).  The width is uniform per
 // problem; lanes j >= vw of a group are never used.
-__device__ __forceinline__ void cg_ldv(const float* p, int vw, float out[4]) {
+__device__ __forceinline__ void cg_row_ldv(const float* p, int vw, float out[4]) {
   if (vw == 4) { const float4 v = *reinterpret_cast<const float4*>(p); out[0] = v.x; out[1] = v.y; out[2] = v.z; out[3] = v.w; }
   else { const float2 v = *reinterpret_cast<const float2*>(p); out[0] = v.x; out[1] = v.y; out[2] = 0.f; out[3] = 0.f; }
 }
-__device__ __forceinline__ void cg_stv(float* p, int vw, const float v[4]) {
+__device__ __forceinline__ void cg_row_stv(float* p, int vw, const float v[4]) {
   if (vw == 4) *reinterpret_cast<float4*>(p) = make_float4(v[0], v[1], v[2], v[3]);
   else *reinterpret_cast<float2*>(p) = make_float2(v[0], v[1]);
 }
@@ -78,7 +79,7 @@ __global__ void cg_chan_stats_kernel(CgStatsBatch batch) {
       const int br = e / PV, p = vw * (e - br * PV), b = b0 + br;
       const float w = pre ? pre[(long long)b * xv.n[1] + c] : 1.f;
       float v[4];
-      cg_ldv(x + cg_row_base(xv, b, c) + p, vw, v);
+      cg_row_ldv(x + cg_row_base(xv, b, c) + p, vw, v);
 #pragma unroll
       for (int j = 0; j < 4; ++j) v[j] *= w;
       s += ((double)v[0] + (double)v[1]) + ((double)v[2] + (double)v[3]);
@@ -226,28 +227,18 @@ __device__ __forceinline__ CgChanAffine cg_chan_affine(const CgNormAct& a, int c
     r.mean = a.save_mean[c]; r.rstd = a.save_rstd[c];
   } else if (a.bn_mode == 1) {
     const double cnt = (double)a.xv.n[0] * (double)(a.xv.n[2] * a.xv.n[3]);
-    double s1 = 0.0, s2 = 0.0;
-    for (int r = 0; r < CG_STAT_REPLICAS; ++r) {      // replicated accumulators (cg_common.h)
-      s1 += a.stats[((long long)r * a.xv.n[1] + c) * 2];
-      s2 += a.stats[((long long)r * a.xv.n[1] + c) * 2 + 1];
-    }
-    const double mean = s1 / cnt;
-    double var = s2 / cnt - mean * mean;
-    if (var < 0.0) var = 0.0;
+    double s1, s2, mean, var;
+    cg_bn_sums(a.stats, a.xv.n[1], c, s1, s2);
+    cg_bn_moments(s1, s2, cnt, mean, var);
     r.mean = (float)mean;
-    r.rstd = (float)(1.0 / sqrt(var + (double)a.eps));
+    r.rstd = cg_bn_rstd(var, a.eps);
     if (blockIdx.y == 0 && threadIdx.x == 0) {
       a.save_mean[c] = r.mean; a.save_rstd[c] = r.rstd;
-      if (a.running_mean) {
-        const double unb = cnt > 1.0 ? var * cnt / (cnt - 1.0) : var;
-        a.running_mean[c] = (1.f - a.momentum) * a.running_mean[c] + a.momentum * (float)mean;
-        a.running_var[c] = (1.f - a.momentum) * a.running_var[c] + a.momentum * (float)unb;
-        if (c == 0 && a.num_batches_tracked) *a.num_batches_tracked += 1;
-      }
+      cg_bn_track(a.running_mean, a.running_var, a.num_batches_tracked, a.momentum, c, r.mean, var, cnt);
     }
   } else {
     r.mean = a.running_mean[c];
-    r.rstd = 1.0f / sqrtf(a.running_var[c] + a.eps);
+    r.rstd = cg_bn_rstd_eval(a.running_var[c], a.eps);
     if (blockIdx.y == 0 && threadIdx.x == 0) { a.save_mean[c] = r.mean; a.save_rstd[c] = r.rstd; }
   }
   r.scale = a.gamma[c] * r.rstd;
@@ -284,14 +275,14 @@ __global__ void cg_norm_act_fwd_kernel(CgNormActBatch batch) {
       const int br = e / PV, p = vw * (e - br * PV), b = b0 + br;
       const float w = a.pre ? a.pre[(long long)b * C + c] : 1.f;
       float xq[4], aq[4] = {0.f, 0.f, 0.f, 0.f}, yv[4];
-      cg_ldv(a.x + cg_row_base(a.xv, b, c) + p, vw, xq);
-      if (a.add) cg_ldv(a.add + cg_row_base(a.av, b, c) + p, vw, aq);
+      cg_row_ldv(a.x + cg_row_base(a.xv, b, c) + p, vw, xq);
+      if (a.add) cg_row_ldv(a.add + cg_row_base(a.av, b, c) + p, vw, aq);
       const unsigned long long idx = ((unsigned long long)b * C + c) * P + p;      // element index: its group of four shares 64 random bits
       const unsigned long long bits = drop ? cg_drop_bits(seed, a.salt, idx >> 2) : 0ull;
       const int j0 = (int)(idx & 3);
 #pragma unroll
       for (int j = 0; j < 4; ++j) yv[j] = j < vw ? cg_norm_act_y(a, af, alpha, xq[j], w, drop ? cg_drop_pick(bits, j0 + j, a.drop_p) : 1.f, aq[j]) : 0.f;
-      cg_stv(a.y + cg_row_base(a.yv, b, c) + p, vw, yv);
+      cg_row_stv(a.y + cg_row_base(a.yv, b, c) + p, vw, yv);
       if (a.ystats) {
         ys += ((double)yv[0] + (double)yv[1]) + ((double)yv[2] + (double)yv[3]);
         yq += ((double)yv[0] * (double)yv[0] + (double)yv[1] * (double)yv[1]) + ((double)yv[2] * (double)yv[2] + (double)yv[3] * (double)yv[3]);
@@ -345,11 +336,11 @@ struct CgNaQuad { float x[4], ad[4], g[4], keep[4]; float w; };
 __device__ __forceinline__ CgNaQuad cg_norm_act_quad(const CgNormAct& a, unsigned long long seed, int b, int c, long long C, int P, int p, int vw) {
   CgNaQuad q;
   q.w = a.pre ? a.pre[(long long)b * C + c] : 1.f;
-  cg_ldv(a.x + cg_row_base(a.xv, b, c) + p, vw, q.x);
-  cg_ldv(a.dy + cg_row_base(a.dyv, b, c) + p, vw, q.g);
+  cg_row_ldv(a.x + cg_row_base(a.xv, b, c) + p, vw, q.x);
+  cg_row_ldv(a.dy + cg_row_base(a.dyv, b, c) + p, vw, q.g);
 #pragma unroll
   for (int j = 0; j < 4; ++j) q.ad[j] = 0.f;
-  if (a.add && !a.add_post) cg_ldv(a.add + cg_row_base(a.av, b, c) + p, vw, q.ad);
+  if (a.add && !a.add_post) cg_row_ldv(a.add + cg_row_base(a.av, b, c) + p, vw, q.ad);
   if (a.drop_p > 0.f) {
     const unsigned long long idx = ((unsigned long long)b * C + c) * P + p;
     const unsigned long long bits = cg_drop_bits(seed, a.salt, idx >> 2);
@@ -450,8 +441,8 @@ __global__ void cg_norm_act_bwd_apply_kernel(CgNormActBatch batch) {
         dxq[j] = gv * q.w; daq[j] = gu;
         if (a.dpre) sp += (double)gv * (double)q.x[j];
       }
-      if (a.dx) cg_stv(a.dx + cg_row_base(a.dxv, b, c) + p, vw, dxq);
-      if (a.dadd) cg_stv(a.dadd + cg_row_base(a.dav, b, c) + p, vw, daq);
+      if (a.dx) cg_row_stv(a.dx + cg_row_base(a.dxv, b, c) + p, vw, dxq);
+      if (a.dadd) cg_row_stv(a.dadd + cg_row_base(a.dav, b, c) + p, vw, daq);
     }
   } else {
     CG_CHUNK_LOOP(nb, P, e) {
@@ -701,12 +692,12 @@ __global__ void cg_sum_many_kernel(CgSumArgs s) {
     float* yr = s.y + cg_row_base(s.yv, b, c);
     for (int p = vw * threadIdx.x; p < P; p += vw * blockDim.x) {
       float v[4], w[4];
-      cg_ldv(s.a[0] + cg_row_base(s.av[0], b, c) + p, vw, v);
+      cg_row_ldv(s.a[0] + cg_row_base(s.av[0], b, c) + p, vw, v);
       for (int i = 1; i < s.n; ++i) {
-        cg_ldv(s.a[i] + cg_row_base(s.av[i], b, c) + p, vw, w);
+        cg_row_ldv(s.a[i] + cg_row_base(s.av[i], b, c) + p, vw, w);
         v[0] += w[0]; v[1] += w[1]; v[2] += w[2]; v[3] += w[3];
       }
-      cg_stv(yr + p, vw, v);
+      cg_row_stv(yr + p, vw, v);
     }
     return;
   }

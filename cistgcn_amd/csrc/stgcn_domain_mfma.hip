@@ -29,10 +29,6 @@ HIP_DYNAMIC_SHARED(unsigned char, cg_dyn_lds)
 
 typedef float cg_f32x4 __attribute__((vector_size(16)));
 
-__device__ __forceinline__ unsigned cg_fastdiv(unsigned n, unsigned magic) {    // n / d for 2 <= d <= 64, n < 2^24; magic = ceil(2^32 / d), 0 for d = 1
-  return magic ? (unsigned)(((unsigned long long)n * magic) >> 32) : n;
-}
-
 // One operand fragment set for a 16-wide k chunk: v[s] is the lane's value for MFMA step s.
 //   KIND 0: image is [index][k] (k contiguous): p points at [index of this lane][4*slot]; one 16-byte read
 //   KIND 1: image is [k][index] (k strided by rs): p points at [4*slot][index of this lane]; four scalar reads
@@ -106,10 +102,10 @@ __device__ __forceinline__ void cg_domm_slots(const CgDomM& g, int C, int gof[CG
     const int e = threadIdx.x + i * CG_DOMM_THREADS;
     gof[i] = 0; lof[i] = 0;
     if (e < n) {
-      const int c = (int)cg_fastdiv((unsigned)e, g.magicRun), r = e - c * run;
+      const int c = (int)cg_div((unsigned)e, g.magicRun), r = e - c * run;
       int grp, j;
-      if (DOMAIN == 1) { grp = (int)cg_fastdiv((unsigned)r, g.magicJ); j = r - grp * g.J; }        // j fastest: contiguous in HBM
-      else { j = (int)cg_fastdiv((unsigned)r, g.magicGT); grp = r - j * g.GT; }                      // joint fastest
+      if (DOMAIN == 1) { grp = (int)cg_div((unsigned)r, g.magicJ); j = r - grp * g.J; }        // j fastest: contiguous in HBM
+      else { j = (int)cg_div((unsigned)r, g.magicGT); grp = r - j * g.GT; }                      // joint fastest
       gof[i] = c * TV + (DOMAIN == 1 ? grp * g.V + j : j * g.V + grp);
       lof[i] = (c * g.RS + grp * g.Js + j) | (grp << 24);
     }
@@ -139,8 +135,8 @@ __device__ __forceinline__ void cg_domm_adj_store(const CgDomM& g, const float v
   for (int i = 0; i < CG_DOMM_PF; ++i) {
     const int e = threadIdx.x + i * CG_DOMM_THREADS;
     if (e < n) {
-      const int r = (int)cg_fastdiv((unsigned)e, g.magicJ), o = e - r * g.J;      // r = grp*J + j
-      const int grp = (int)cg_fastdiv((unsigned)r, g.magicJ), j = r - grp * g.J;
+      const int r = (int)cg_div((unsigned)e, g.magicJ), o = e - r * g.J;      // r = grp*J + j
+      const int grp = (int)cg_div((unsigned)r, g.magicJ), j = r - grp * g.J;
       sA[(grp * g.Jr + j) * g.Jsa + o] = v[i];
     }
   }
@@ -169,8 +165,8 @@ __device__ __forceinline__ void cg_domm_graph_product(const CgDomM& g, const flo
   const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), nw = CG_DOMM_THREADS / 64, l15 = lane & 15, slot = lane >> 4;
   const int MTi = g.CiM / 16, NT = g.Jr / 16, NP = (NT + 1) / 2;
   for (int w = wave; w < g.GT * MTi * NP; w += nw) {
-    const int r = (int)cg_fastdiv((unsigned)w, g.magicNP), np = w - r * NP;
-    const int grp = (int)cg_fastdiv((unsigned)r, g.magicMTi), mt = r - grp * MTi;
+    const int r = (int)cg_div((unsigned)w, g.magicNP), np = w - r * NP;
+    const int grp = (int)cg_div((unsigned)r, g.magicMTi), mt = r - grp * MTi;
     const int n0 = 32 * np, n1 = (n0 + 16 < g.Jr) ? n0 + 16 : n0;
     cg_f32x4 c0 = cg_f32x4{0.f, 0.f, 0.f, 0.f}, c1 = c0;
     const float* as = sA + grp * g.Jr * g.Jsa;
@@ -272,7 +268,7 @@ __global__ __launch_bounds__(CG_DOMM_THREADS, 2) void cg_stgcn_domain_bwd_mfma_k
 
     // P4: dG[ci][p] = sum_co W[co][ci] dY[co][p]  -> sBuf (G is dead)
     for (int w = wave; w < MTi * NPp; w += nw) {
-      const int mt = (int)cg_fastdiv((unsigned)w, g.magicNPp), np = w - mt * NPp;
+      const int mt = (int)cg_div((unsigned)w, g.magicNPp), np = w - mt * NPp;
       const int n0 = 32 * np, n1 = (n0 + 16 < 16 * NTp) ? n0 + 16 : n0;
       cg_f32x4 c0 = cg_f32x4{0.f, 0.f, 0.f, 0.f}, c1 = c0;
       cg_mma_pair<1, 1>(wimg + 16 * mt, wrs, sDY + n0, sDY + n1, g.RS, g.Cout, c0, c1);
@@ -300,8 +296,8 @@ __global__ __launch_bounds__(CG_DOMM_THREADS, 2) void cg_stgcn_domain_bwd_mfma_k
     for (int w = wave; w < n2 + n3; w += nw) {
       cg_f32x4 c0 = cg_f32x4{0.f, 0.f, 0.f, 0.f}, c1 = c0;
       if (w < n2) {
-        const int r = (int)cg_fastdiv((unsigned)w, g.magicNP), np = w - r * NP;
-        const int grp = (int)cg_fastdiv((unsigned)r, g.magicMTi), mt = r - grp * MTi;
+        const int r = (int)cg_div((unsigned)w, g.magicNP), np = w - r * NP;
+        const int grp = (int)cg_div((unsigned)r, g.magicMTi), mt = r - grp * MTi;
         const int n0 = 32 * np, n1 = (n0 + 16 < g.Jr) ? n0 + 16 : n0;
         if (grp >= ng) continue;
         const float* as = sA + grp * g.Jr * g.Jsa;
@@ -316,8 +312,8 @@ __global__ __launch_bounds__(CG_DOMM_THREADS, 2) void cg_stgcn_domain_bwd_mfma_k
         }
       } else {
         const int v = w - n2;
-        const int r = (int)cg_fastdiv((unsigned)v, g.magicNP), np = v - r * NP;
-        const int grp = (int)cg_fastdiv((unsigned)r, g.magicNT), mt = r - grp * NT;
+        const int r = (int)cg_div((unsigned)v, g.magicNP), np = v - r * NP;
+        const int grp = (int)cg_div((unsigned)r, g.magicNT), mt = r - grp * NT;
         const int n0 = 32 * np, n1 = (n0 + 16 < g.Jr) ? n0 + 16 : n0;
         if (grp >= ng) continue;
         cg_mma_pair<1, 1>(sX + grp * g.Js + 16 * mt, g.RS, sBuf + grp * g.Js + n0, sBuf + grp * g.Js + n1, g.RS, g.Cin, c0, c1);
@@ -415,13 +411,13 @@ __global__ __launch_bounds__(CG_DOMM_THREADS, 2) void cg_stgcn_domain_fwd_mfma2_
     }
     float* yb = y + (long long)b * g.Cout * TV;
     for (int w = wave; w < MTo * NPp; w += nw) {                           // PY
-      const int mt = (int)cg_fastdiv((unsigned)w, g.magicNPp), np = w - mt * NPp;
+      const int mt = (int)cg_div((unsigned)w, g.magicNPp), np = w - mt * NPp;
       const int n0 = 32 * np, n1 = (n0 + 16 < 16 * NTp) ? n0 + 16 : n0;
       cg_f32x4 c0 = cg_f32x4{0.f, 0.f, 0.f, 0.f}, c1 = c0;
       cg_mma_pair<0, 1>(sW + 16 * mt * g.WS, g.WS, sBuf + n0, sBuf + n1, g.RS, g.Cin, c0, c1);
       const int p0 = n0 + l15, p1 = n1 + l15;
-      const int gr0 = (int)cg_fastdiv((unsigned)p0, g.magicJs), o0 = p0 - gr0 * g.Js;
-      const int gr1 = (int)cg_fastdiv((unsigned)p1, g.magicJs), o1 = p1 - gr1 * g.Js;
+      const int gr0 = (int)cg_div((unsigned)p0, g.magicJs), o0 = p0 - gr0 * g.Js;
+      const int gr1 = (int)cg_div((unsigned)p1, g.magicJs), o1 = p1 - gr1 * g.Js;
       const bool ok0 = gr0 < ng && o0 < g.J, ok1 = n1 != n0 && gr1 < ng && o1 < g.J;
       const int a0 = ok0 ? cg_domm_off(g, DOMAIN, g0 + gr0, o0) : 0, a1 = ok1 ? cg_domm_off(g, DOMAIN, g0 + gr1, o1) : 0;
 #pragma unroll
@@ -450,7 +446,6 @@ __global__ __launch_bounds__(CG_DOMM_THREADS, 2) void cg_stgcn_domain_fwd_mfma2_
 // ---- host side ---------------------------------------------------------------------------------------------------
 static int cg_up(int v, int m) { return (v + m - 1) / m * m; }
 static int cg_up_4mod8(int v) { int r = cg_up(v, 4); return (r % 8 == 4) ? r : r + 4; }
-static unsigned cg_magic(int d) { return d > 1 ? (unsigned)((0x100000000ULL + d - 1) / d) : 0u; }
 
 size_t cg_domm_lds_bytes(const CgDomM& g, bool bwd) {
   if (bwd) return ((size_t)(2 * g.CiM + g.CoM) * g.RS + (size_t)g.GT * g.Jr * g.Jsa + (g.w_global ? 0 : (size_t)g.CoM * g.WS)) * sizeof(float);
@@ -473,8 +468,8 @@ int cg_domm_geom(CgDomM& g, int B, int Cin, int Cout, int T, int V, int domain, 
   g.Jsa = g.Jr + 4;
   g.CiM = cg_up(Cin, 16); g.CoM = cg_up(Cout, 16);
   g.WS = g.CiM + 4;
-  g.magicJ = cg_magic(g.J);
-  g.magicJs = cg_magic(g.Js);
+  g.magicJ = cg_div_magic(g.J);
+  g.magicJs = cg_div_magic(g.Js);
   g.dbg = 0;
   // two workgroups per CU: the image must fit 80 KiB.  The backward drops the weight image first (the dG product then
   // reads W through L1/L2, which needs whole 16-wide fragments: channel counts that are multiples of 16)
@@ -502,12 +497,12 @@ int cg_domm_geom(CgDomM& g, int B, int Cin, int Cout, int T, int V, int domain, 
   if (best == 0) return CG_ESHAPE;
   g.GT = best;
   g.RS = cg_domm_rs(g, best);
-  g.magicGT = cg_magic(g.GT);
-  g.magicRun = cg_magic(g.GT * g.J);
-  g.magicNP = cg_magic((g.Jr / 16 + 1) / 2);
-  g.magicMTi = cg_magic(g.CiM / 16);
-  g.magicNT = cg_magic(g.Jr / 16);
-  g.magicNPp = cg_magic(((g.GT * g.Js + 15) / 16 + 1) / 2);
+  g.magicGT = cg_div_magic(g.GT);
+  g.magicRun = cg_div_magic(g.GT * g.J);
+  g.magicNP = cg_div_magic((g.Jr / 16 + 1) / 2);
+  g.magicMTi = cg_div_magic(g.CiM / 16);
+  g.magicNT = cg_div_magic(g.Jr / 16);
+  g.magicNPp = cg_div_magic(((g.GT * g.Js + 15) / 16 + 1) / 2);
   g.ntiles = (g.NG + best - 1) / best;
   const long long total = (long long)B * g.ntiles;
   if (total > 2147483647LL) return CG_ESHAPE;

@@ -40,10 +40,6 @@ typedef float cg_f32x2 __attribute__((vector_size(8)));
 // {q, q ^ 4}, so the swizzle must differ between rows in the bits other than bit 2.
 __device__ __forceinline__ int cg_domp_swz(int o) { const int h = o >> 1; return (h & 3) | ((h & 4) << 1); }
 
-__device__ __forceinline__ unsigned cg_domp_div(unsigned n, unsigned magic) {     // n / d, magic = ceil(2^32 / d), 0 for d = 1; n < 2^20
-  return magic ? (unsigned)(((unsigned long long)n * magic) >> 32) : n;
-}
-
 // VW consecutive floats (VW * 4-byte aligned) -> registers; zeros when !ok
 template <int VW>
 __device__ __forceinline__ void cg_domp_ld(const float* __restrict__ p, bool ok, float (&v)[VW]) {
@@ -71,7 +67,7 @@ __device__ __forceinline__ void cg_domp_st(float* __restrict__ p, const float (&
 // position p of a (T,V) plane -> (group, index along the contraction axis)
 template <int DOMAIN>
 __device__ __forceinline__ void cg_domp_split(const CgDomP& g, int p, int& grp, int& j) {
-  const int t = (int)cg_domp_div((unsigned)p, g.magicV), v = p - t * g.V;
+  const int t = (int)cg_div((unsigned)p, g.magicV), v = p - t * g.V;
   if (DOMAIN == 0) { grp = v; j = t; } else { grp = t; j = v; }
 }
 
@@ -238,7 +234,7 @@ __global__ __launch_bounds__(CG_DOMP_THREADS, 2) void cg_stgcn_planes_fwd_kernel
   const int nq = g.TV / VW;
   float* yb = y + ((long long)b * g.Cout + o0) * g.TV;
   for (int e = tid; e < 16 * nq; e += CG_DOMP_THREADS) {
-    const int o = (int)cg_domp_div((unsigned)e, g.magicNQ), pv = e - o * nq;
+    const int o = (int)cg_div((unsigned)e, g.magicNQ), pv = e - o * nq;
     if (o0 + o >= g.Cout) break;
     float v[VW];
 #pragma unroll
@@ -389,7 +385,7 @@ __global__ __launch_bounds__(CG_DOMPB_THREADS, 2) void cg_stgcn_planes_bwd_kerne
     for (int i = 0; i < PF; ++i)
 #pragma unroll
       for (int jj = 0; jj < VWY; ++jj) {
-        const int idx = (pk + 32 * i) * VWY + jj, q = (int)cg_domp_div((unsigned)idx, g.magicV), v = idx - q * V;
+        const int idx = (pk + 32 * i) * VWY + jj, q = (int)cg_div((unsigned)idx, g.magicV), v = idx - q * V;
         pso[i][jj] = v * GY + po * 16 + ((q & 15) ^ sw);
       }
   }
@@ -525,7 +521,7 @@ __global__ __launch_bounds__(CG_DOMPB_THREADS, 2) void cg_stgcn_planes_bwd_kerne
       for (int h = 0; h < 2; ++h) {
         const int pp = 16 * (h ? pt1 : pt) + l15;
         if (pp < Pn && (h == 0 || pt1 != pt)) {
-          const int t = (int)cg_domp_div((unsigned)pp, g.magicV), v = pp - t * V;
+          const int t = (int)cg_div((unsigned)pp, g.magicV), v = pp - t * V;
           float* dst = sZ + v * GZ + 4 * slot * 16 + t;
 #pragma unroll
           for (int r = 0; r < 4; ++r) dst[r * 16] = h ? acc1[r] : acc0[r];
@@ -738,7 +734,6 @@ __global__ __launch_bounds__(CG_DOMPB_THREADS, 2) void cg_stgcn_planes_bwd_kerne
 // ---------------------------------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------------------------------
-static unsigned cg_domp_magic(int d) { return d > 1 ? (unsigned)((0x100000000ULL + d - 1) / d) : 0u; }
 static int cg_domp_up(int v, int m) { return (v + m - 1) / m * m; }
 
 int cg_domp_geom(CgDomP& g, int B, int Cin, int Cout, int T, int V, int domain) {
@@ -758,8 +753,8 @@ int cg_domp_geom(CgDomP& g, int B, int Cin, int Cout, int T, int V, int domain) 
   if (g.J <= 16) { g.VWB = 1; g.NL = 1; }
   else if (g.J <= 32) { if (g.J % 2 == 0) { g.VWB = 2; g.NL = 1; } else { g.VWB = 1; g.NL = 2; } }
   else { if (g.J % 4 == 0) { g.VWB = 4; g.NL = 1; } else if (g.J % 2 == 0) { g.VWB = 2; g.NL = 2; } else { g.VWB = 1; g.NL = 4; } }
-  g.magicV = cg_domp_magic(V);
-  g.magicNQ = cg_domp_magic(g.TV / g.VW);
+  g.magicV = cg_div_magic(V);
+  g.magicNQ = cg_div_magic(g.TV / g.VW);
   return CG_OK;
 }
 
