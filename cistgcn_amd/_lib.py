@@ -2,6 +2,10 @@
 
 There is exactly one backend.  If the library is missing the loader raises; nothing in this
 package computes on the CPU or through stock PyTorch operators instead.
+
+The Structure classes, `LIMITS` and `_SIGNATURES` below are written by hand after the header the kernels are compiled
+against.  tests/test_boundary.py holds them to it: every size, field offset, field size and macro value against a C++
+program that includes the header, every argument list against its prototype.
 """
 import ctypes
 import os
@@ -11,8 +15,29 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, "libcistgcn_hip.so")
 
 _handle = None
-STAT_REPLICAS = 16     # CG_STAT_REPLICAS of include/cistgcn_hip.h
-ALPHA_SLOTS = 64       # CG_ALPHA_SLOTS: f64 words the partial sums of a shared PReLU slope's gradient are spread over
+# Limits a caller of the ABI has to honour, by their macro names in include/cistgcn_hip.h.
+LIMITS = {
+    "CG_STAT_REPLICAS": 16,      # replicas of a BatchNorm channel-sum buffer
+    "CG_ALPHA_SLOTS": 64,        # f64 words the partial sums of a shared PReLU slope's gradient are spread over
+    "CG_MAX_BATCH": 16,          # problems per cg_contract_many launch
+    "CG_ROW_MAX_BATCH": 6,       # problems per launch of the row kernels
+    "CG_SUM_MAX": 8,             # addends per cg_sum_many launch
+    "CG_COPY_MAX": 4,            # copies per cg_copy_many launch
+    "CG_BIN_MAXG": 8,            # consumer gradients per cg_block_input_bwd
+    "CG_MID_MAXN": 6,            # items per cg_block_mid_* launch
+    "CG_PWM_MAXN": 4,            # cg_pointwise_maps_*: maps per launch,
+    "CG_PWM_MAXROWS": 128,       # their output channels (each rounded up to 16) together,
+    "CG_PWM_MAXCIN": 128,        # input channels,
+    "CG_PWM_MAXM": 64,           # output channels of one map
+    "CG_GATE_MAXC": 64,          # cg_gate_head_*: channels,
+    "CG_GATE_MAXS": 192,         # block statistics per sample
+    "CG_CTX_MAXC": 64,           # channels of cg_context_heads_*
+    "CG_EM_METRICS": 9,          # outputs of cg_eval_metrics
+    "CG_AM_OUT": 33,             # outputs of cg_attack_metrics,
+    "CG_AM_BINS": 64,            # bins of its histograms
+}
+STAT_REPLICAS = LIMITS["CG_STAT_REPLICAS"]
+ALPHA_SLOTS = LIMITS["CG_ALPHA_SLOTS"]
 # Host pointers are refused unless a test harness has injected an emulated build of the very same
 # kernel sources (tests/hipemu).  The product never sets this.
 _host_pointers_ok = False
@@ -185,15 +210,19 @@ class DeepfoolStep(ctypes.Structure):
                 ("steps", c_void_p), ("frozen_at", c_void_p)]
 
 
-class EvalMetricsArgs(ctypes.Structure):      # CgEvalMetrics
+class EvalMetricsArgs(ctypes.Structure):
     _fields_ = [("B", c_int), ("To", c_int), ("J", c_int), ("Nb", c_int), ("frames", c_int), ("pad", c_int),
                 ("pred", c_void_p), ("target", c_void_p), ("speeds", c_void_p), ("bones", c_void_p),
                 ("out", c_void_p * 9), ("ws", c_void_p)]
 
 
-class AttackMetricsArgs(ctypes.Structure):      # CgAttackMetrics
+class AttackMetricsArgs(ctypes.Structure):
     _fields_ = [("B", c_int), ("T", c_int), ("J", c_int), ("pad", c_int),
                 ("adv", c_void_p), ("orig", c_void_p), ("out", c_void_p * 33), ("counts", c_void_p), ("gmax", c_void_p), ("ws", c_void_p)]
+
+
+# A class mirrors the header's struct "Cg" + its own name, except these two.
+C_STRUCT_NAMES = {"EvalMetricsArgs": "CgEvalMetrics", "AttackMetricsArgs": "CgAttackMetrics"}
 
 
 P = c_void_p

@@ -14,8 +14,9 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libcistgcn_hip.so")
 OBJ = os.path.join(os.path.dirname(HERE), "build", "obj")
+INCLUDE = os.path.join(os.path.dirname(HERE), "include")      # cistgcn_hip.h: the kernels are compiled against the public header
 ARCH = "gfx950"
-FLAGS = ["--offload-arch=" + ARCH, "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function", "-I", CSRC]
+FLAGS = ["--offload-arch=" + ARCH, "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function", "-I", CSRC, "-I", INCLUDE]
 
 
 def sources():
@@ -23,7 +24,8 @@ def sources():
 
 
 def _headers_mtime():
-    return max([os.path.getmtime(p) for p in glob.glob(os.path.join(CSRC, "*.h"))] + [os.path.getmtime(__file__)])
+    hdrs = glob.glob(os.path.join(CSRC, "*.h")) + [os.path.join(INCLUDE, "cistgcn_hip.h"), __file__]
+    return max(os.path.getmtime(p) for p in hdrs)
 
 
 def _stale():

@@ -63,27 +63,8 @@ extern "C" int cg_mpjpe_sample_bwd(const float* pred, const float* tgt, const fl
 }
 
 // ---------------------------------------------------------------------------------------------
-// the attack step
+// the attack step (argument block CgAttackStep: include/cistgcn_hip.h)
 // ---------------------------------------------------------------------------------------------
-struct CgAttackStep {      // mirrored by include/cistgcn_hip.h and cistgcn_amd/_lib.py
-  int B, T, V, mode, iterations, patience;
-  float epsilon, mu;
-  const float* x0;      // (B,T,V,3) the clean input
-  float* x;             // (B,T,V,3) in: x_i, out: x_adv (= the next x_i)
-  const float* grad;    // (B,T,V,3) d(sum_b w_b loss_b)/dx_i
-  float* g;             // (B,T,V,3) momentum (MI-FGSM only)
-  const float* mask;    // (T,V) 1 = this joint of this frame may move; null = all
-  const float* loss;    // (B,) loss_b of this iteration
-  float* best;          // (B,) highest loss so far
-  int* stall;           // (B,) iterations without improvement
-  int* active;          // (B,) 1 while the sample is still optimised
-  float* w;             // (B,) upstream weight of the NEXT backward: 1/B while active, else 0
-  int* queries;         // (B,) model calls spent on the sample
-  int* n_active;        // (1,) samples still active (for the host to poll)
-  int* steps;           // (B,) steps this sample has been through (each workgroup counts its own)
-  int* frozen_at;       // (B,) index of the step at whose end the sample froze, INT_MAX while it is active
-};
-
 struct CgOpMin { __device__ __forceinline__ float operator()(float a, float b) const { return fminf(a, b); } };
 struct CgOpMax { __device__ __forceinline__ float operator()(float a, float b) const { return fmaxf(a, b); } };
 struct CgOpAdd { __device__ __forceinline__ double operator()(double a, double b) const { return a + b; } };
@@ -216,17 +197,8 @@ extern "C" int cg_attack_step(const CgAttackStep* a, void* stream_) {
 
 // ---------------------------------------------------------------------------------------------
 // the DeepFool step (DEEPFOOL.compute_gradient, :697-717): x += mask * r,  r = -grad * mean_t(pred) / (||grad||_1 + 1e-10)
+// (argument block CgDeepfoolStep: include/cistgcn_hip.h)
 // ---------------------------------------------------------------------------------------------
-struct CgDeepfoolStep {      // mirrored by include/cistgcn_hip.h and cistgcn_amd/_lib.py
-  int B, T, To, V, patience, pad;
-  float* x;             // (B,T,V,3) in: x_i, out: x_adv (= the next x_i)
-  const float* grad;    // (B,T,V,3) d(sum_b w_b loss_b)/dx_i
-  const float* pred;    // (B,To,V,3) the prediction of the same forward pass
-  const float* mask;    // (T,V) 1 = this joint of this frame may move; null = all
-  const float* loss;    // (B,) loss_b of this iteration; null (with the eight below) = no bookkeeping, every sample steps
-  float* best; int* stall; int* active; float* w; int* queries; int* n_active; int* steps; int* frozen_at;      // as in CgAttackStep
-};
-
 // The To-means of the prediction's V*3 columns stay in LDS (f64) up to this many columns; a wider skeleton re-reads its column in
 // every element, in the same order, so the two paths give the same bits.  Half the default dynamic LDS: no driver call to raise it.
 #define CG_DEEPFOOL_LDS_COLS (CG_LDS_DEFAULT / 2 / (int)sizeof(double))

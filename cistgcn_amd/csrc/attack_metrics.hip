@@ -19,8 +19,6 @@
 
 #define CG_AM_THREADS 256
 #define CG_AM_WAVES (CG_AM_THREADS / CG_WAVE)
-#define CG_AM_OUT 33
-#define CG_AM_BINS 64
 #define CG_AM_TILE CG_WAVE      // cross pass: samples of adv per wavefront and samples of orig per LDS tile
 #define CG_AM_HB 8              // histogram pass: a workgroup bins a rectangle of CG_AM_HB samples x CG_AM_HT frame indices
 #define CG_AM_HT 8
@@ -36,16 +34,6 @@ enum { CG_AM_S_E = 0, CG_AM_S_N, CG_AM_S_PA, CG_AM_S_SE, CG_AM_S_H, CG_AM_S_AO, 
 enum { CG_AM_X_HSUM = 0, CG_AM_X_AO, CG_AM_X_AA = CG_AM_X_AO + 3, CG_AM_X_OO = CG_AM_X_AA + 3, CG_AM_X_HMAX = CG_AM_X_OO + 3, CG_AM_CROSS };
 // order of a family's ten results: out[3 + 10 * family + q], family 0 temporal_*, 1 spatial_*, 2 *_sample; out[0..2] the scalars
 enum { CG_AM_Q_E = 0, CG_AM_Q_N, CG_AM_Q_PA, CG_AM_Q_HMEAN, CG_AM_Q_HMAX, CG_AM_Q_MSE, CG_AM_Q_COS, CG_AM_Q_KLD, CG_AM_Q_JSD, CG_AM_Q_KS };
-
-struct CgAttackMetrics {      // mirrored by include/cistgcn_hip.h and cistgcn_amd/_lib.py
-  int B, T, J, pad;
-  const float* adv;         // (B,T,J,3), the reference's in_seq
-  const float* orig;        // (B,T,J,3), the reference's adv_seq
-  float* out[CG_AM_OUT];
-  int32_t* counts;          // [2][B][64] | [2][T][64] | [2][J][64]: index 0 adv, 1 orig
-  float* gmax;              // [B] | [T] | [J] histogram ranges
-  double* ws;               // cg_attack_metrics_ws_doubles(B,T,J)
-};
 
 struct CgAmWs {
   double* map;      // [CG_AM_MAPS][B*T*J]

@@ -14,7 +14,6 @@
 #include <initializer_list>
 #include "cg_common.h"
 #include "cg_phase.h"
-#include "block_input.h"
 
 HIP_DYNAMIC_SHARED(unsigned char, cg_dyn_lds)
 

@@ -4,18 +4,7 @@
 // one-channel input), so each keeps its own result struct; the rules of nn.BatchNorm - biased variance for the normalisation, unbiased into
 // running_var, one count per forward - are written here and nowhere else.
 #pragma once
-#include "cg_common.h"
-
-// one BatchNorm of a chain; mirrored by include/cistgcn_hip.h and cistgcn_amd/_lib.py.  `stats`: replicated f64 {sum, sum of squares}
-// of ITS INPUT over batch and positions ([CG_STAT_REPLICAS][C][2], zero before the producing phase; train mode only).  `save`: [2][C]
-// mean / rstd actually used by the forward (written by the first phase that needs them, read by the later phases and the backward).
-struct CgTailBN {
-  double* stats;
-  const float* gamma; const float* beta;
-  float* running_mean; float* running_var; long long* num_batches_tracked;
-  float momentum, eps;
-  float* save;
-};
+#include "cg_common.h"        // CgTailBN (cistgcn_hip.h): one BatchNorm of a chain
 
 // sums of channel c over the replicas of a [CG_STAT_REPLICAS][ld][2] buffer (cg_common.h), in replica order
 __device__ __forceinline__ void cg_bn_sums(const double* stats, long long ld, int c, double& s1, double& s2) {

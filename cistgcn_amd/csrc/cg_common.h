@@ -1,10 +1,12 @@
-// Included by every source of the kernel library: status codes, launcher limits, and the small device helpers more than one file
-// needs - wave / block reductions, row-of-16 DPP exchange, fixed-width vector load / store, division by a run-time constant, the
-// dropout hash.  (BatchNorm constants: cg_bn.h; fragment reads of the phase kernels: cg_phase.h.)
+// Included by every source of the kernel library: the public C ABI (include/cistgcn_hip.h: every argument block, caller-facing limit and
+// entry-point prototype - the kernels are compiled against it, nothing of it is repeated here), status codes, launcher limits, and
+// the small device helpers more than one file needs - wave / block reductions, row-of-16 DPP exchange, fixed-width vector load / store,
+// division by a run-time constant, the dropout hash.  (BatchNorm constants: cg_bn.h; fragment reads of the phase kernels: cg_phase.h.)
 // Wavefront = 64 lanes (CDNA4); every reduction below is written for that width.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "../../include/cistgcn_hip.h"      // by its place in the tree: found with or without include/ on the include path
 
 #define CG_WAVE 64
 
@@ -19,18 +21,6 @@
 #define CG_OK 0
 #define CG_EARG (-1)
 #define CG_ESHAPE (-2)
-
-// BatchNorm channel sums are accumulated with f64 atomics by every workgroup of the producing kernel; with
-// thousands of workgroups per channel one address serialises (~tens of microseconds).  Producers therefore add
-// into replica (block id mod CG_STAT_REPLICAS) of a [CG_STAT_REPLICAS][C][2] buffer, the consumer sums the replicas (cg_bn_sums, cg_bn.h).
-#define CG_STAT_REPLICAS 16
-
-// 4-D strided view: dims n[0..3] (n[0] = batch rows, n[1] = channel), element strides s[0..3].
-// Layout-agnostic: NCTV, NTCV and (N,3,V,T) views of one buffer differ only in s[].
-struct CgView4 {
-  long long n[4];
-  long long s[4];
-};
 
 // Zero fill by a kernel (rowops.hip).  hipMemsetAsync is NOT used anywhere in this library: as a node of a captured HIP
 // graph it was not reliably ordered against the neighbouring kernels (see cg_zero in rowops.hip).
@@ -174,10 +164,7 @@ __device__ __forceinline__ double cg_row16_sum(double v) {
   return v;
 }
 
-// The gradient of a shared PReLU slope is a sum over the whole tensor.  One f64 word would take an atomic from every
-// workgroup: same-address atomics serialise at ~20 ns each on MI355X (measured, profiles/README.md), 4096 of them cost more than
-// the kernel's memory traffic.  Its partial sums are therefore spread over CG_ALPHA_SLOTS words behind the channel sums.
-#define CG_ALPHA_SLOTS 64
+// the gradient of a shared PReLU slope: sum of its CG_ALPHA_SLOTS partial sums (cistgcn_hip.h), in slot order
 __device__ __forceinline__ double cg_alpha_sum(const double* slots) {
   double s = 0.0;
   for (int i = 0; i < CG_ALPHA_SLOTS; ++i) s += slots[i];

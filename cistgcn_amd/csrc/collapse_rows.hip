@@ -8,7 +8,6 @@
 //             contiguous 64 x V piece per sample, dW[o,k] += sum_v dy[b,o,v] x[b,k,v] stays in registers over the slice
 #include "cg_common.h"
 #include "cg_phase.h"
-#include "collapse_rows.h"
 
 HIP_DYNAMIC_SHARED(unsigned char, cg_dyn_lds)
 

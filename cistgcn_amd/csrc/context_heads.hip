@@ -12,7 +12,7 @@
 //             slope gradient; phase 2 (per sample): dx[b,p]; workgroup 0 also writes dw, dgamma, dbeta, dalpha in closed form:
 //             with xhat = (w x - m) r:   S2 = sum gu xhat = r (w G - m S1),   dw = gamma r (G - S1 E[x] - S2 r (w E[x^2] - m E[x]))
 #include "cg_common.h"
-#include "context_heads.h"
+#include "cg_bn.h"
 
 HIP_DYNAMIC_SHARED(unsigned char, cg_dyn_lds)
 

@@ -23,20 +23,9 @@
 // One launch runs up to CG_MAX_BATCH independent contractions ("horizontal fusion"): the descriptors
 // travel by value in the kernel arguments and every workgroup looks up the problem its block id
 // falls into.  The model issues the same-depth maps of its parallel branches (gate s/t, the four
-// Map2Adj towers, residual maps, and in backward every dA / dX / bias sum of a stage) as one launch.
-struct CgContractDesc {
-  const float* A; const float* X; float* Y; const float* bias; double* stats; const int32_t* tab;
-  int G, M, N, K, splitk, kchunk, a_kfast, x_kfast;
-  int accumulate;            // 1: fp32 atomic adds into Y (several problems sum into one zeroed output)
-  int x_vec;                 // 1: X is contiguous and 16-byte aligned along n in groups of four -> float4 loads
-  int stat_ch;               // number of channels of `stats` (replica stride = 2 * stat_ch doubles)
-  int mode;                  // 0: tiled kernel below; 1: streaming kernel (cg_stream_body); 2: K-reduction (cg_kred_body)
-  long long block0;          // first block id of this problem inside the launch
-  float* ws;                 // mode 2: zeroed scratch of cg_contract_kred_ws_floats(G, M, N) floats
-  int chain;                 // mode 1: 1 + index (in the caller's array) of a problem whose product is ADDED to this one's
-  int pad2;                  //         output in registers (same G, M, N; it writes nothing itself), 0 = none
-};
-#define CG_MAX_BATCH 16
+// Map2Adj towers, residual maps, and in backward every dA / dX / bias sum of a stage) as one launch.  A descriptor (CgContractDesc,
+// include/cistgcn_hip.h) selects by `mode` the tiled kernel below (0), the streaming kernel cg_stream_body (1) or the K-reduction
+// cg_kred_body (2).
 struct CgContractBatch { int n; int pad; CgContractDesc d[CG_MAX_BATCH]; };
 
 // fp32-input MFMA (v_mfma_f32_16x16x4_f32): exact f32 fma chain in k order, one A and one B value per lane

@@ -16,23 +16,12 @@
 #define CG_EM_WAVES (CG_EM_THREADS / CG_WAVE)
 #define CG_EM_PRE_THREADS 1024
 #define CG_EM_PRE_WAVES (CG_EM_PRE_THREADS / CG_WAVE)
-#define CG_EM_METRICS 9
 #define CG_EM_SUMS 7
 
-// order of CgEvalMetrics.out (mirrored by include/cistgcn_hip.h and cistgcn_amd/ops.py)
+// order of CgEvalMetrics.out (the list in include/cistgcn_hip.h, EVAL_METRICS of cistgcn_amd/ops.py)
 enum { CG_EM_MPJPE = 0, CG_EM_PA, CG_EM_N, CG_EM_MVE, CG_EM_W, CG_EM_BONE, CG_EM_WBONE, CG_EM_WJ, CG_EM_WJT };
 // the per-frame sums `frames` mode keeps: w_mpjpe and w_bone_l are w_t times the sums of mpjpe and bone_l
 enum { CG_EM_S_E = 0, CG_EM_S_PA, CG_EM_S_N, CG_EM_S_MVE, CG_EM_S_BONE, CG_EM_S_WJ, CG_EM_S_WJT };
-
-struct CgEvalMetrics {      // mirrored by include/cistgcn_hip.h and cistgcn_amd/_lib.py
-  int B, To, J, Nb, frames, pad;
-  const float* pred;        // (B,To,J,3)
-  const float* target;      // (B,To,J,3)
-  const float* speeds;      // (B,To,J)
-  const int32_t* bones;     // (Nb,2) joint pairs
-  float* out[CG_EM_METRICS];      // frames: (To,) each, (To-1,) for mve; else (B,To,J), (B,To-1,J) for mve, (B,To,Nb) for the bone metrics
-  double* ws;               // cg_eval_metrics_ws_doubles(B,To,J): [To*J] batch maxima | [CG_EM_SUMS][B][To] per-frame sums
-};
 
 // w_t = (t + 1) / To in fp32, as `arange(1, To + 1) / To` gives it (test.py:301-302)
 __device__ __forceinline__ double cg_em_wt(int t, int To) { return (double)((float)(t + 1) / (float)To); }

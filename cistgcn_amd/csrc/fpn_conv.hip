@@ -8,7 +8,6 @@
 //             dW / db: persistent workgroups per dilation keep the [outputs][(c,i,j)] tiles in registers over their samples
 #include "cg_common.h"
 #include "cg_phase.h"
-#include "fpn_conv.h"
 
 HIP_DYNAMIC_SHARED(unsigned char, cg_dyn_lds)
 

@@ -13,7 +13,6 @@
 // single CU.)
 #include "cg_common.h"
 #include "cg_phase.h"
-#include "gate_head.h"
 
 HIP_DYNAMIC_SHARED(unsigned char, cg_dyn_lds)
 

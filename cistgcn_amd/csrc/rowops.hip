@@ -46,7 +46,6 @@ static int cg_rows_per_block(const CgView4& v) {
 // include/cistgcn_hip.h : host-only, rows of one channel per workgroup of the row kernels for this view (no launch)
 extern "C" int cg_norm_act_rows_per_block(const CgView4* xv) { return xv ? cg_rows_per_block(*xv) : CG_EARG; }
 
-#define CG_ROW_MAX_BATCH 6     // problems per launch of the row kernels (kernel-argument budget)
 // Vector width of the contiguous-row paths: 4 (rows 16-byte aligned, P % 4 == 0) or 2 (rows 8-byte aligned, P % 2 == 0: the
 // (T,V) planes of the 25-joint skeletons, P = 1250, and the (25, 66) planes of the output block).  The width is uniform per
 // problem; lanes j >= vw of a group are never used.
@@ -104,7 +103,6 @@ __global__ void cg_chan_stats_kernel(CgStatsBatch batch) {
   }
 }
 
-struct CgStatsArgs { const float* x; CgView4 xv; const float* pre; double* stats; };
 static int cg_view_vec(const void* ptr, const CgView4& v);       // vector width of contiguous aligned rows: 4, 2 or 0 (defined with the row kernels below)
 
 // include/cistgcn_hip.h : cg_chan_stats_many (up to CG_ROW_MAX_BATCH tensors per launch)
@@ -165,33 +163,9 @@ extern "C" int cg_chan_sum(const float* x, const CgView4* xv, float* out, void* 
 }
 
 // ---------------------------------------------------------------------------------------------
-// fused  y = PReLU( Dropout( (x*pre) * scale + shift ) [+ add] ) [+ add if add_post]
+// fused  y = PReLU( Dropout( (x*pre) * scale + shift ) [+ add] ) [+ add if add_post]      (argument block CgNormAct: include/cistgcn_hip.h)
 // ---------------------------------------------------------------------------------------------
-struct CgNormAct {
-  const float* x;  CgView4 xv;
-  float* y;        CgView4 yv;
-  const float* pre;              // (B,C) per-sample channel gate, or null
-  const float* add; CgView4 av;  // addend (same logical shape) or null
-  int add_post;                  // 0: added before the PReLU, 1: after it
-  int bn_mode;                   // 0 none, 1 batch statistics (train), 2 running statistics (eval)
-  const double* stats;           // [C][2] sums over B*P (bn_mode 1)
-  const float* gamma; const float* beta;
-  float* running_mean; float* running_var; long long* num_batches_tracked;
-  float momentum, eps;
-  float* save_mean; float* save_rstd;    // [C]; written in fwd (both modes), read in bwd
-  float drop_p; const unsigned long long* seed; unsigned int salt;
-  const float* alpha; int alpha_n;       // PReLU slope(s) or null
-  // backward only
-  const float* dy; CgView4 dyv;
-  float* dx; CgView4 dxv;
-  float* dadd; CgView4 dav;     // gradient of a pre-activation addend (null: not needed)
-  float* dpre;                  // (B,C) or null
-  double* red;                  // [C][2] sum g, sum g*xhat  (+ alpha_n slots behind it for d alpha)
-  float* dgamma; float* dbeta; float* dalpha;
-  double* ystats;               // forward, optional: [C][2] f64 sums of y (zero on entry) for the BatchNorm that consumes y
-};
-
-// u = (v - mean) * scale + shift, scale = gamma * rstd, shift = beta: the mean is subtracted FIRST (as
+// u =(v - mean) * scale + shift, scale = gamma * rstd, shift = beta: the mean is subtracted FIRST (as
 // nn.BatchNorm does); the folded form v*scale + (beta - mean*scale) cancels catastrophically when
 // |mean| >> std.
 struct CgChanAffine { float scale, shift, mean, rstd; };
@@ -681,7 +655,6 @@ extern "C" int cg_add3(float* y, const CgView4* yv, const float* a, const CgView
 // y = sum of up to CG_SUM_MAX same-shape strided tensors in one launch: the gradient of a tensor that feeds several
 // consumers (a block input goes to the statistics, the gate/tower maps, both graph stages and the residuals) is
 // summed once instead of by one autograd accumulation kernel per extra consumer.
-#define CG_SUM_MAX 8
 struct CgSumArgs { float* y; CgView4 yv; int n; int vec; const float* a[CG_SUM_MAX]; CgView4 av[CG_SUM_MAX]; };
 
 __global__ void cg_sum_many_kernel(CgSumArgs s) {
@@ -709,7 +682,6 @@ __global__ void cg_sum_many_kernel(CgSumArgs s) {
   }
 }
 
-struct CgSumItem { const float* a; CgView4 av; };
 // include/cistgcn_hip.h : cg_sum_many
 extern "C" int cg_sum_many(float* y, const CgView4* yv, const CgSumItem* items, int n, void* stream_) {
   if (!y || !yv || !items || n <= 0 || n > CG_SUM_MAX) return CG_EARG;
@@ -733,9 +705,8 @@ extern "C" int cg_sum_many(float* y, const CgView4* yv, const CgSumItem* items, 
   return cg_launch_status();
 }
 
-// up to four strided copies in one launch (the slices of a channel concatenation)
-struct CgCopyItem { float* y; CgView4 yv; const float* a; CgView4 av; };
-struct CgCopyBatch { int n; int pad; CgCopyItem it[4]; };
+// up to CG_COPY_MAX strided copies in one launch (the slices of a channel concatenation)
+struct CgCopyBatch { int n; int pad; CgCopyItem it[CG_COPY_MAX]; };
 
 __global__ void cg_copy_many_kernel(CgCopyBatch batch) {
   const CgCopyItem& it = batch.it[blockIdx.z];
@@ -750,7 +721,7 @@ __global__ void cg_copy_many_kernel(CgCopyBatch batch) {
 }
 
 extern "C" int cg_copy_many(const CgCopyItem* items, int n, void* stream_) {
-  if (!items || n <= 0 || n > 4) return CG_EARG;
+  if (!items || n <= 0 || n > CG_COPY_MAX) return CG_EARG;
   CgCopyBatch batch;
   batch.n = n; batch.pad = 0;
   long long gx = 1, gy = 1, big = 0;

@@ -505,7 +505,6 @@ extern "C" int cg_seed_bump(unsigned long long* seed, void* stream_) {
 // column was used.  One workgroup per slab, both domains of a block in one launch (blockIdx.y).
 // ---------------------------------------------------------------------------------------------
 #define CG_R1_JMAX 64
-struct CgRank1 { const float* s; const float* q; float* o; const float* dout; float* ds; float* dq; int domain; int pad; };
 struct CgRank1Batch { int n, B, T, V; CgRank1 it[2]; };
 
 // slab j of sample b: vectors sv[i], qv[k] and their strides

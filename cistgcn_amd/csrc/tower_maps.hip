@@ -10,7 +10,6 @@
 // LDS, every map padded to a multiple of 16 rows.
 #include "cg_common.h"
 #include "cg_phase.h"
-#include "tower_maps.h"
 #include <type_traits>
 
 HIP_DYNAMIC_SHARED(unsigned char, cg_dyn_lds)
@@ -459,12 +458,12 @@ __global__ void cg_pwm_fold_kernel(CgPwArgs a) {
 // ---- host side ---------------------------------------------------------------------------------------------------
 static int cg_pwm_geometry(const CgPwMaps* t, bool bwd, CgPwGeom* g) {
   if (!t || t->n <= 0 || t->n > CG_PWM_MAXN) return CG_EARG;
-  if (t->B <= 0 || t->Cin <= 0 || t->Cin > 128 || t->P <= 0 || (t->P & 1)) return CG_ESHAPE;
+  if (t->B <= 0 || t->Cin <= 0 || t->Cin > CG_PWM_MAXCIN || t->P <= 0 || (t->P & 1)) return CG_ESHAPE;
   g->vw = (t->P & 3) == 0 ? 4 : 2;
   if (!t->x) return CG_EARG;
   int rows = 0, tile = 0;
   for (int i = 0; i < t->n; ++i) {
-    if (t->M[i] <= 0 || t->M[i] > 64) return CG_ESHAPE;
+    if (t->M[i] <= 0 || t->M[i] > CG_PWM_MAXM) return CG_ESHAPE;
     if (!t->W[i]) return CG_EARG;
     g->row_base[i] = rows;
     for (int r0 = 0; r0 < t->M[i]; r0 += 16) { if (tile >= CG_PWM_MAXROWS / 16) return CG_ESHAPE; g->tile_map[tile] = i; g->tile_row0[tile] = r0; ++tile; }

@@ -377,7 +377,7 @@ def _contract_prepare(spec, a, x, bias=None, bias_label=None, sizes=None, sa=Non
     return r
 
 
-_MAX_CONTRACT_BATCH = 16
+_MAX_CONTRACT_BATCH = _lib.LIMITS["CG_MAX_BATCH"]
 _ACC_MAX_FLOATS = 1 << 22      # shared-input gradients: fp32 atomics into one buffer up to this size, else separate outputs + one sum
 
 
@@ -634,7 +634,7 @@ def contract_stats(spec, a, x, bias=None, bias_label=None, stats_label="o"):
 # ----------------------------------------------------------------------------------------------
 # fused BatchNorm / Dropout / residual / PReLU row kernel
 # ----------------------------------------------------------------------------------------------
-_ROW_BATCH = 6
+_ROW_BATCH = _lib.LIMITS["CG_ROW_MAX_BATCH"]
 
 
 def _na_fill_fwd(a, x, pre, add, gamma, beta, alpha, cfg, pending_stats):
@@ -964,7 +964,7 @@ class _Fanout(torch.autograd.Function):
         return _sum_tensors(gs), None
 
 
-_SUM_MAX = 8
+_SUM_MAX = _lib.LIMITS["CG_SUM_MAX"]
 
 
 def fanout(x, n):
@@ -1406,6 +1406,7 @@ def eval_scatter_mpjpe(pred, target, dim_used, dim_repeat_32=(), dim_repeat_22=(
 
 # order of CgEvalMetrics.out (include/cistgcn_hip.h)
 EVAL_METRICS = ("mpjpe", "pa_mpjpe", "n_mpjpe", "mve", "w_mpjpe", "bone_l", "w_bone_l", "w_joints", "w_joints_t")
+assert len(EVAL_METRICS) == _lib.LIMITS["CG_EM_METRICS"]
 
 
 def eval_metrics(pred, target, speeds, bones, reduce="frames"):
@@ -1454,7 +1455,8 @@ def eval_metrics(pred, target, speeds, bones, reduce="frames"):
 _ATTACK_SUFFIXES = ("mpjpe", "n_mpjpe", "pa_mpjpe", "hausdorff_mean", "hausdorff_max", "mse", "cos_simil", "KLD", "JSD", "KSTest")
 ATTACK_METRICS = (("mpjpe", "n_mpjpe", "pa_mpjpe") + tuple("temporal_" + s for s in _ATTACK_SUFFIXES) + tuple("spatial_" + s for s in _ATTACK_SUFFIXES)
                   + tuple(("cosine_simil" if s == "cos_simil" else s) + "_sample" for s in _ATTACK_SUFFIXES))
-ATTACK_BINS = 64
+assert len(ATTACK_METRICS) == _lib.LIMITS["CG_AM_OUT"]
+ATTACK_BINS = _lib.LIMITS["CG_AM_BINS"]
 
 
 def _attack_metrics_layout(B, T, J):
@@ -2033,7 +2035,7 @@ def block_input_ok(x):
     return bool(_lib.lib().cg_block_input_supported(B, C, T, V))
 
 
-_BLOCK_INPUT_MAXG = 8
+_BLOCK_INPUT_MAXG = _lib.LIMITS["CG_BIN_MAXG"]
 
 
 class _BlockInput(torch.autograd.Function):
@@ -2235,7 +2237,7 @@ def _mid_geometry(B, kind, C, L, O):
 
 def block_mid_ok(B, items):
     """True when `block_mid` takes the items: (kind, C, L, O, prelu or None) each, kind 0 = full, 1 = pointwise."""
-    return 1 <= len(items) <= 6 and all(bool(_lib.lib().cg_block_mid_supported(B, k, C, L, O)) and (p is None or p.weight.numel() == 1)
+    return 1 <= len(items) <= _lib.LIMITS["CG_MID_MAXN"] and all(bool(_lib.lib().cg_block_mid_supported(B, k, C, L, O)) and (p is None or p.weight.numel() == 1)
                                         for k, C, L, O, p in items)
 
 
@@ -2357,7 +2359,7 @@ def block_mid(items, train, drop_p=0.0, taps=None):
 
 def context_heads_ok(x, hidden):
     """True when `context_heads` takes the two one-channel heads of x (B,1,H,W)."""
-    return x.dim() == 4 and x.shape[1] == 1 and x.is_contiguous() and hidden <= 64 and x.shape[2] * x.shape[3] <= 16384
+    return x.dim() == 4 and x.shape[1] == 1 and x.is_contiguous() and hidden <= _lib.LIMITS["CG_CTX_MAXC"] and x.shape[2] * x.shape[3] <= 16384
 
 
 class _ContextHeads(torch.autograd.Function):
@@ -2452,11 +2454,13 @@ def context_heads(x, head_max, head_mean, train, taps=None):
 
 def pointwise_maps_ok(x, weights):
     """True when `pointwise_maps` takes this problem (else the caller batches the maps through the generic contraction)."""
-    if x.dim() != 4 or not x.is_contiguous() or len(weights) > 4:
+    lim = _lib.LIMITS
+    if x.dim() != 4 or not x.is_contiguous() or len(weights) > lim["CG_PWM_MAXN"]:
         return False
     B, C, H, W = x.shape
     rows = sum((w.shape[0] + 15) // 16 * 16 for w in weights)
-    return C <= 128 and (H * W) % 2 == 0 and rows <= 128 and (rows // 16) * ((C + 15) // 16) <= 32 and all(w.shape[0] <= 64 for w in weights)
+    return (C <= lim["CG_PWM_MAXCIN"] and (H * W) % 2 == 0 and rows <= lim["CG_PWM_MAXROWS"] and (rows // 16) * ((C + 15) // 16) <= 32
+            and all(w.shape[0] <= lim["CG_PWM_MAXM"] for w in weights))
 
 
 class _PointwiseMaps(torch.autograd.Function):

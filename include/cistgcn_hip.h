@@ -28,10 +28,11 @@ extern "C" {
 
 /* BatchNorm channel sums ("stats" / "ystats" below) are [CG_STAT_REPLICAS][C][2] f64 buffers, zero on entry:
  * every workgroup adds {sum, sum of squares} into replica (block id mod CG_STAT_REPLICAS) so that f64 atomics do
- * not serialise on one address; cg_norm_act_fwd sums the replicas. */
+ * not serialise on one address (with thousands of workgroups per channel: tens of microseconds); the consumer sums the replicas. */
 #define CG_STAT_REPLICAS 16
 /* The gradient of a shared PReLU slope (one scalar per tensor) is accumulated as CG_ALPHA_SLOTS partial sums behind the channel
- * sums of a `red` buffer: same-address f64 atomics serialise, thousands of workgroups on one word cost more than the kernel. */
+ * sums of a `red` buffer: same-address f64 atomics serialise at ~20 ns each on MI355X (measured, profiles/README.md), 4096 of them
+ * on one word cost more than the kernel's memory traffic. */
 #define CG_ALPHA_SLOTS 64
 
 /* 4-D strided view: n[0] batch, n[1] channel, n[2] x n[3] positions; s[] in elements.
@@ -56,10 +57,11 @@ int cg_contract(const float* A, const float* X, float* Y, const float* bias, dou
                 int G, int M, int N, int K, int splitk, int a_kfast, int x_kfast,
                 long long y_dense_numel, void* stream);
 
-/* Horizontal fusion: up to 16 independent contractions in ONE launch (same-depth maps of the parallel branches
+/* Horizontal fusion: up to CG_MAX_BATCH independent contractions in ONE launch (same-depth maps of the parallel branches
  * of a DSTD_GC block - gate s/t, the four Map2Adj towers, residual maps - and, in backward, every dA / dX / bias
  * sum of such a stage).  Split-K and accumulate outputs must be zero on entry (input gradients of maps that
  * share one input are accumulated into ONE buffer instead of being summed by extra kernels). */
+#define CG_MAX_BATCH 16
 typedef struct CgContractDesc {
   const float* A; const float* X; float* Y; const float* bias; double* stats; const int32_t* tab;
   int G, M, N, K, splitk, kchunk /* set by the library */, a_kfast, x_kfast;
@@ -71,7 +73,7 @@ typedef struct CgContractDesc {
                                     four (the n offsets of Y as those of X).  2: K-reduction kernel for weight gradients (few outputs, K = batch x
                                     positions): requires K % 4 == 0, A and X contiguous along k in 16-byte aligned groups of
                                     four, no `stats`, K / splitk <= 4080, and `ws` */
-  long long block0;              /* set by the library */
+  long long block0;              /* set by the library: first block id of this problem inside the launch */
   float* ws;                     /* mode 2: ZEROED scratch of cg_contract_kred_ws_floats(G, M, N) floats */
   int chain;                     /* mode 1: 1 + index (in `descs`) of another mode-1 problem with the same G, M, N whose product is
                                     added to this one's output in registers (the input gradient of a tensor that feeds several
@@ -85,8 +87,9 @@ long long cg_contract_kred_ws_floats(int G, int M, int N);
  * stats[c] = { sum, sum of squares } over batch and positions of x*pre (f64, must be zero on entry).
  * Replaces the reduction half of nn.BatchNorm{1,2}d in train mode. */
 int cg_chan_stats(const float* x, const CgView4* xv, const float* pre, double* stats, void* stream);
+#define CG_ROW_MAX_BATCH 6       /* problems per launch of the row kernels (cg_chan_stats_many, cg_norm_act_*_many): kernel-argument budget */
 typedef struct CgStatsArgs { const float* x; CgView4 xv; const float* pre; double* stats; } CgStatsArgs;
-int cg_chan_stats_many(const CgStatsArgs* items, int n, void* stream);   /* up to 6 tensors per launch */
+int cg_chan_stats_many(const CgStatsArgs* items, int n, void* stream);   /* up to CG_ROW_MAX_BATCH tensors per launch */
 /* out[c] += sum over batch and positions (bias gradients of the convolutions); `out` (C floats) zero on entry. */
 int cg_chan_sum(const float* x, const CgView4* xv, float* out, void* stream);
 
@@ -99,7 +102,7 @@ typedef struct CgNormAct {
   const float* x;  CgView4 xv;
   float* y;        CgView4 yv;
   const float* pre;              /* (B,C) per-sample channel gate or NULL */
-  const float* add; CgView4 av;  /* addend or NULL */
+  const float* add; CgView4 av;  /* addend (same logical shape) or NULL */
   int add_post;                  /* 0: before the PReLU, 1: after it */
   int bn_mode;                   /* 0 none, 1 batch statistics, 2 running statistics */
   const double* stats;           /* [C][2], bn_mode 1 */
@@ -112,15 +115,16 @@ typedef struct CgNormAct {
   /* backward only */
   const float* dy; CgView4 dyv;
   float* dx; CgView4 dxv;
-  float* dadd; CgView4 dav;
-  float* dpre;
-  double* red;                   /* [2C + (alpha_n == 1 ? CG_ALPHA_SLOTS : alpha_n)] f64 scratch, zero on entry */
+  float* dadd; CgView4 dav;      /* gradient of a pre-activation addend (NULL: not needed) */
+  float* dpre;                   /* (B,C) or NULL */
+  double* red;                   /* [2C + (alpha_n == 1 ? CG_ALPHA_SLOTS : alpha_n)] f64 scratch, zero on entry: per channel sum g, sum g * xhat,
+                                    the slope sums behind them */
   float* dgamma; float* dbeta; float* dalpha;
   double* ystats;                /* forward, optional: [C][2] f64 sums of y (zero on entry) for the BatchNorm consuming y */
 } CgNormAct;
 int cg_norm_act_fwd(const CgNormAct* a, void* stream);
 int cg_norm_act_bwd(const CgNormAct* a, int need_reduce, void* stream);
-/* the same for up to 6 independent row problems per launch (branches of one block at the same depth) */
+/* the same for up to CG_ROW_MAX_BATCH independent row problems per launch (branches of one block at the same depth) */
 int cg_norm_act_fwd_many(const CgNormAct* arr, int n, void* stream);
 int cg_norm_act_bwd_many(const CgNormAct* arr, const int* need_reduce, int n, void* stream);
 /* pass 1 of the backward alone (channel sums, slope gradient) + dgamma / dbeta / dalpha: for a consumer that applies the BatchNorm / PReLU
@@ -136,14 +140,16 @@ int cg_reduce_bc_bwd(const float* dout, const int32_t* arg, int kind, float* dx,
 /* y = a (+ b) (+ c) on strided views: torch.cat slices (CISTGCN.py:77,378-380,388,468), halo
  * padding for the dilated FPN convolutions (:54-68), F.interpolate broadcast (:76), the tail
  * x[:, -1:] + x8^T + act (:595-597). */
-/* y = a[0] + ... + a[n-1] (n <= 8), same logical shape, any strides: sums the gradients of a multi-consumer tensor in one
+/* y = a[0] + ... + a[n-1] (n <= CG_SUM_MAX), same logical shape, any strides: sums the gradients of a multi-consumer tensor in one
  * launch (replaces autograd's one accumulation kernel per extra consumer) */
+#define CG_SUM_MAX 8
 typedef struct CgSumItem { const float* a; CgView4 av; } CgSumItem;
 int cg_sum_many(float* y, const CgView4* yv, const CgSumItem* items, int n, void* stream);
 int cg_add3(float* y, const CgView4* yv, const float* a, const CgView4* av, const float* b, const CgView4* bv,
             const float* c, const CgView4* cv, void* stream);
+#define CG_COPY_MAX 4
 typedef struct CgCopyItem { float* y; CgView4 yv; const float* a; CgView4 av; } CgCopyItem;
-int cg_copy_many(const CgCopyItem* items, int n, void* stream);   /* up to 4 strided copies (cat slices) per launch */
+int cg_copy_many(const CgCopyItem* items, int n, void* stream);   /* up to CG_COPY_MAX strided copies (cat slices) per launch */
 int cg_zero(void* p, long long bytes, void* stream);
 
 /* ---- stage kernels --------------------------------------------------------------------------------
@@ -209,26 +215,32 @@ int cg_stgcn_domain_bwd(const float* x, const float* adj, const float* W, const 
  * All tensors contiguous (B,C,T,V) / (B,C); C <= 64.  `stats` / `red_*` / `dWc_ws` are zeroed by the caller (slices of the
  * per-step arenas); BatchNorm bookkeeping (save mean / rstd, running statistics) as cg_norm_act. */
 typedef struct CgTailBN {
-  double* stats;                 /* [CG_STAT_REPLICAS][C][2] sums of this BatchNorm's input (train mode) */
+  double* stats;                 /* [CG_STAT_REPLICAS][C][2] {sum, sum of squares} of this BatchNorm's INPUT over batch and positions (train mode
+                                    only; zero before the producing phase) */
   const float* gamma; const float* beta;
   float* running_mean; float* running_var; long long* num_batches_tracked;
   float momentum, eps;
-  float* save;                   /* [2][C] mean, rstd used by the forward */
+  float* save;                   /* [2][C] mean, rstd used by the forward (written by the first phase that needs them, read by the later phases
+                                    and the backward) */
 } CgTailBN;
 typedef struct CgDstdTail {
   int B, C, T, V, train, pad0;
-  const float* y[2]; const float* r[2]; const float* w[2];
-  CgTailBN bn_t[2]; const float* alpha_d[2];
-  CgTailBN bn_p[2]; const float* alpha_p[2];
-  const float* Wc; CgTailBN bn_c; const float* alpha_c;
-  const float* gate; const float* bres;
+  const float* y[2];             /* tcn outputs of the space / time Domain_GCNN layer (B,C,T,V), pre-BatchNorm */
+  const float* r[2];             /* their residual addends (B,C,T,V): the block input or the residual conv + BN */
+  const float* w[2];             /* gates w1 / w2 (B,C) */
+  CgTailBN bn_t[2]; const float* alpha_d[2];      /* tcn.1 + layer PReLU */
+  CgTailBN bn_p[2]; const float* alpha_p[2];      /* prelu1 / prelu2 (BatchNorm + PReLU) */
+  const float* Wc; CgTailBN bn_c; const float* alpha_c;   /* compressor conv (C, 2C), BN, PReLU */
+  const float* gate; const float* bres;           /* SE gate (B,C), block residual (B,C,T,V) */
   float drop_p; unsigned int salt[2]; int pad1; const unsigned long long* seed;
-  float* h0; float* pooled; float* out; double* ostats;
-  float* tap_x[2]; float* tap_a[2]; float* tap_h;      /* optional: outputs of the five PReLUs (diagnostics) */
+  float* h0; float* pooled; float* out; double* ostats;      /* forward results (ostats optional: sums of out) */
+  float* tap_x[2]; float* tap_a[2]; float* tap_h;      /* optional taps (B,C,T,V): outputs of the layer PReLUs, of prelu1/2, of the compressor
+                                                          PReLU - not needed by the computation (diagnostics / branch records) */
+  /* backward */
   const float* dout; const float* dpooled; float* dgate;
-  double* red_c;
-  float* gp[2]; double* red_p[2];
-  float* dWc_ws; float* dWc;
+  double* red_c;                 /* [2C + CG_ALPHA_SLOTS] f64, zero on entry: channel sums, then the spread partial sums of d alpha */
+  float* gp[2]; double* red_p[2];    /* gradient in front of prelu1/2's BatchNorm (B,C,T,V); [2C + CG_ALPHA_SLOTS] f64 each, zero on entry */
+  float* dWc_ws; float* dWc;     /* cg_dstd_tail_ws_floats(C) zeroed scratch; (C, 2C) */
   float* dr[2]; float* dw[2]; double* red_t[2]; float* dy[2];
   float* dgamma_t[2]; float* dbeta_t[2]; float* dalpha_d[2];
   float* dgamma_p[2]; float* dbeta_p[2]; float* dalpha_p[2];
@@ -238,8 +250,9 @@ typedef struct CgDstdTail {
                                   * order - no pass over dout and h0, red_c need not be zero, the same bits from run to run */
   /* optional: the tcn BatchNorm's backward sums a phase early.  With `red_q` and T * V % 4 == 0 backward phase 4 writes dy as well and phase
    * 5 is replaced by phase 6 (the per-channel parameter gradients, one small launch); train mode then needs `fmom` from forward phase 1. */
-  double* fmom[2];               /* [CG_STAT_REPLICAS][C][4] f64, zero before forward phase 1 (train): moments of q = keep PReLU_d'(u) w */
-  double* red_q[2];              /* [CG_STAT_REPLICAS][C][2] f64, zero before backward phase 3 */
+  double* fmom[2];               /* [CG_STAT_REPLICAS][C][4] f64, zero before forward phase 1 (train): moments of q = keep PReLU_d'(u) w
+                                    (sums of q, q z, q yhat, q z yhat) */
+  double* red_q[2];              /* [CG_STAT_REPLICAS][C][2] f64, zero before backward phase 3: sums of q g_p, q g_p (y - mean_t) */
   int rs_shared, pad2;           /* with the above and r[0] == r[1] (else -1): phase 4 writes dr[0] = the sum of both residual gradients, dr[1] untouched */
 } CgDstdTail;
 int cg_dstd_tail_fwd(const CgDstdTail* t, int phase, void* stream);
@@ -289,17 +302,18 @@ long long cg_collapse_sums_ws_floats(int C, int rows);
 
 /* ---- dilated 3x3 convolutions of the time extrapolator, FPN CISTGCN.py:54-79: n <= 3 convolutions with padding = dilation =
  * dil[i] of ONE input (B,C,H,W) = (batch, frames, channels, joints).  A sample fits in LDS with its halo: forward, input gradient
- * (summed over the convolutions) and weight / bias gradients each walk whole samples.  Shapes outside cg_fpn_conv_supported:
- * CG_ESHAPE (the caller uses cg_contract_many). */
+ * (summed over the convolutions) and weight / bias gradients each walk whole samples.  H * W % 4 == 0, H * W <= 256, C <= 64, O <= 32 and the
+ * sample's halo image plus one weight matrix must fit in LDS; shapes outside cg_fpn_conv_supported: CG_ESHAPE (the caller uses cg_contract_many). */
 typedef struct CgFpnConv {
   int B, C, O, H, W, n;
   int dil[3]; int pad;
   const float* x; long long xs[3];     /* element strides of x: batch, channel, row; unit stride along W */
-  const float* w[3]; const float* bias[3];
-  float* y[3];
+  const float* w[3]; const float* bias[3];      /* (O,C,3,3); bias may be NULL */
+  float* y[3];                   /* (B,O,H,W) contiguous */
+  /* backward */
   const float* dy[3];
-  float* dx;
-  float* dw[3]; float* db[3];
+  float* dx;                     /* optional: sum over the convolutions */
+  float* dw[3]; float* db[3];    /* optional each */
   float* ws;                     /* cg_fpn_conv_ws_floats(B, C, O, n) floats of scratch */
 } CgFpnConv;
 int cg_fpn_conv_fwd(const CgFpnConv* t, void* stream);
@@ -310,19 +324,24 @@ long long cg_fpn_conv_ws_floats(int B, int C, int O, int n);
 /* ---- stacked pointwise maps of one input: the first convolutions of the Map2Adj towers of a block, CISTGCN.py:138-163 applied
  * to the normalised block input by :183-186 (up to four 1x1 convolutions of the same (B,C,T,V) tensor).  Forward: every y_i =
  * W_i x from one read of x, with the f64 channel sums of y_i (train-mode BatchNorm behind it).  Backward: dx = sum_i W_i^T dy_i and
- * every dW_i = dy_i x^T from one read of x and of each dy_i.  x (B,Cin,P) contiguous, P = T*V with P % 2 == 0 (rows of 16- or 8-byte alignment), Cin <= 128,
- * M_i <= 64, sum of ceil16(M_i) <= 128, (sum of ceil16(M_i) / 16) * ceil(Cin / 16) <= 32; other shapes: CG_ESHAPE (the caller uses cg_contract_many). */
-#define CG_PWM_MAXN 4
+ * every dW_i = dy_i x^T from one read of x and of each dy_i.  x (B,Cin,P) contiguous, P = T*V with P % 2 == 0 (rows of 16- or 8-byte alignment), Cin <= CG_PWM_MAXCIN,
+ * M_i <= CG_PWM_MAXM, sum of ceil16(M_i) <= CG_PWM_MAXROWS, (sum of ceil16(M_i) / 16) * ceil(Cin / 16) <= 32; other shapes: CG_ESHAPE (the caller
+ * uses cg_contract_many). */
+#define CG_PWM_MAXN 4        /* maps per launch */
+#define CG_PWM_MAXROWS 128   /* sum of the maps' output channels, each rounded up to 16 */
+#define CG_PWM_MAXCIN 128    /* input channels */
+#define CG_PWM_MAXM 64       /* output channels of one map */
 typedef struct CgPwMaps {
   int B, Cin, P, n;
   const float* x;
   const float* W[CG_PWM_MAXN]; int M[CG_PWM_MAXN];       /* (M_i, Cin) */
   float* y[CG_PWM_MAXN];                                 /* (B, M_i, P) */
   double* stats[CG_PWM_MAXN];                            /* all null, or [CG_STAT_REPLICAS][M_i][2] each, zero on entry */
+  /* backward */
   const float* dy[CG_PWM_MAXN];
-  float* dx;                                             /* (B, Cin, P) */
-  float* dW[CG_PWM_MAXN];
-  float* dW_ws;                                          /* cg_pointwise_maps_ws_floats(Cin) zeroed floats */
+  float* dx;                                             /* (B, Cin, P): sum over the maps of W_i^T dy_i */
+  float* dW[CG_PWM_MAXN];                                /* (M_i, Cin) */
+  float* dW_ws;                                          /* cg_pointwise_maps_ws_floats(Cin) zeroed floats (replicated accumulators) */
   const float* bias[CG_PWM_MAXN];                        /* optional (M_i): y_i = W_i x + bias_i (nn.Conv2d(..., 1) with bias: the residual maps) */
   float* db[CG_PWM_MAXN];                                /* backward, optional (M_i): bias gradient, sum of dy_i over batch and positions */
   /* backward, optional (all maps or none): BatchNorm2d + PReLU follow the maps (the Map2Adj towers, CISTGCN.py:138-141) and dy_i is the
@@ -331,7 +350,7 @@ typedef struct CgPwMaps {
   const float* yraw[CG_PWM_MAXN];
   const float* bn_save[CG_PWM_MAXN]; const float* bn_gamma[CG_PWM_MAXN]; const float* bn_beta[CG_PWM_MAXN];
   const double* bn_red[CG_PWM_MAXN]; const float* prelu[CG_PWM_MAXN];
-  int bn_train, pad;
+  int bn_train, pad;                                     /* 1: batch statistics (the sums enter dy), 0: running statistics */
 } CgPwMaps;
 int cg_pointwise_maps_fwd(const CgPwMaps* t, void* stream);
 int cg_pointwise_maps_bwd(const CgPwMaps* t, void* stream);
@@ -349,8 +368,9 @@ typedef struct CgAdjTail {
   const float* s; const float* q;
   const float* W0; CgTailBN bn; const float* alpha; const float* W4;
   float drop_p; unsigned int salt; const unsigned long long* seed;
-  float* e; float* adj;          /* (B,Kc,J,J) */
-  float* tap;                    /* optional (B,Kc,J,J): PReLU output (diagnostics) */
+  float* e; float* adj;          /* (B,Kc,J,J): first conv output (kept for the backward), the adjacency */
+  float* tap;                    /* optional (B,Kc,J,J): PReLU output (diagnostics / branch records) */
+  /* backward */
   const float* dadj; float* g; double* red;       /* g (B,Kc,J,J) scratch; red: cg_map2adj_tail_red_doubles(Kc) f64 words */
   float* ds; float* dq; float* part;   /* part: cg_map2adj_tail_part_floats(B, Kc, J) floats of scratch */
   float* dW0_ws; float* dW4_ws;  /* cg_map2adj_tail_ws_floats(Kc) / 2 floats each */
@@ -372,17 +392,18 @@ long long cg_map2adj_tail_red_doubles(int Kc);
 #define CG_BIN_MAXG 8
 typedef struct CgBlockInput {
   int B, C, T, V, train, ng;
-  const float* x;
-  CgTailBN bn;
-  float* xn;
-  float* rm; float* rq;
-  float* out;
-  const float* g[CG_BIN_MAXG];
-  const float* dout[2];
-  long long dout_ld[2];         /* row strides of dout[i] in floats */
-  float* pq;
-  float* gsum;
-  double* red;
+  const float* x;               /* (B,C,T,V) contiguous block input */
+  CgTailBN bn;                  /* global_norm; bn.stats: [CG_STAT_REPLICAS][C][2] f64 sums of x (train); bn.save [2][C] mean / rstd */
+  float* xn;                    /* (B,C,T,V) normalised input */
+  float* rm; float* rq;         /* (B,C,T) mean / centred sum of squares of every row of V joints of xn (kept for the backward) */
+  float* out;                   /* (B, 2 + 2T) block statistics of xn */
+  /* backward */
+  const float* g[CG_BIN_MAXG];  /* gradients with respect to xn from its consumers, (B,C,T,V) contiguous, ng of them (null entries skipped) */
+  const float* dout[2];         /* gradients of `out` from its (up to two) consumers, (B, 2 + 2T); null entries skipped */
+  long long dout_ld[2];         /* their row strides in floats (column slices of a wider tensor are taken as they are) */
+  float* pq;                    /* (B,C,T,2) scratch: slope / offset of the statistics' gradient per row */
+  float* gsum;                  /* (B,C,T,V) scratch: the summed gradient in front of the BatchNorm (eval mode: may alias dx) */
+  double* red;                  /* [CG_STAT_REPLICAS][C][2] f64, zero on entry */
   float* dx; float* dgamma; float* dbeta;
 } CgBlockInput;
 int cg_block_input_fwd(const CgBlockInput* t, void* stream);
@@ -392,32 +413,35 @@ int cg_block_input_supported(int B, int C, int T, int V);
 /* ---- tail of the gate paths of a DSTD_GC block, conv_s / conv_t slots 5-7 and map_s / map_t, CISTGCN.py:337-352 / :378-384 ------
  * per path: z (B,C) -> BatchNorm2d -> Dropout -> PReLU -> cat with the block statistics (B,S) -> Linear (C, C+S) -> BatchNorm1d -> Dropout ->
  * PReLU -> Linear (C,C) = the gate (B,C).  A workgroup owns sixteen samples;
- * two launches forward, three backward, for both paths (cut only at the batch statistics, which every workgroup computes itself).  C <= 64,
- * S <= 192 (cg_gate_head_supported; else CG_ESHAPE: cg_norm_act_* +
+ * two launches forward, three backward, for both paths (cut only at the batch statistics, which every workgroup computes itself).  C <= CG_GATE_MAXC,
+ * S <= CG_GATE_MAXS (cg_gate_head_supported; else CG_ESHAPE: cg_norm_act_* +
  * cg_copy_many + cg_contract_many).  Forward writes y (B,C: the first Linear's output, kept for the backward), w, both bn.save;
  * backward needs `scratch` = cg_gate_head_scratch_floats(B, C, S) floats and `red` = two zeroed f64 words per path, dWl / dW2 ZERO on entry
  * (accumulated with float atomics), and writes dz, dstats (B,S) and every parameter gradient. */
+#define CG_GATE_MAXC 64
+#define CG_GATE_MAXS 192
 typedef struct CgGatePath {
-  const float* z;
-  const float* stats; long long stats_ld;
-  CgTailBN bn2; const float* alpha2;
-  const float* Wl;
+  const float* z;               /* (B,C) contiguous: output of the joint-collapsing convolution conv_p[4] */
+  const float* stats; long long stats_ld;      /* (B,S) block statistics, S = 2 + 2T; row stride in floats */
+  CgTailBN bn2; const float* alpha2;           /* bn.stats unused (the kernel reduces over the batch itself); bn.save [2][C] */
+  const float* Wl;              /* (C, C+S) */
   CgTailBN bn3; const float* alpha3;
-  const float* W2;
-  unsigned int salt2, salt3;
-  float* y;
-  float* w;
-  float* tap2; float* tap3;
-  const float* dw;
-  float* dz;
-  float* dstats;
+  const float* W2;              /* (C, C) */
+  unsigned int salt2, salt3;    /* dropout site ids of the two Dropout layers */
+  float* y;                     /* (B,C) Linear output in front of bn3 (kept for the backward) */
+  float* w;                     /* (B,C) result */
+  float* tap2; float* tap3;     /* optional (B,C): the two PReLU outputs (diagnostics / branch records) */
+  /* backward */
+  const float* dw;              /* (B,C) */
+  float* dz;                    /* (B,C) */
+  float* dstats;                /* (B,S) contiguous */
   float* dWl; float* dW2;
   float* dgamma2; float* dbeta2; float* dalpha2; float* dgamma3; float* dbeta3; float* dalpha3;
-  float* scratch;
-  double* red;
+  float* scratch;               /* cg_gate_head_scratch_floats(B, C, S) floats (the gradients in front of the two BatchNorms) */
+  double* red;                  /* two f64 words, zero on entry (slope sums) */
 } CgGatePath;
 typedef struct CgGateHead {
-  int B, C, S, train, n, pad;
+  int B, C, S, train, n, pad;   /* n paths (1 or 2) */
   float drop_p; int pad2; const unsigned long long* seed;
   CgGatePath p[2];
 } CgGateHead;
@@ -428,33 +452,35 @@ long long cg_gate_head_scratch_floats(int B, int C, int S);
 
 /* ---- middle of a DSTD_GC block (csrc/block_mid.hip): CISTGCN.py:331-352 (conv_s|t slots 5-7 and the (1,V) convolution) and :138-163
  * (time_compress / joint_compress slots 4-6) --------------------------------------------------------------------------
- * up to six items, each x (B,C,L) -> BatchNorm2d -> Dropout [-> PReLU] = h, then
+ * up to CG_MID_MAXN items, each x (B,C,L) -> BatchNorm2d -> Dropout [-> PReLU] = h, then
  *   kind 0 (full):      y[b,o]   = sum_{c,l} W[o,c,l] h[b,c,l]     (B,O)
  *   kind 1 (pointwise): y[b,o,l] = sum_c W[o,c] h[b,c,l]           (B,O,L)
  * C, L, O <= 64.  One launch forward (train mode: bn.stats = the producer's replicated f64 sums of x, rows of stats_ld channels), two backward,
  * cut at the batch statistics.  Backward scratch per item (sizes from cg_block_mid_geometry, nothing has to be zero): g (B,C,L) floats, `part`
  * doubles, `wpart` floats.  No atomics: every gradient is the same from run to run.  sb_ / ns_ are filled in by the launcher. */
+#define CG_MID_MAXN 6
 typedef struct CgMidItem {
   int kind, C, L, O;
-  int sb_, ns_;
-  const float* x; long long x_ld;
-  CgTailBN bn; long long stats_ld;
-  const float* alpha;
-  const float* W;
+  int sb_, ns_;                 /* samples per slice, slices: filled in by the launcher (cg_block_mid_geometry) */
+  const float* x; long long x_ld;      /* (B,C,L), sample stride in floats (rows of C*L floats are dense) */
+  CgTailBN bn; long long stats_ld;     /* bn.stats: [CG_STAT_REPLICAS][stats_ld][2] f64 sums of x, this item's channels from c = 0 (train) */
+  const float* alpha;           /* optional single PReLU slope */
+  const float* W;               /* (O, C*L) | (O, C) */
   unsigned int salt; int pad;
-  float* y;
-  float* tap;
-  const float* dy;
-  float* dx;
+  float* y;                     /* (B,O) | (B,O,L) */
+  float* tap;                   /* optional (B,C,L): h (branch records) */
+  /* backward */
+  const float* dy;              /* like y */
+  float* dx;                    /* (B,C,L) dense */
   float* dW; float* dgamma; float* dbeta; float* dalpha;
-  float* g;
-  double* part;
-  float* wpart;
+  float* g;                     /* (B,C,L) scratch: the gradient in front of the BatchNorm */
+  double* part;                 /* [ns][2C+1] scratch, all written by launch 1 (see cg_block_mid_geometry) */
+  float* wpart;                 /* [ns][O*C*L | O*C] scratch, all written by launch 1 */
 } CgMidItem;
 typedef struct CgBlockMid {
   int B, train, n, pad;
   float drop_p; int pad2; const unsigned long long* seed;
-  CgMidItem it[6];
+  CgMidItem it[CG_MID_MAXN];
 } CgBlockMid;
 int cg_block_mid_fwd(const CgBlockMid* t, void* stream);
 int cg_block_mid_bwd(const CgBlockMid* t, void* stream);
@@ -467,23 +493,25 @@ int cg_block_mid_geometry(int B, int kind, int C, int L, int O, int* out);
  * Conv2d(1, C, 1, bias=False) -> BatchNorm2d(C) -> PReLU of the one-channel tensor x (B,1,T_out,3V), reduced over the positions:
  *   head 0 (context_conv1): y[0][b,c] = max_p z (first arg-max in `arg`), head 1 (context_conv3): y[1][b,c] = mean_p z.
  * The (B,C,P) activations are functions of x[b,p] and per-channel constants (batch statistics of w[c] x are w[c] mean(x),
- * w[c]^2 var(x)); they are never stored.  x (B,P) contiguous, C <= 64, P <= 16384 (else CG_ESHAPE: the caller composes the heads
+ * w[c]^2 var(x)); they are never stored.  x (B,P) contiguous, C <= CG_CTX_MAXC, P <= 16384 (else CG_ESHAPE: the caller composes the heads
  * from cg_pointwise_maps / cg_norm_act / cg_reduce_bc).  Train mode needs `xstats` = [CG_STAT_REPLICAS][1][2] f64 sums of x
  * (cg_chan_stats_many on the (B,1,P) view).  bn[h].save ([2][C]) and xsave ([2]) are written by the forward, read by the backward.
  * Backward: two launches (per-channel sums, then dx and the parameter gradients in closed form); `red`:
  * cg_context_heads_red_doubles(C) f64 words, zero on entry. */
+#define CG_CTX_MAXC 64
 typedef struct CgCtxHeads {
   int B, P, C, train;
   const float* x;
-  const double* xstats;
-  const float* w[2]; CgTailBN bn[2]; const float* alpha[2];
-  float* y[2];
-  int32_t* arg;
-  float* xsave;
+  const double* xstats;         /* train: [CG_STAT_REPLICAS][1][2] f64 {sum x, sum x^2} over batch and positions (cg_chan_stats_many) */
+  const float* w[2]; CgTailBN bn[2]; const float* alpha[2];      /* bn.save: [2][C] mean / rstd of the channel (written by the forward) */
+  float* y[2];                  /* (B,C) */
+  int32_t* arg;                 /* (B,C) first arg-max position of head 0 */
+  float* xsave;                 /* [2] mean and (biased) variance of x the forward used (train) */
   float* tap[2];                /* optional (B,C,P): the PReLU outputs (diagnostics / branch records) */
-  const float* dy[2];
-  double* red;
-  float* dx;
+  /* backward */
+  const float* dy[2];           /* (B,C) */
+  double* red;                  /* [CG_STAT_REPLICAS][2][C][3] f64, zero on entry: sum gu, sum gu * x, sum over the negative side of g * u */
+  float* dx;                    /* (B,P) */
   float* dw[2]; float* dgamma[2]; float* dbeta[2]; float* dalpha[2];
 } CgCtxHeads;
 int cg_context_heads_fwd(const CgCtxHeads* t, void* stream);
@@ -595,8 +623,20 @@ int cg_mpjpe_sample_bwd(const float* pred, const float* tgt, const float* w, flo
 typedef struct CgAttackStep {
   int B, T, V, mode, iterations, patience;
   float epsilon, mu;
-  const float* x0; float* x; const float* grad; float* g; const float* mask; const float* loss;
-  float* best; int* stall; int* active; float* w; int* queries; int* n_active; int* steps; int* frozen_at;
+  const float* x0;      /* (B,T,V,3) the clean input */
+  float* x;             /* (B,T,V,3) in: x_i, out: x_adv (= the next x_i) */
+  const float* grad;    /* (B,T,V,3) d(sum_b w_b loss_b)/dx_i */
+  float* g;             /* (B,T,V,3) momentum (MI-FGSM only) */
+  const float* mask;    /* (T,V) 1 = this joint of this frame may move; NULL = all */
+  const float* loss;    /* (B,) loss_b of this iteration */
+  float* best;          /* (B,) highest loss so far */
+  int* stall;           /* (B,) iterations without improvement */
+  int* active;          /* (B,) 1 while the sample is still optimised */
+  float* w;             /* (B,) upstream weight of the NEXT backward: 1/B while active, else 0 */
+  int* queries;         /* (B,) model calls spent on the sample */
+  int* n_active;        /* (1,) samples still active (for the host to poll) */
+  int* steps;           /* (B,) steps this sample has been through (each workgroup counts its own) */
+  int* frozen_at;       /* (B,) index of the step at whose end the sample froze, INT_MAX while it is active */
 } CgAttackStep;
 int cg_attack_step(const CgAttackStep* a, void* stream);
 long long cg_attack_step_max_floats(void);
@@ -611,8 +651,12 @@ long long cg_attack_step_max_floats(void);
  * (V*3) and are re-read per element beyond.  NULL x / grad / pred or a partial state: CG_EARG; a non-positive extent: CG_ESHAPE. */
 typedef struct CgDeepfoolStep {
   int B, T, To, V, patience, pad;
-  float* x; const float* grad; const float* pred; const float* mask; const float* loss;
-  float* best; int* stall; int* active; float* w; int* queries; int* n_active; int* steps; int* frozen_at;
+  float* x;             /* (B,T,V,3) in: x_i, out: x_adv (= the next x_i) */
+  const float* grad;    /* (B,T,V,3) d(sum_b w_b loss_b)/dx_i */
+  const float* pred;    /* (B,To,V,3) the prediction of the same forward pass */
+  const float* mask;    /* (T,V) 1 = this joint of this frame may move; NULL = all */
+  const float* loss;    /* (B,) loss_b of this iteration; NULL (with the eight below) = no bookkeeping, every sample steps */
+  float* best; int* stall; int* active; float* w; int* queries; int* n_active; int* steps; int* frozen_at;      /* as in CgAttackStep */
 } CgDeepfoolStep;
 int cg_deepfool_step(const CgDeepfoolStep* a, void* stream);
 
@@ -635,11 +679,12 @@ int cg_deepfool_step(const CgDeepfoolStep* a, void* stream);
  * pred / target (B,To,J,3), speeds (B,To,J) contiguous and never written; bones (Nb,2) joint indices in [0,J);
  * J <= 64, To >= 2, Nb >= 1, B >= 1, else CG_ESHAPE.  ws: cg_eval_metrics_ws_doubles(B,To,J) doubles (0 for an unsupported shape).
  * No floating-point atomics (the sums over the batch are added in a fixed order): two calls give the same bits. */
+#define CG_EM_METRICS 9
 typedef struct CgEvalMetrics {
   int B, To, J, Nb, frames, pad;
   const float* pred; const float* target; const float* speeds; const int32_t* bones;
-  float* out[9];
-  double* ws;
+  float* out[CG_EM_METRICS];
+  double* ws;               /* cg_eval_metrics_ws_doubles(B,To,J): [To*J] batch maxima | [7][B][To] per-frame sums */
 } CgEvalMetrics;
 int cg_eval_metrics(const CgEvalMetrics* a, void* stream);
 long long cg_eval_metrics_ws_doubles(int B, int To, int J);
@@ -662,13 +707,15 @@ long long cg_eval_metrics_ws_doubles(int B, int To, int J);
  * The last three are over 64-bin density histograms of the joint-to-joint distances inside a frame (convert_to_dists :39-48), grouped
  * by sample, frame index or first joint; the 65 edges run from 0 to the group's maximum over both tensors, edge k = fl32(k / 64) * max
  * in fp32, and the binned distances carry the reference's fp32 bits.  A group whose maximum is 0 (all its joints coincide) gives NaN
- * in these three.  counts: int32 [2][B][64] | [2][T][64] | [2][J][64] (0 adv, 1 orig), zero-filled here; gmax: [B] | [T] | [J].
+ * in these three.  counts: int32 [2][B][CG_AM_BINS] | [2][T][CG_AM_BINS] | [2][J][CG_AM_BINS] (0 adv, 1 orig), zero-filled here; gmax: [B] | [T] | [J].
  * adv / orig contiguous and never written; B >= 1, T >= 1, 2 <= J <= 64, else CG_ESHAPE.  ws: cg_attack_metrics_ws_doubles(B,T,J)
  * doubles (0 for an unsupported shape).  No floating-point atomics: two calls give the same bits. */
+#define CG_AM_OUT 33         /* 3 scalars + 3 families of ten */
+#define CG_AM_BINS 64        /* bins of the density histograms */
 typedef struct CgAttackMetrics {
   int B, T, J, pad;
   const float* adv; const float* orig;
-  float* out[33];
+  float* out[CG_AM_OUT];
   int32_t* counts; float* gmax;
   double* ws;
 } CgAttackMetrics;

@@ -8,6 +8,7 @@ import subprocess
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(os.path.dirname(HERE))
 CSRC = os.path.join(ROOT, "cistgcn_amd", "csrc")
+INCLUDE = os.path.join(ROOT, "include")      # cistgcn_hip.h, which csrc/cg_common.h includes
 # HIPEMU_SANITIZE=1: AddressSanitizer build of the very same sources (run python under LD_PRELOAD=$(g++ -print-file-name=libasan.so)
 # with ASAN_OPTIONS=detect_leaks=0); the GPU pool offers no device sanitizer, this is where out-of-bounds indexing is hunted.
 SANITIZE = os.environ.get("HIPEMU_SANITIZE", "0") == "1"
@@ -30,7 +31,8 @@ def build(force=False):
 def _build_locked(force):
     from concurrent.futures import ThreadPoolExecutor
     srcs = sorted(glob.glob(os.path.join(CSRC, "*.hip")))
-    hdrs = glob.glob(os.path.join(CSRC, "*.h")) + [os.path.join(HERE, "hip", "hip_runtime.h"), os.path.abspath(__file__)]
+    hdrs = glob.glob(os.path.join(CSRC, "*.h")) + [os.path.join(INCLUDE, "cistgcn_hip.h"), os.path.join(HERE, "hip", "hip_runtime.h"),
+                                                   os.path.abspath(__file__)]
     deps = srcs + hdrs + [os.path.join(HERE, "emu_runtime.cpp")]
     if not force and os.path.exists(OUT) and all(os.path.getmtime(p) <= os.path.getmtime(OUT) for p in deps):
         return OUT
@@ -43,7 +45,7 @@ def _build_locked(force):
         if not force and os.path.exists(o) and os.path.getmtime(o) > max(os.path.getmtime(s), hdr_time):
             return o, None
         cmd = ["g++", "-x", "c++", "-std=c++17", "-O1", "-g", "-fPIC", "-pthread", "-Wno-unknown-pragmas", "-Wno-attributes",
-               "-I", HERE, "-I", CSRC, "-c", s, "-o", o + ".tmp"] + (["-fsanitize=address", "-fno-omit-frame-pointer"] if SANITIZE else [])
+               "-I", HERE, "-I", CSRC, "-I", INCLUDE, "-c", s, "-o", o + ".tmp"] + (["-fsanitize=address", "-fno-omit-frame-pointer"] if SANITIZE else [])
         res = subprocess.run(cmd, capture_output=True, text=True)
         if res.returncode != 0:
             return o, "g++ failed on %s:\n%s" % (s, res.stderr[-4000:])
