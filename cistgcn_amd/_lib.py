@@ -35,6 +35,9 @@ LIMITS = {
     "CG_EM_METRICS": 9,          # outputs of cg_eval_metrics
     "CG_AM_OUT": 33,             # outputs of cg_attack_metrics,
     "CG_AM_BINS": 64,            # bins of its histograms
+    "CG_PERTURB_MAX_STEPS": 16,  # steps per cg_perturb_sequences launch, and the step kinds of its table:
+    "CG_PERTURB_ROTATION": 0, "CG_PERTURB_SCALE": 1, "CG_PERTURB_NOISE": 2, "CG_PERTURB_TRANSLATION": 3, "CG_PERTURB_FLIP": 4,
+    "CG_PERTURB_INVERT": 5,
 }
 STAT_REPLICAS = LIMITS["CG_STAT_REPLICAS"]
 ALPHA_SLOTS = LIMITS["CG_ALPHA_SLOTS"]
@@ -303,6 +306,7 @@ _SIGNATURES = {
     "cg_map2adj_tail_part_floats": [c_int, c_int, c_int],
     "cg_map2adj_tail_red_doubles": [c_int],
     "cg_augment_sequences": [P, P, P, P, P, P, P, P, P, P, c_int, c_int, c_int, c_int, P],
+    "cg_perturb_sequences": [P, POINTER(c_int), P, P, P, P, P, P, P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, P],
     "cg_map2adj_tail_geometry": [c_int, c_int, c_int, POINTER(c_int)],
     "cg_dstd_tail_geometry": [c_int, c_int, c_int, c_int, POINTER(c_int)],
     "cg_pointwise_maps_geometry": [c_int, c_int, c_int, c_int, POINTER(c_int), c_int, POINTER(c_int)],

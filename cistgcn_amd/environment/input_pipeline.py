@@ -10,7 +10,14 @@ numbers are drawn on the host with `np.random.uniform` in exactly the order the 
 the samples of the batch one after the other, so a seeded run reproduces the reference's augmentations; the data-dependent parts
 (centroids, extents, the rotation itself) run on the device.  `RandomNoise` (custom_transforms.py:350-400) and `RandomPoseInvers`
 (:301-347) are taken in their whole-sequence form; the `seq_idx` / `continuous` variants (unused by the shipped YAML) raise.
+
+`RobustnessTest(opt_trs)` is the other user of these transforms: the `robustness_test:` section of an evaluation YAML
+(`loaders/loader.py:75-127`), where every transform also has a frame window (`seq_idx`), may ramp in linearly (`continuous`) and
+persists behind its window or stops there (`keep`), and where the order of the kinds is no longer fixed.  It drives a second kernel
+that executes a step list (cg_perturb_sequences); the draws, the outputs and the two methods are those of `DeviceAugmentation`.
 """
+import ctypes
+
 import numpy as np
 import torch
 
@@ -189,6 +196,183 @@ class DeviceAugmentation:
         _lib.call("cg_augment_sequences", ops._ptr(raw), ops._ptr(params), ops._ptr(out["sample"]), ops._ptr(out["target"]),
                   ops._ptr(out["target_vel"]), ops._ptr(out["target_gvel"]), ops._ptr(proc), ops._ptr(out["sample_vel"]), ops._ptr(noise), ops._ptr(perm),
                   B, L, J, int(input_n), ops._stream(raw))
+        if keep_processed:
+            out["processed"] = proc
+        return out
+
+
+MAX_STEPS = _lib.LIMITS["CG_PERTURB_MAX_STEPS"]
+_KIND = {k: _lib.LIMITS["CG_PERTURB_" + k.upper()] for k in ("rotation", "scale", "noise", "translation", "flip", "invert")}
+
+
+class _WindowStep(_Step):
+    """a step of a `robustness_test:` section: `_Step` plus the frame window (None: the whole sequence) and its two switches"""
+
+    def __init__(self, kind, ranges, prob_threshold, seq_idx=None, continuous=False, keep=True):
+        _Step.__init__(self, kind, ranges, prob_threshold)
+        self.seq_idx = None if not seq_idx else tuple(int(v) for v in seq_idx)       # '' / [] / None: the whole sequence
+        if self.seq_idx is not None and len(self.seq_idx) != 2:
+            raise ValueError("robustness test %s: seq_idx must be [first, last + 1], got %r" % (kind, seq_idx))
+        self.continuous, self.keep = bool(continuous), bool(keep)
+
+
+class RobustnessTest:
+    """The transforms of a `robustness_test:` section (`evaluate_robustness.py` writes one per point of its sweep over
+    config/robustness-test-CISTGCN.yaml) on the device.  Takes the section object `loaders/loader.py::get_transformations` takes
+    and builds the same list in the same order (:46-127): random_flip, random_rotation, random_scale, random_noise,
+    random_translation (threshold 0.5, whole sequence), then rotation, scale, noise, translation, flip, pose_invers with their
+    `prob_threshold`, `seq_idx`, `continuous` and `keep`.  A kind may occur twice; an explicit flip after a translation is fine.
+    `draw` / `__call__` are those of `DeviceAugmentation`, so `DevicePrefetcher` takes either.
+
+    Where this differs from the reference, on purpose:
+      * scalars of either number type become degenerate intervals (`_range`); the reference's RandomScale / RandomTranslation
+        raise IndexError on an int scalar.  Falsy entries mean [0, 0] as there: `scale: {x: 1.2, y: 0, z: 0}` collapses y and z,
+        which is what the sweep produces.
+      * a window outside [0, L] or with first >= last + 1 is refused (ValueError) for every kind, when L is known; the
+        reference fails with a shape error for rotation / scale / noise / translation and silently clamps for flip / inversion.
+      * RandomPoseInvers swaps the joints inside the dataset's own array when it is the first transform; `raw` is never
+        written here.
+    """
+
+    def __init__(self, opt_trs=None):
+        self.steps = []
+        if opt_trs is None or opt_trs == "":
+            return
+
+        def section(name):
+            s = getattr(opt_trs, name, None)
+            return None if (s is None or s == "") else s
+
+        for name in ("random_flip", "random_rotation", "random_scale", "random_noise", "random_translation", "rotation", "scale", "noise",
+                     "translation", "flip", "pose_invers"):
+            s = section(name)
+            if s is None:
+                continue
+            rand = name.startswith("random_")
+            kind = name.replace("random_", "")
+            if name == "random_noise":                     # loader.py:65-67: a bare amplitude
+                self.steps.append(_WindowStep("noise", float(s), 0.5))
+                continue
+            # loader.py:46-74 leaves the four keywords at the constructors' defaults, :75-127 passes them
+            kw = {} if rand else {"seq_idx": getattr(s, "seq_idx", None), "keep": getattr(s, "keep", True)}
+            thr = 0.5 if rand else float(getattr(s, "prob_threshold", 0.5))
+            if kind == "pose_invers":
+                self.steps.append(_WindowStep("invert", H36M_INVERSE_PAIRS, thr, **kw))
+                continue
+            if kind == "flip":
+                self.steps.append(_WindowStep("flip", tuple(bool(getattr(s, a, "")) for a in "xyz"), thr, **kw))
+                continue
+            if not rand:
+                kw["continuous"] = getattr(s, "continuous", False)
+            if kind == "noise":
+                self.steps.append(_WindowStep("noise", float(s.noise), thr, **kw))
+                continue
+            if all(getattr(s, a, "") == "" for a in "xyz"):
+                continue                                   # the reference skips a transform whose three entries are ''
+            r = [_range(getattr(s, a, ""), "%s.%s" % (name, a)) for a in "xyz"]
+            self.steps.append(_WindowStep(kind, tuple(v if v is not None else (0.0, 0.0) for v in r), thr, **kw))
+        self._check_count()
+
+    def _check_count(self):
+        if len(self.steps) > MAX_STEPS:
+            raise ValueError("robustness test: %d steps, the kernel takes %d" % (len(self.steps), MAX_STEPS))
+
+    @property
+    def needs_joints(self):
+        return any(st.kind in ("noise", "invert") for st in self.steps)
+
+    @property
+    def n_noise(self):
+        return sum(st.kind == "noise" for st in self.steps)
+
+    def draw(self, batch, rng=None, joints=None):
+        """(batch, n_steps, 4) float32 rows [apply?, v0, v1, v2] (with a RandomNoise step: a dict {"params", "noise"}, noise
+        (batch, n_noise, joints, 3), and `joints` is required).  Consumes `rng.uniform` (default: the global `np.random`, which the
+        reference's transforms use) exactly where the reference does, sample by sample and step by step: one coin per step - for a
+        flip one coin per enabled axis - and, where the coin says 'apply' (coin > prob_threshold), the three amounts or the
+        (joints, 3) array."""
+        self._check_count()
+        rng = np.random if rng is None else rng
+        out = np.zeros((batch, len(self.steps), 4), dtype=np.float32)
+        n_noise = self.n_noise
+        if n_noise and joints is None:
+            raise ValueError("RobustnessTest.draw: RandomNoise draws one number per joint and axis: pass joints=")
+        noise = np.zeros((batch, n_noise, int(joints), 3), dtype=np.float32) if n_noise else None
+        for b in range(batch):
+            slot = 0
+            for i, st in enumerate(self.steps):
+                if st.kind == "flip":                      # custom_transforms.py:265, :275, :285
+                    for a in range(3):
+                        if st.ranges[a] and rng.uniform() > st.prob_threshold:
+                            out[b, i, 1 + a] = 1.0
+                    out[b, i, 0] = float(out[b, i, 1:].any())
+                    continue
+                if st.kind == "noise":
+                    slot += 1
+                if not (rng.uniform() > st.prob_threshold):
+                    continue
+                out[b, i, 0] = 1.0
+                if st.kind == "noise":                     # :372: one array draw of (joints, 3) numbers
+                    out[b, i, 1] = st.ranges
+                    noise[b, slot - 1] = np.asarray(rng.uniform(-1, 1, (int(joints), 3)), dtype=np.float64).astype(np.float32)
+                elif st.kind != "invert":
+                    out[b, i, 1:] = [np.float32(rng.uniform(lo, hi)) for lo, hi in st.ranges]
+        return {"params": out, "noise": noise} if n_noise else out
+
+    _perm = DeviceAugmentation._perm
+
+    def step_table(self, L):
+        """(n_steps, 6) int32 [kind, s0, s1, continuous, keep, noise slot] for sequences of L frames; ValueError for a window that
+        does not satisfy 0 <= s0 < s1 <= L"""
+        self._check_count()
+        tab = np.zeros((len(self.steps), 6), dtype=np.int32)
+        slot = 0
+        for i, st in enumerate(self.steps):
+            s0, s1 = (0, L) if st.seq_idx is None else st.seq_idx
+            if not (0 <= s0 < s1 <= L):
+                raise ValueError("robustness test %s: seq_idx [%d, %d] is not a window of a %d-frame sequence" % (st.kind, s0, s1, L))
+            tab[i] = (_KIND[st.kind], s0, s1, st.continuous, st.keep, slot if st.kind == "noise" else 0)
+            slot += st.kind == "noise"
+        return tab
+
+    def __call__(self, raw, input_n, params=None, keep_processed=False):
+        """raw: (B, L, J, 3) float32 on the HIP device.  Returns the dictionary `DeviceAugmentation.__call__` returns."""
+        ops._chk(raw, "raw")
+        if not raw.is_cuda and not _lib._host_pointers_ok:
+            raise ValueError("RobustnessTest runs on MI355X only: got a %s tensor (no CPU path exists)" % raw.device)
+        if raw.dim() != 4 or raw.shape[3] != 3:
+            raise ValueError("expected windows of shape (B, L, J, 3), got %s" % (tuple(raw.shape),))
+        raw = raw if raw.is_contiguous() else ops._copy(raw)
+        B, L, J, _ = raw.shape
+        tab = self.step_table(L)
+        n_steps, n_noise = len(self.steps), self.n_noise
+        if params is None:
+            params = self.draw(B, joints=J)
+        noise = None
+        if isinstance(params, dict):
+            params, noise = params["params"], params["noise"]
+        if n_noise:
+            if noise is None:
+                raise ValueError("the section has a RandomNoise step: pass the dictionary `draw` returns")
+            if isinstance(noise, np.ndarray):
+                noise = torch.from_numpy(np.ascontiguousarray(noise, dtype=np.float32)).to(raw.device, non_blocking=True)
+            if tuple(noise.shape) != (B, n_noise, J, 3):
+                raise ValueError("expected (%d, %d, %d, 3) noise draws" % (B, n_noise, J))
+        perm = self._perm(J, raw.device)
+        if isinstance(params, np.ndarray):
+            params = torch.from_numpy(np.ascontiguousarray(params, dtype=np.float32)).to(raw.device, non_blocking=True)
+        if tuple(params.shape) != (B, n_steps, 4):
+            raise ValueError("expected a (%d, %d, 4) parameter table" % (B, n_steps))
+        dev, f32 = raw.device, torch.float32
+        To = L - input_n
+        out = {"sample": torch.empty(B, input_n, J, 3, dtype=f32, device=dev), "target": torch.empty(B, To, J, 3, dtype=f32, device=dev),
+               "target_vel": torch.empty(B, To, J, 3, dtype=f32, device=dev), "target_gvel": torch.empty(B, To, J, 1, dtype=f32, device=dev),
+               "sample_vel": torch.empty(B, input_n, J, 3, dtype=f32, device=dev)}
+        proc = torch.empty(B, L, J, 3, dtype=f32, device=dev) if keep_processed else None
+        steps = (ctypes.c_int * max(1, tab.size))(*[int(v) for v in tab.reshape(-1)])
+        _lib.call("cg_perturb_sequences", ops._ptr(raw), steps, ops._ptr(params) if n_steps else None, ops._ptr(noise) if n_noise else None,
+                  ops._ptr(perm), ops._ptr(out["sample"]), ops._ptr(out["target"]), ops._ptr(out["target_vel"]), ops._ptr(out["target_gvel"]),
+                  ops._ptr(proc), ops._ptr(out["sample_vel"]), B, L, J, int(input_n), n_steps, n_noise, ops._stream(raw))
         if keep_processed:
             out["processed"] = proc
         return out

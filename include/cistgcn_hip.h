@@ -578,6 +578,49 @@ int cg_augment_sequences(const float* raw, const float* params, float* sample, f
                          float* target_gvel, float* processed, float* sample_vel, const float* noise_tab, const int32_t* perm,
                          int B, int L, int J, int input_n, void* stream);
 
+/* ---- robustness-test transforms (the `robustness_test:` section evaluate_robustness.py writes) ----------------------------------
+ * The same transform classes with their `seq_idx`, `continuous` and `keep` arguments (environment/custom_transforms.py:
+ * RandomRotation :50-78, RandomScale :127-153, RandomTranslation :202-231, RandomFlip :262-294, RandomPoseInvers :321-344,
+ * RandomNoise :370-392), in the order loaders/loader.py:46-127 builds them, and the same per-item tensors as cg_augment_sequences
+ * (loaders/h36m_motion_3d.py:94-108), for a whole batch in one launch.  The order of the transforms is data: the kernel executes
+ * a list of up to CG_PERTURB_MAX_STEPS steps; a kind may occur more than once.
+ *   steps     (n_steps,6) int on the HOST, the same for every sequence: [kind, s0, s1, continuous, keep, noise slot].  (A host
+ *             table, copied into the launch: it is validated here without reading device memory, and the call stays capturable.)
+ *   params    (B,n_steps,4) fp32 on the device: [apply?, v0, v1, v2] per sequence and step, drawn on the host in the reference's
+ *             order.  v by kind - rotation: the rotation vector in DEGREES (the kernel does Rodrigues' formula itself, in f64, per
+ *             frame); scale: the three factors; translation: the three rates; flip: per-axis 0/1; noise: the amplitude in v0;
+ *             inversion: unused.
+ *   noise_tab (B,n_noise,J,3) the U(-1,1) draws of RandomNoise, one slot per noise step (NULL when there is none)
+ *   perm      (J) the joint permutation of RandomPoseInvers as in cg_augment_sequences (NULL when no step inverts)
+ * A step owns the frame window [s0, s1), 0 <= s0 < s1 <= L ((0, L): the whole sequence).  With n = s1 - s0 its weight is
+ *   f(t) = 0 for t < s0;  continuous ? (t - s0) / (n - 1) : 1 for s0 <= t < s1 (n == 1 and continuous: 0, as
+ *   torch.linspace(0, v, 1) is [0]);  keep ? f(s1 - 1) : 0 for t >= s1.
+ * Every step takes its centroid / extent from the WHOLE current sequence, frames outside its window included:
+ *   rotation     p' = (p - c) R(t) + c, c the centroid of all L*J points, R(t) the matrix of the rotation vector f(t) * v (row-vector
+ *                convention as above); frames with f(t) == 0 are not touched
+ *   scale        p *= 1 + f(t) * (v - 1), about the origin (exactly v where f(t) == 1)
+ *   translation  p += f(t) * v * ext, ext = per-axis max - min over the sequence before the step
+ *   noise        p += f(t) * v0 * u[j][a] * ext[a]
+ *   flip         no ramp: frames of [s0, s1), and with keep those from s1 on, are mirrored about the one centroid of the step's input
+ *   inversion    no ramp: the joint permutation applies to frames [s0, s1), with keep to all frames >= s0.  It is applied while the
+ *                results are written, so it must be the LAST step (where loader.py puts it)
+ * With whole-sequence, non-continuous steps in the order flip, rotation, scale, noise, translation, inversion the results are
+ * bit-identical to cg_augment_sequences (given the rotation matrix the host computes there).  raw is never written.
+ * Returns -1 for a missing pointer (noise_tab / perm included when a step needs them), -2 for n_steps outside [0,
+ * CG_PERTURB_MAX_STEPS], a window that is not 0 <= s0 < s1 <= L, an unknown kind, an inversion that is not the last step, a noise
+ * slot outside [0, n_noise), or a sequence past the LDS bound of cg_augment_sequences (L*J*12 bytes <= 150 KiB).  n_steps == 0:
+ * the untouched window and its item tensors. */
+#define CG_PERTURB_MAX_STEPS 16
+#define CG_PERTURB_ROTATION 0
+#define CG_PERTURB_SCALE 1
+#define CG_PERTURB_NOISE 2
+#define CG_PERTURB_TRANSLATION 3
+#define CG_PERTURB_FLIP 4
+#define CG_PERTURB_INVERT 5
+int cg_perturb_sequences(const float* raw, const int* steps, const float* params, const float* noise_tab, const int32_t* perm,
+                         float* sample, float* target, float* target_vel, float* target_gvel, float* processed, float* sample_vel,
+                         int B, int L, int J, int input_n, int n_steps, int n_noise, void* stream);
+
 /* ---- optimizer on the flat parameter buffer -----------------------------------
  * torch.optim.Adam semantics (environment/utils.py:53-57): L2 weight decay added to the gradient,
  * bias-corrected moments; optional clip_grad_value_ (environment/train.py:97-98) and gradient
