@@ -398,9 +398,11 @@ class CISTGCN(nn.Module):
     @staticmethod
     def _map_groups(x, ws):
         """index groups of the 1x1 maps `ws` of x that `ops.pointwise_maps` takes in one launch each; None when one of them does not
-        fit the kernel at all.  The limits are the kernel's (csrc/tower_maps.hip, restated by `ops.pointwise_maps_ok`): at most four
-        maps and 128 stacked output rows per launch, every map rounded up to its 16-row tiles."""
-        max_maps, max_rows, tile = 4, 128, 16
+        fit the kernel at all.  The limits are the kernel's (CG_PWM_MAXN maps and CG_PWM_MAXROWS stacked output rows per launch,
+        include/cistgcn_hip.h; `ops.pointwise_maps_ok` checks the same two), every map rounded up to its 16-row tiles."""
+        lim = ops._lib.LIMITS
+        max_maps, max_rows = lim["CG_PWM_MAXN"], lim["CG_PWM_MAXROWS"]
+        tile = 16                      # output rows of one matrix-core tile of csrc/tower_maps.hip (the header names no constant for it)
         groups, rows = [], 0
         for i, w in enumerate(ws):
             if not ops.pointwise_maps_ok(x, [w]):

@@ -2,6 +2,20 @@
 libcistgcn_hip.so.  PyTorch supplies device memory, streams and the autograd tape; every number
 is produced by a HIP kernel.  Views (permute / reshape / slicing) are metadata only: all kernels
 take strides, so layout changes of the reference (`CISTGCN.py:582,588,592,595`) cost nothing.
+
+An operator fills the argument block of its kernel (a struct of `_lib`, declared in include/cistgcn_hip.h) and launches through
+`_lib.call`.  A fused operator has a `_block(...)` that fills what its forward and its backward both read; each of the two adds its
+own outputs and scratch.  The pieces of a block that recur are filled in one place each (section "plumbing"):
+
+  operand of a raw-pointer kernel     `_dense` (float32 or TypeError, strided -> copied by a kernel); `_contig` where the site has
+                                      checked the type already or takes other types
+  BatchNorm record (CgTailBN)         `_tail_bn`;  BatchNorm / PReLU of a CgNormAct: `_na_fill_fwd` / `_na_fill_bwd`
+  f64 channel sums (BatchNorm input)  `_sums`; of a tensor no kernel has summed yet: `_chan_stats`
+  f64 sums of a BatchNorm / PReLU backward   `_red`
+  dropout probability and seed        `_dropout`
+  train mode on a single value        `_check_train_size`
+  an output that got no gradient      `_upstream`
+  the tuple `backward` returns        `_mask`;  saved tensors back into their groups: `_split`
 """
 import ctypes
 import os
@@ -16,7 +30,8 @@ _vp = ctypes.c_void_p
 
 
 # ----------------------------------------------------------------------------------------------
-# plumbing
+# plumbing: pointers, streams and operand checks; the step scratch (`_arena`, zero pools) and the dropout seed; then the helpers
+# that fill the recurring pieces of an argument block (listed in the module docstring)
 # ----------------------------------------------------------------------------------------------
 def _ptr(t):
     return _vp(t.data_ptr()) if t is not None else None
@@ -36,10 +51,15 @@ def _chk(t, name="tensor"):
     return t
 
 
-def _dense(t, name="tensor"):
-    """The operand of a kernel that takes a raw pointer and no view: float32 (else TypeError), strided input is copied by a kernel."""
-    _chk(t, name)
+def _contig(t):
+    """The operand of a kernel that takes a raw pointer and no view: strided input is copied by a kernel.  No type check: for sites
+    that have made their own (or take other types than float32)."""
     return t if t.is_contiguous() else _copy(t)
+
+
+def _dense(t, name="tensor"):
+    """`_contig` of a float32 tensor (else TypeError)."""
+    return _contig(_chk(t, name))
 
 
 def _view4(t):
@@ -226,6 +246,83 @@ def begin_step(device, bump_seed=False):
         _seed_epochs[device] = _seed_epochs.get(device, 0) + 1
 
 
+def _sums(dev, C):
+    """Step scratch for the f64 (sum, sum of squares) of C channels as the kernels accumulate them: CG_STAT_REPLICAS copies."""
+    return _arena(dev).take(2 * C * _lib.STAT_REPLICAS)
+
+
+def _red(dev, C, nalpha):
+    """Step scratch for the sums of a BatchNorm / PReLU backward over C channels (`red` of include/cistgcn_hip.h): two f64 words per
+    channel, then the slope sums - CG_ALPHA_SLOTS spread partial sums for ONE shared slope (nalpha 1), a word per slope for nalpha > 1,
+    none for nalpha 0.  `_NormActMany` passes the number of slopes it has (0 without PReLU).  `_TowerMaps` passes max(slopes, 1): a map
+    without PReLU runs with the constant slope `_one`, and its block is sized as the collapsing kernels would have left it.  Those
+    (`_Collapse._ask_sums`) and `_DstdTail` pass 1: their PReLUs share one slope by contract (`tower_maps_ok`, the tail's layout)."""
+    return _arena(dev).take(2 * C + (_lib.ALPHA_SLOTS if nalpha == 1 else nalpha))
+
+
+def _dropout(blk, cfg, dev):
+    """Dropout of a block with `drop_p` and `seed` fields: p = cfg["drop_p"] in train mode, else 0; the seed word only when p > 0 (with
+    p == 0 no kernel reads it).  Returns p.  The salts (site ids) sit in per-path / per-item records of most blocks: the caller's."""
+    p = float(cfg.get("drop_p", 0.0)) if cfg.get("train") else 0.0
+    blk.drop_p = p
+    if p > 0.0:
+        blk.seed = seed_state(dev).data_ptr()
+    return p
+
+
+def _chan_stats(x, pre=None, pending=None):
+    """f64 channel sums of x (times the gate `pre`) where no producer has left them: one cg_chan_stats_many problem, launched at once
+    or appended to `pending` for a launch shared with others.  Returns the sums."""
+    stats = _sums(x.device, x.shape[1])
+    it = _lib.StatsArgs()
+    it.x, it.xv, it.pre, it.stats = x.data_ptr(), _view4(x), _ptr(pre), stats.data_ptr()
+    if pending is not None:
+        pending.append(it)
+    else:
+        _lib.call("cg_chan_stats_many", (_lib.StatsArgs * 1)(it), 1, _stream(x))
+    return stats
+
+
+def _check_train_size(n, shape):
+    """train-mode BatchNorm over n values per channel: the error of torch.nn for n = 1"""
+    if n < 2:
+        raise ValueError("Expected more than 1 value per channel when training, got input size %s" % (tuple(shape),))
+
+
+def _upstream(d, shape, dev):
+    """The gradient of an output as a kernel reads it: pooled zeros where the output did not reach the loss, contiguous."""
+    if d is None:
+        d = _zeros(int(np.prod(shape)), dev)[0].view(shape)
+    return _contig(d)
+
+
+def _mask(ctx, grads, k0):
+    """`grads` of the inputs k0, k0 + 1, ... of a Function, None where the input needs none"""
+    return tuple(g if (g is not None and ctx.needs_input_grad[k0 + k]) else None for k, g in enumerate(grads))
+
+
+def _split(flat, *counts):
+    """consecutive runs of `flat` (saved tensors, flattened arguments) of the given lengths"""
+    out, at = [], 0
+    for c in counts:
+        out.append(flat[at:at + c])
+        at += c
+    return out
+
+
+def _tail_bn(dst, bn, stats, save, train, tracked=None):
+    """Fill a CgTailBN from the parameter holder `bn`: `stats` the f64 sums of the input (train-mode forward; None: eval mode, a backward,
+    or the caller points `dst.stats` into a producer's sums itself), `save` the (mean, rstd) pair the forward writes and the backward reads.
+    num_batches_tracked is passed in train mode only, as only then a kernel advances it; `tracked=True` passes it regardless
+    (`_Collapse._block`: the deferred BatchNorm of `tower_maps`, whose record has always carried it)."""
+    dst.stats = stats.data_ptr() if stats is not None else None
+    dst.gamma, dst.beta = bn.weight.data_ptr(), bn.bias.data_ptr()
+    dst.running_mean, dst.running_var = bn.running_mean.data_ptr(), bn.running_var.data_ptr()
+    dst.num_batches_tracked = bn.num_batches_tracked.data_ptr() if (train if tracked is None else tracked) else None
+    dst.momentum, dst.eps = bn.momentum, bn.eps
+    dst.save = save.data_ptr()
+
+
 # ----------------------------------------------------------------------------------------------
 # generic contraction
 # ----------------------------------------------------------------------------------------------
@@ -364,7 +461,7 @@ def _contract_prepare(spec, a, x, bias=None, bias_label=None, sizes=None, sa=Non
     r.y, r.zero, r.stats, r.tag, r.chained = y, (p.splitk > 1 and not kred), None, spec, False
     r.ws_floats = p.ws_floats
     if stats_label is not None and p.splitk == 1 and p.mode != 2:
-        r.stats = _arena(x.device).take(2 * sizes[stats_label] * _lib.STAT_REPLICAS)   # replicated f64 channel sums of y
+        r.stats = _sums(x.device, sizes[stats_label])                                  # replicated f64 channel sums of y
     d = _lib.ContractDesc()
     d.A, d.X, d.Y, d.tab = a.data_ptr(), x.data_ptr(), y.data_ptr(), p.tables.data_ptr()
     d.bias = bias.data_ptr() if bias is not None else None
@@ -481,7 +578,7 @@ def _bias(bias, bias_label, spec, a, x):
     n = a.shape[la.index(bias_label)] if bias_label in la else x.shape[lx.index(bias_label)] if bias_label and bias_label in lx else None
     if bias.dim() != 1 or bias.numel() != n:
         raise ValueError("contract: bias of shape %s along index %r of %s" % (tuple(bias.shape), bias_label, spec))
-    return bias if bias.is_contiguous() else _copy(bias)
+    return _contig(bias)
 
 
 class _ContractMany(torch.autograd.Function):
@@ -672,8 +769,7 @@ def _na_fill_fwd(a, x, pre, add, gamma, beta, alpha, cfg, pending_stats):
         save = torch.empty(2, C, dtype=torch.float32, device=dev)
         a.save_mean, a.save_rstd = save[0].data_ptr(), save[1].data_ptr()
         if train:
-            if B * P <= 1:
-                raise ValueError("Expected more than 1 value per channel when training, got input size %s" % (tuple(x.shape),))
+            _check_train_size(B * P, x.shape)
             stats = cfg.get("stats")
             if stats is not None:
                 if stats.dtype != torch.float64:
@@ -681,23 +777,76 @@ def _na_fill_fwd(a, x, pre, add, gamma, beta, alpha, cfg, pending_stats):
                 if stats.numel() != 2 * C * _lib.STAT_REPLICAS or not stats.is_contiguous():
                     raise ValueError("norm_act: channel sums must be a contiguous tensor of 2 * %d * %d doubles" % (C, _lib.STAT_REPLICAS))
             if stats is None:
-                stats = _arena(dev).take(2 * C * _lib.STAT_REPLICAS)
-                it = _lib.StatsArgs()
-                it.x, it.xv, it.pre, it.stats = x.data_ptr(), v, (pre.data_ptr() if pre is not None else None), stats.data_ptr()
-                pending_stats.append(it)
+                stats = _chan_stats(x, pre, pending_stats)
             a.stats = stats.data_ptr()
-    p = float(cfg.get("drop_p", 0.0)) if cfg.get("train") else 0.0
+    p = _dropout(a, cfg, dev)
     if p > 0.0:
-        a.drop_p, a.seed, a.salt = p, seed_state(dev).data_ptr(), cfg["salt"]
+        a.salt = cfg["salt"]
     if alpha is not None:
         if _chk(alpha, "PReLU weight").numel() not in (1, C) or not alpha.is_contiguous():
             raise ValueError("norm_act: PReLU weight must be a contiguous tensor of 1 or %d slopes" % C)
         a.alpha, a.alpha_n = alpha.data_ptr(), alpha.numel()
     emitted = None
     if cfg.get("emit_stats"):
-        emitted = _arena(dev).take(2 * C * _lib.STAT_REPLICAS)
+        emitted = _sums(dev, C)
         a.ystats = emitted.data_ptr()
     return y, save, p, emitted
+
+
+def _na_fill_bwd(a, x, pre, add, gamma, beta, alpha, save, cfg, dy, need=(False, False, False), min_slopes=0):
+    """Fill a CgNormAct for the backward of a problem `_na_fill_fwd` filled: its operands, the saved statistics, the dropout of the
+    forward and the upstream gradient `dy`; no input sums and no num_batches_tracked (forward only).  `need`: which of dx, dpre, dadd to
+    allocate and point at - `_TowerMaps` wants none, its pointwise backward forms dx itself.  `min_slopes`: see `_red`.
+    Returns (1 if the problem has sums to reduce else 0, red, [dx, dpre, dadd, dgamma, dbeta, dalpha])."""
+    dev = x.device
+    v = _view4(x)
+    B, C = v.n[0], v.n[1]
+    f32 = torch.float32
+    a.x, a.xv = x.data_ptr(), v
+    if pre is not None:
+        a.pre = pre.data_ptr()
+    add_post = 1 if cfg.get("add_post") else 0
+    a.add_post = add_post
+    if add is not None:
+        a.add, a.av = add.data_ptr(), _view4(add)
+    bn = cfg.get("bn")
+    if bn is not None:
+        a.bn_mode = 1 if cfg["train"] else 2
+        a.gamma, a.beta = gamma.data_ptr(), beta.data_ptr()
+        a.running_mean, a.running_var = bn.running_mean.data_ptr(), bn.running_var.data_ptr()
+        a.momentum, a.eps = bn.momentum, bn.eps
+        a.save_mean, a.save_rstd = save[0].data_ptr(), save[1].data_ptr()
+    if _dropout(a, cfg, dev) > 0.0:
+        a.salt = cfg["salt"]
+    nalpha = 0
+    if alpha is not None:
+        nalpha = alpha.numel()
+        a.alpha, a.alpha_n = alpha.data_ptr(), nalpha
+    a.dy, a.dyv = dy.data_ptr(), _view4(dy)
+    dx = dpre = dadd = dgamma = dbeta = dalpha = red = None
+    if need[0]:
+        dx = torch.empty(x.shape, dtype=f32, device=dev)
+        a.dx, a.dxv = dx.data_ptr(), _view4(dx)
+    if pre is not None and need[1]:
+        dpre = torch.empty(B, C, dtype=f32, device=dev)
+        a.dpre = dpre.data_ptr()
+    if add is not None and need[2]:
+        if add_post:
+            dadd = dy
+        else:
+            dadd = torch.empty(add.shape, dtype=f32, device=dev)
+            a.dadd, a.dav = dadd.data_ptr(), _view4(dadd)
+    flag = 1 if (bn is not None or alpha is not None) else 0
+    if flag:
+        red = _red(dev, C, max(nalpha, min_slopes))
+        a.red = red.data_ptr()
+        if bn is not None:
+            dgamma, dbeta = torch.empty(C, dtype=f32, device=dev), torch.empty(C, dtype=f32, device=dev)
+            a.dgamma, a.dbeta = dgamma.data_ptr(), dbeta.data_ptr()
+        if alpha is not None:
+            dalpha = torch.empty(alpha.shape, dtype=f32, device=dev)
+            a.dalpha = dalpha.data_ptr()
+    return flag, red, [dx, dpre, dadd, dgamma, dbeta, dalpha]
 
 
 class _NormActMany(torch.autograd.Function):
@@ -709,7 +858,7 @@ class _NormActMany(torch.autograd.Function):
     def forward(ctx, cfgs, *ts):
         ctx.set_materialize_grads(False)      # emitted channel sums never receive a gradient
         n = len(cfgs)
-        six = [ts[6 * i:6 * i + 6] for i in range(n)]
+        six = _split(ts, *[6] * n)
         arr = (NormAct * n)()
         pending, ys, saves, ps, emitted = [], [], [], [], []
         for i in range(n):
@@ -722,7 +871,7 @@ class _NormActMany(torch.autograd.Function):
         for c0 in range(0, n, _ROW_BATCH):
             m = min(_ROW_BATCH, n - c0)
             _lib.call("cg_norm_act_fwd_many", ctypes.cast(ctypes.byref(arr[c0]), ctypes.POINTER(NormAct)), m, stream)
-        ctx.cfgs, ctx.ps, ctx.modes = cfgs, ps, [arr[i].bn_mode for i in range(n)]
+        ctx.cfgs = cfgs
         ctx.seed_epoch = seed_epoch(six[0][0].device) if any(p > 0.0 for p in ps) else None
         flat = []
         for i in range(n):
@@ -744,58 +893,10 @@ class _NormActMany(torch.autograd.Function):
         live = [i for i in range(n) if dys[i] is not None]
         if len(live) != n:
             raise RuntimeError("norm_act_many: an output was not used in the loss; call the problems separately")
-        for i in range(n):
-            x, pre, add, gamma, beta, alpha, save = saved[7 * i:7 * i + 7]
-            cfg, dy, a = ctx.cfgs[i], dys[i], arr[i]
-            dev = x.device
-            v = _view4(x)
-            B, C = v.n[0], v.n[1]
-            a.x, a.xv = x.data_ptr(), v
-            if pre is not None:
-                a.pre = pre.data_ptr()
-            add_post = 1 if cfg.get("add_post") else 0
-            a.add_post = add_post
-            if add is not None:
-                a.add, a.av = add.data_ptr(), _view4(add)
-            a.bn_mode = ctx.modes[i]
-            bn = cfg.get("bn")
-            if bn is not None:
-                a.gamma, a.beta = gamma.data_ptr(), beta.data_ptr()
-                a.running_mean, a.running_var = bn.running_mean.data_ptr(), bn.running_var.data_ptr()
-                a.momentum, a.eps = bn.momentum, bn.eps
-                a.save_mean, a.save_rstd = save[0].data_ptr(), save[1].data_ptr()
-            if ctx.ps[i] > 0.0:
-                a.drop_p, a.seed, a.salt = ctx.ps[i], seed_state(dev).data_ptr(), cfg["salt"]
-            nalpha = 0
-            if alpha is not None:
-                nalpha = alpha.numel()
-                a.alpha, a.alpha_n = alpha.data_ptr(), nalpha
-            a.dy, a.dyv = _chk(dy, "upstream gradient").data_ptr(), _view4(dy)
-            need = ctx.needs_input_grad[1 + 6 * i:7 + 6 * i]
-            dx = dpre = dadd = dgamma = dbeta = dalpha = None
-            if need[0]:
-                dx = torch.empty(x.shape, dtype=torch.float32, device=dev)
-                a.dx, a.dxv = dx.data_ptr(), _view4(dx)
-            if pre is not None and need[1]:
-                dpre = torch.empty(B, C, dtype=torch.float32, device=dev)
-                a.dpre = dpre.data_ptr()
-            if add is not None and need[2]:
-                if add_post:
-                    dadd = dy
-                else:
-                    dadd = torch.empty(add.shape, dtype=torch.float32, device=dev)
-                    a.dadd, a.dav = dadd.data_ptr(), _view4(dadd)
-            flags[i] = 1 if (bn is not None or alpha is not None) else 0
-            if flags[i]:
-                a.red = _arena(dev).take(2 * C + (_lib.ALPHA_SLOTS if nalpha == 1 else nalpha)).data_ptr()
-                if bn is not None:
-                    dgamma = torch.empty(C, dtype=torch.float32, device=dev)
-                    dbeta = torch.empty(C, dtype=torch.float32, device=dev)
-                    a.dgamma, a.dbeta = dgamma.data_ptr(), dbeta.data_ptr()
-                if alpha is not None:
-                    dalpha = torch.empty(alpha.shape, dtype=torch.float32, device=dev)
-                    a.dalpha = dalpha.data_ptr()
-            grads += [dx, dpre, dadd, dgamma, dbeta, dalpha]
+        for i, seven in enumerate(_split(saved, *[7] * n)):
+            flags[i], _, g = _na_fill_bwd(arr[i], *seven, ctx.cfgs[i], _chk(dys[i], "upstream gradient"),
+                                          need=ctx.needs_input_grad[1 + 6 * i:4 + 6 * i])
+            grads += g
         stream = _stream(saved[0])
         for c0 in range(0, n, _ROW_BATCH):
             m = min(_ROW_BATCH, n - c0)
@@ -1187,7 +1288,7 @@ class _FpnConvs(torch.autograd.Function):
     def forward(ctx, x, dils, *wb):
         ctx.set_materialize_grads(False)
         _chk(x)
-        ws = [w if w.is_contiguous() else _copy(w) for w in wb[0::2]]
+        ws = [_contig(w) for w in wb[0::2]]
         t = _FpnConvs._block(x, dils, ws)
         B, C, H, W = x.shape
         ys = [torch.empty(B, w.shape[0], H, W, dtype=torch.float32, device=x.device) for w in ws]
@@ -1204,7 +1305,7 @@ class _FpnConvs(torch.autograd.Function):
         n = len(ctx.dils)
         if any(d is None for d in dys):
             raise RuntimeError("dilated_convs: every output needs a gradient")
-        dys = [d if d.is_contiguous() else _copy(d) for d in dys]
+        dys = [_contig(d) for d in dys]
         t = _FpnConvs._block(x, ctx.dils, ws)
         dev = x.device
         dx = torch.empty(x.shape, dtype=torch.float32, device=dev) if ctx.needs_input_grad[0] else None
@@ -1216,10 +1317,7 @@ class _FpnConvs(torch.autograd.Function):
         t.dx, t.ws = _ptr(dx), zb.data_ptr()
         _lib.call("cg_fpn_conv_bwd", ctypes.byref(t), _stream(x))
         del dys
-        grads = []
-        for i in range(n):
-            grads += [dws[i] if ctx.needs_input_grad[2 + 2 * i] else None, dbs[i] if ctx.needs_input_grad[3 + 2 * i] else None]
-        return (dx, None) + tuple(grads)
+        return (dx, None) + _mask(ctx, [g for pair in zip(dws, dbs) for g in pair], 2)
 
 
 # ----------------------------------------------------------------------------------------------
@@ -1231,7 +1329,7 @@ class _FeatureLift(torch.autograd.Function):
         _chk(x)
         if x.dim() != 4 or x.shape[-1] != 3:
             raise ValueError("expected poses of shape (B, T, V, 3), got %s" % (tuple(x.shape),))
-        x = x if x.is_contiguous() else _copy(x)
+        x = _contig(x)
         B, T, V, _ = x.shape
         f = torch.empty(B, 10, T, V, dtype=torch.float32, device=x.device)
         _lib.call("cg_feature_lift_fwd", _ptr(x), _ptr(f), B, T, V, _stream(x))
@@ -1371,7 +1469,7 @@ def gather_joints(x, dim_used):
     dim_used = [int(v) for v in dim_used]
     if not dim_used or min(dim_used) < 0 or max(dim_used) >= x.shape[2]:
         raise IndexError("gather_joints: joint index out of range")
-    x = x if x.is_contiguous() else _copy(x)
+    x = _contig(x)
     B, T, J, _ = x.shape
     y = torch.empty(B, T, len(dim_used), 3, dtype=torch.float32, device=x.device)
     _lib.call("cg_gather_joints", _ptr(x), _ptr(y), _ptr(_index_tensor(dim_used, x.device)), B * T, J, len(dim_used), _stream(x))
@@ -1395,8 +1493,8 @@ def eval_scatter_mpjpe(pred, target, dim_used, dim_repeat_32=(), dim_repeat_22=(
         src[int(j)] = int(k)
     if max(src) >= J22:
         raise IndexError("eval_scatter_mpjpe: repeated joint index out of range")
-    pred = pred if pred.is_contiguous() else _copy(pred)
-    target = target if target.is_contiguous() else _copy(target)
+    pred = _contig(pred)
+    target = _contig(target)
     out = torch.empty_like(target)
     err = torch.empty(To, dtype=torch.float32, device=pred.device)
     _lib.call("cg_eval_scatter_mpjpe", _ptr(pred), _ptr(target), _ptr(out), _ptr(err), _ptr(_index_tensor(src, pred.device)),
@@ -1432,9 +1530,9 @@ def eval_metrics(pred, target, speeds, bones, reduce="frames"):
     if min(flat) < 0 or max(flat) >= J:
         raise IndexError("eval_metrics: bone joint index out of range for %d joints" % J)
     Nb = len(pairs)
-    pred = pred if pred.is_contiguous() else _copy(pred)
-    target = target if target.is_contiguous() else _copy(target)
-    speeds = speeds if speeds.is_contiguous() else _copy(speeds)
+    pred = _contig(pred)
+    target = _contig(target)
+    speeds = _contig(speeds)
     dev = pred.device
     if reduce == "frames":
         shapes = {k: (To - 1,) if k == "mve" else (To,) for k in EVAL_METRICS}
@@ -1482,8 +1580,8 @@ def _attack_metrics_flat(adv, orig):
     if B < 1 or T < 1 or J < 2 or J > 64:
         raise ValueError("attack_metrics: needs B >= 1, T >= 1 and 2 <= J <= 64, got B=%d T=%d J=%d" % (B, T, J))
     stream = _stream(adv)      # refuses host tensors before anything is allocated or launched
-    adv = adv if adv.is_contiguous() else _copy(adv)
-    orig = orig if orig.is_contiguous() else _copy(orig)
+    adv = _contig(adv)
+    orig = _contig(orig)
     dev = adv.device
     layout, n = _attack_metrics_layout(B, T, J)
     flat = torch.empty(n, dtype=torch.float32, device=dev)
@@ -1532,8 +1630,8 @@ class _Mpjpe(torch.autograd.Function):
         _chk(pred), _chk(target)
         if pred.shape != target.shape or pred.shape[-1] != 3:
             raise AssertionError("mpjpe: predicted %s vs target %s" % (tuple(pred.shape), tuple(target.shape)))
-        pred = pred if pred.is_contiguous() else _copy(pred)
-        target = target if target.is_contiguous() else _copy(target)
+        pred = _contig(pred)
+        target = _contig(target)
         loss = torch.empty((), dtype=torch.float32, device=pred.device)
         _lib.call("cg_mpjpe_fwd", _ptr(pred), _ptr(target), _ptr(loss), pred.numel() // 3, _stream(pred))
         ctx.save_for_backward(pred, target)
@@ -1559,8 +1657,8 @@ class _MpjpePerSample(torch.autograd.Function):
         _chk(pred), _chk(target)
         if pred.dim() != 4 or pred.shape != target.shape or pred.shape[-1] != 3:
             raise AssertionError("mpjpe_per_sample: predicted %s vs target %s, expected (B,To,V,3)" % (tuple(pred.shape), tuple(target.shape)))
-        pred = pred if pred.is_contiguous() else _copy(pred)
-        target = target if target.is_contiguous() else _copy(target)
+        pred = _contig(pred)
+        target = _contig(target)
         B = pred.shape[0]
         loss = torch.empty(B, dtype=torch.float32, device=pred.device)
         _lib.call("cg_mpjpe_sample_fwd", _ptr(pred), _ptr(target), _ptr(loss), B, pred.numel() // (3 * B), _stream(pred))
@@ -1574,7 +1672,7 @@ class _MpjpePerSample(torch.autograd.Function):
         _chk(w, "upstream gradient")
         if w.numel() != B:
             raise ValueError("mpjpe_per_sample: upstream gradient of %d elements for %d samples" % (w.numel(), B))
-        w = w.reshape(B) if w.is_contiguous() else _copy(w.reshape(B))
+        w = _contig(w.reshape(B))                       # (B,) like the loss: the reshape is a view
         d = torch.empty_like(pred)
         _lib.call("cg_mpjpe_sample_bwd", _ptr(pred), _ptr(target), _ptr(w), _ptr(d), B, pred.numel() // (3 * B), _stream(pred))
         return d, None
@@ -1709,7 +1807,7 @@ class _StgcnDomain(torch.autograd.Function):
         if tuple(adj.shape) != exp or w.numel() != Cout * Cin:
             raise ValueError("stgcn_domain: adjacency %s / weight %s do not match x %s" % (tuple(adj.shape), tuple(w.shape), tuple(x.shape)))
         y = torch.empty(B, Cout, T, V, dtype=torch.float32, device=x.device)
-        stats = _arena(x.device).take(2 * Cout * _lib.STAT_REPLICAS) if want_stats else None
+        stats = _sums(x.device, Cout) if want_stats else None
         _lib.call("cg_stgcn_domain_fwd", _ptr(x), _ptr(adj), _ptr(w), _ptr(bias), _ptr(y), _ptr(stats),
                   B, Cin, Cout, T, V, domain, _stream(x))
         ctx.domain = domain
@@ -1724,7 +1822,7 @@ class _StgcnDomain(torch.autograd.Function):
         x, adj, w = ctx.saved_tensors
         B, Cin, T, V = x.shape
         Cout = w.shape[0]
-        dy = dy if dy.is_contiguous() else _copy(dy)
+        dy = _contig(dy)
         dx = torch.empty_like(x)
         dadj = torch.empty_like(adj)
         dw = torch.empty_like(w)
@@ -1744,53 +1842,48 @@ def stgcn_domain(x, adj, w, bias, domain, want_stats=False):
 # ----------------------------------------------------------------------------------------------
 # tail of a DSTD_GC block as phase kernels (csrc/dstd_tail.hip)
 # ----------------------------------------------------------------------------------------------
-def _tail_bn(dst, bn, stats, save, train):
-    dst.stats = stats.data_ptr() if stats is not None else None
-    dst.gamma, dst.beta = bn.weight.data_ptr(), bn.bias.data_ptr()
-    dst.running_mean, dst.running_var = bn.running_mean.data_ptr(), bn.running_var.data_ptr()
-    dst.num_batches_tracked = bn.num_batches_tracked.data_ptr() if train else None
-    dst.momentum, dst.eps = bn.momentum, bn.eps
-    dst.save = save.data_ptr()
-
-
 class _DstdTail(torch.autograd.Function):
     """y_i (tcn outputs) -> block output, CISTGCN.py:266-269, :388, :305-309, :390 (see csrc/dstd_tail.hip).
     Tensor inputs: y1 y2 r1 r2 w1 w2 | g_t1 b_t1 a_d1 g_t2 b_t2 a_d2 | g_p1 b_p1 a_p1 g_p2 b_p2 a_p2 | Wc g_c b_c a_c |
     se_w1 se_w2 | bres."""
 
     @staticmethod
+    def _block(cfg, ts, saves, stats=None):
+        """What forward and backward both read.  `stats`: the f64 sums of the inputs of the five BatchNorms (tcn1, tcn2, prelu1, prelu2,
+        compressor) - the forward's; the backward passes none and fills the records as in eval mode (it reads the saved mean / rstd)."""
+        B, C, T, V = ts[0].shape
+        train = bool(cfg["train"])
+        t = _lib.DstdTail()
+        t.B, t.C, t.T, t.V, t.train = B, C, T, V, 1 if train else 0
+        t.y[0], t.y[1], t.r[0], t.r[1], t.w[0], t.w[1] = (v.data_ptr() for v in ts[:6])
+        for k, dst in enumerate((t.bn_t[0], t.bn_t[1], t.bn_p[0], t.bn_p[1], t.bn_c)):
+            _tail_bn(dst, cfg["bn"][k], stats[k] if stats is not None else None, saves[k], train and stats is not None)
+        t.alpha_d[0], t.alpha_d[1], t.alpha_p[0], t.alpha_p[1] = (ts[k].data_ptr() for k in (8, 11, 14, 17))
+        t.Wc, t.alpha_c, t.bres = ts[18].data_ptr(), ts[21].data_ptr(), ts[24].data_ptr()
+        p = _dropout(t, cfg, ts[0].device)
+        t.salt[0], t.salt[1] = cfg["salts"]
+        return t, p
+
+    @staticmethod
     def forward(ctx, cfg, *ts):
         ctx.set_materialize_grads(False)
-        (y1, y2, r1, r2, w1, w2, gt1, bt1, ad1, gt2, bt2, ad2, gp1, bp1, ap1, gp2, bp2, ap2, wc, gc, bc, ac, sw1, sw2, bres) = ts
-        for t in (y1, y2, r1, r2, w1, w2, bres):
+        y1, r1, r2, sw1, sw2 = ts[0], ts[2], ts[3], ts[22], ts[23]
+        for t in (*ts[:6], ts[24]):                                    # y1 y2 r1 r2 w1 w2 bres
             _chk(t)
             if not t.is_contiguous():
                 raise ValueError("dstd_tail expects contiguous tensors")
         B, C, T, V = y1.shape
         dev, train = y1.device, bool(cfg["train"])
         f32 = torch.float32
-        t = _lib.DstdTail()
-        t.B, t.C, t.T, t.V, t.train = B, C, T, V, 1 if train else 0
         saves = torch.empty(5, 2, C, dtype=f32, device=dev)           # tcn x2, prelu1/2, compressor: mean / rstd
-        t.y[0], t.y[1], t.r[0], t.r[1], t.w[0], t.w[1] = (v.data_ptr() for v in (y1, y2, r1, r2, w1, w2))
         arena = _arena(dev)
-        zst = [arena.take(2 * C * _lib.STAT_REPLICAS) for _ in range(2)] if train else [None, None]
-        hst = arena.take(2 * C * _lib.STAT_REPLICAS) if train else None
-        bns = cfg["bn"]                                                # (tcn1, tcn2, prelu1, prelu2, compressor) parameter holders
-        _tail_bn(t.bn_t[0], bns[0], cfg["ystats"][0], saves[0], train); _tail_bn(t.bn_t[1], bns[1], cfg["ystats"][1], saves[1], train)
-        _tail_bn(t.bn_p[0], bns[2], zst[0], saves[2], train); _tail_bn(t.bn_p[1], bns[3], zst[1], saves[3], train)
-        _tail_bn(t.bn_c, bns[4], hst, saves[4], train)
-        t.alpha_d[0], t.alpha_d[1], t.alpha_p[0], t.alpha_p[1] = ad1.data_ptr(), ad2.data_ptr(), ap1.data_ptr(), ap2.data_ptr()
-        t.Wc, t.alpha_c, t.bres = wc.data_ptr(), ac.data_ptr(), bres.data_ptr()
-        p = float(cfg.get("drop_p", 0.0)) if train else 0.0
-        t.drop_p = p
-        if p > 0.0:
-            t.seed = seed_state(dev).data_ptr()
-        t.salt[0], t.salt[1] = cfg["salts"]
+        zst = [_sums(dev, C) for _ in range(2)] if train else [None, None]
+        hst = _sums(dev, C) if train else None
+        t, p = _DstdTail._block(cfg, ts, saves, (*cfg["ystats"], *zst, hst))
         h0 = torch.empty(B, C, T, V, dtype=f32, device=dev)
         pooled = torch.empty(B, C, dtype=f32, device=dev)
         out = torch.empty(B, C, T, V, dtype=f32, device=dev)
-        ostats = arena.take(2 * C * _lib.STAT_REPLICAS) if cfg.get("emit_stats") else None
+        ostats = _sums(dev, C) if cfg.get("emit_stats") else None
         t.h0, t.pooled, t.out, t.ostats = h0.data_ptr(), pooled.data_ptr(), out.data_ptr(), _ptr(ostats)
         taps = cfg.get("taps")
         if taps is not None:                                           # branch records (diagnostics): five PReLU outputs
@@ -1813,7 +1906,7 @@ class _DstdTail(torch.autograd.Function):
         _lib.call("cg_se_gate_fwd", _ptr(pooled), _ptr(sw1), _ptr(sw2), _ptr(gate), B, C, H, stream)
         t.gate = gate.data_ptr()
         _lib.call("cg_dstd_tail_fwd", ctypes.byref(t), 4, stream)
-        ctx.cfg, ctx.p = cfg, p
+        ctx.cfg = cfg
         ctx.last_pass, ctx.has_fmom = last_pass, fmom is not None
         ctx.seed_epoch = seed_epoch(dev) if p > 0.0 else None
         ctx.save_for_backward(*ts, h0, pooled, gate, saves, *([fmom] if fmom is not None else []))
@@ -1823,27 +1916,16 @@ class _DstdTail(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dout, _=None):
-        sv = ctx.saved_tensors
-        (y1, y2, r1, r2, w1, w2, gt1, bt1, ad1, gt2, bt2, ad2, gp1, bp1, ap1, gp2, bp2, ap2, wc, gc, bc, ac, sw1, sw2, bres) = sv[:25]
-        h0, pooled, gate, saves = sv[25:29]
-        fmom = sv[29] if ctx.has_fmom else None
+        ts, (h0, pooled, gate, saves), rest = _split(ctx.saved_tensors, 25, 4, 1)
+        y1, wc, sw1, sw2 = ts[0], ts[18], ts[22], ts[23]
+        fmom = rest[0] if ctx.has_fmom else None
         cfg = ctx.cfg
         _check_seed_epoch(ctx, y1.device, "dstd_tail")
         B, C, T, V = y1.shape
-        dev, train, f32 = y1.device, bool(cfg["train"]), torch.float32
-        dout = dout if dout.is_contiguous() else _copy(dout)
-        t = _lib.DstdTail()
-        t.B, t.C, t.T, t.V, t.train = B, C, T, V, 1 if train else 0
-        t.y[0], t.y[1], t.r[0], t.r[1], t.w[0], t.w[1] = (v.data_ptr() for v in (y1, y2, r1, r2, w1, w2))
-        bns = cfg["bn"]
-        for dst, bn, k in ((t.bn_t[0], bns[0], 0), (t.bn_t[1], bns[1], 1), (t.bn_p[0], bns[2], 2), (t.bn_p[1], bns[3], 3), (t.bn_c, bns[4], 4)):
-            _tail_bn(dst, bn, None, saves[k], False)
-        t.alpha_d[0], t.alpha_d[1], t.alpha_p[0], t.alpha_p[1] = ad1.data_ptr(), ad2.data_ptr(), ap1.data_ptr(), ap2.data_ptr()
-        t.Wc, t.alpha_c, t.bres, t.gate, t.h0 = wc.data_ptr(), ac.data_ptr(), bres.data_ptr(), gate.data_ptr(), h0.data_ptr()
-        t.drop_p = ctx.p
-        if ctx.p > 0.0:
-            t.seed = seed_state(dev).data_ptr()
-        t.salt[0], t.salt[1] = cfg["salts"]
+        dev, f32 = y1.device, torch.float32
+        dout = _contig(dout)
+        t, _ = _DstdTail._block(cfg, ts, saves)
+        t.gate, t.h0 = gate.data_ptr(), h0.data_ptr()
         t.dout = dout.data_ptr()
         stream = _stream(y1)
         dgate = torch.empty(B, C, dtype=f32, device=dev)
@@ -1860,9 +1942,9 @@ class _DstdTail(torch.autograd.Function):
         _lib.call("cg_se_gate_bwd", _ptr(pooled), _ptr(sw1), _ptr(sw2), _ptr(gate), _ptr(dgate), _ptr(dpooled), _ptr(dsw1), _ptr(dsw2),
                   B, C, H, 1, stream)
         arena = _arena(dev)
-        red_c = arena.take(2 * C + _lib.ALPHA_SLOTS)
-        red_p = [arena.take(2 * C + _lib.ALPHA_SLOTS) for _ in range(2)]
-        red_t = [arena.take(2 * C + _lib.ALPHA_SLOTS) for _ in range(2)]
+        red_c = _red(dev, C, 1)
+        red_p = [_red(dev, C, 1) for _ in range(2)]
+        red_t = [_red(dev, C, 1) for _ in range(2)]
         shared = ctx.last_pass and bool(cfg.get("rs_shared"))          # identity residual: one summed gradient, written once
         big = [None if (k == 3 and shared) else torch.empty(B, C, T, V, dtype=f32, device=dev) for k in range(6)]      # gp x2, dr x2, dy x2
         dws = [torch.empty(B, C, dtype=f32, device=dev) for _ in range(2)]
@@ -1894,7 +1976,7 @@ class _DstdTail(torch.autograd.Function):
                  small[0], small[1], al(10), small[2], small[3], al(11),
                  small[4], small[5], al(12), small[6], small[7], al(13),
                  dwc.view(wc.shape), small[8], small[9], al(14), dsw1, dsw2, dout)
-        return (None,) + tuple(g if ctx.needs_input_grad[1 + k] else None for k, g in enumerate(grads))
+        return (None,) + _mask(ctx, grads, 1)
 
 
 def dstd_tail(ys, ystats, rs, ws, bns, alphas, wc, se, bres, train, drop_p=0.0, salts=(0, 0), emit_stats=False, taps=None, tail_sums=True,
@@ -1924,11 +2006,13 @@ class _Map2AdjTail(torch.autograd.Function):
     Tensor inputs per tower: s q W0 gamma beta alpha W4."""
 
     @staticmethod
-    def _items(cfg, ts, train, saves, stats, e, dev, p):
+    def _items(cfg, ts, saves, stats, e):
+        """One CgAdjTail per tower, what forward and backward both read; `stats`: the f64 sums the forward's first phase fills (train mode),
+        None in eval mode and in the backward.  Returns (items, dropout probability)."""
         n = len(ts) // 7
+        train = bool(cfg["train"])
         items = (_lib.AdjTail * n)()
-        for i in range(n):
-            s, q, w0, gamma, beta, alpha, w4 = ts[7 * i:7 * i + 7]
+        for i, (s, q, w0, gamma, beta, alpha, w4) in enumerate(_split(ts, *[7] * n)):
             B, V, T = s.shape
             t = items[i]
             dom = cfg["domains"][i]
@@ -1936,11 +2020,10 @@ class _Map2AdjTail(torch.autograd.Function):
             t.Kc, t.J = (V, T) if dom == 0 else (T, V)
             t.s, t.q, t.W0, t.alpha, t.W4 = s.data_ptr(), q.data_ptr(), w0.data_ptr(), alpha.data_ptr(), w4.data_ptr()
             _tail_bn(t.bn, cfg["bn"][i], stats[i] if stats is not None else None, saves[i], train and stats is not None)
-            t.drop_p, t.salt = p, cfg["salts"][i]
-            if p > 0.0:
-                t.seed = seed_state(dev).data_ptr()
+            p = _dropout(t, cfg, s.device)
+            t.salt = cfg["salts"][i]
             t.e = e[i].data_ptr()
-        return items
+        return items, p
 
     @staticmethod
     def forward(ctx, cfg, *ts):
@@ -1952,18 +2035,16 @@ class _Map2AdjTail(torch.autograd.Function):
                 if not t.is_contiguous():
                     raise ValueError("map2adj_tail expects contiguous tower outputs")
         dev, train, f32 = ts[0].device, bool(cfg["train"]), torch.float32
-        p = float(cfg.get("drop_p", 0.0)) if train else 0.0
-        arena = _arena(dev)
         shapes = []
         for i in range(n):
             B, V, T = ts[7 * i].shape
             Kc, J = (V, T) if cfg["domains"][i] == 0 else (T, V)
             shapes.append((B, Kc, J, J))
         saves = [torch.empty(2, sh[1], dtype=f32, device=dev) for sh in shapes]
-        stats = [arena.take(2 * sh[1] * _lib.STAT_REPLICAS) for sh in shapes] if train else None
+        stats = [_sums(dev, sh[1]) for sh in shapes] if train else None
         e = [torch.empty(sh, dtype=f32, device=dev) for sh in shapes]
         adj = [torch.empty(sh, dtype=f32, device=dev) for sh in shapes]
-        items = _Map2AdjTail._items(cfg, ts, train, saves, stats, e, dev, p)
+        items, p = _Map2AdjTail._items(cfg, ts, saves, stats, e)
         taps = cfg.get("taps")
         for i in range(n):
             items[i].adj = adj[i].data_ptr()
@@ -1973,7 +2054,7 @@ class _Map2AdjTail(torch.autograd.Function):
         stream = _stream(ts[0])
         for phase in (1, 2):
             _lib.call("cg_map2adj_tail_fwd", items, n, phase, stream)
-        ctx.cfg, ctx.p, ctx.n = cfg, p, n
+        ctx.cfg, ctx.n = cfg, n
         ctx.seed_epoch = seed_epoch(dev) if p > 0.0 else None
         ctx.save_for_backward(*ts, *e, *saves)
         return tuple(adj)
@@ -1981,14 +2062,13 @@ class _Map2AdjTail(torch.autograd.Function):
     @staticmethod
     def backward(ctx, *dadj):
         n, cfg = ctx.n, ctx.cfg
-        sv = ctx.saved_tensors
-        ts, e, saves = sv[:7 * n], sv[7 * n:8 * n], sv[8 * n:9 * n]
-        dev, train, f32 = ts[0].device, bool(cfg["train"]), torch.float32
+        ts, e, saves = _split(ctx.saved_tensors, 7 * n, n, n)
+        dev, f32 = ts[0].device, torch.float32
         if any(d is None for d in dadj):
             raise RuntimeError("map2adj_tail: every adjacency needs a gradient")
         _check_seed_epoch(ctx, dev, "map2adj_tail")
-        dadj = [d if d.is_contiguous() else _copy(d) for d in dadj]
-        items = _Map2AdjTail._items(cfg, ts, train, saves, None, e, dev, ctx.p)
+        dadj = [_contig(d) for d in dadj]
+        items, _ = _Map2AdjTail._items(cfg, ts, saves, None, e)
         arena = _arena(dev)
         grads, keep = [], []
         stream = _stream(ts[0])
@@ -2012,7 +2092,7 @@ class _Map2AdjTail(torch.autograd.Function):
         for phase in (1, 2):
             _lib.call("cg_map2adj_tail_bwd", items, n, phase, stream)
         del keep
-        return (None,) + tuple(g if ctx.needs_input_grad[1 + k] else None for k, g in enumerate(grads))
+        return (None,) + _mask(ctx, grads, 1)
 
 
 def map2adj_tail(seeds, expansors, train, drop_p=0.0, salts=(0, 0), taps=None):
@@ -2062,14 +2142,10 @@ class _BlockInput(torch.autograd.Function):
         t = _BlockInput._block(x, cfg["bn"], save, train)
         stream = _stream(x)
         if train:
-            if B * T * V <= 1:
-                raise ValueError("Expected more than 1 value per channel when training, got input size %s" % (tuple(x.shape),))
+            _check_train_size(B * T * V, x.shape)
             stats = cfg.get("stats")
             if stats is None:
-                stats = _arena(dev).take(2 * C * _lib.STAT_REPLICAS)
-                it = _lib.StatsArgs()
-                it.x, it.xv, it.pre, it.stats = x.data_ptr(), _view4(x), None, stats.data_ptr()
-                _lib.call("cg_chan_stats_many", (_lib.StatsArgs * 1)(it), 1, stream)
+                stats = _chan_stats(x)
             t.bn.stats = stats.data_ptr()
         xn = torch.empty_like(x)
         rows = torch.empty(2, B, C, T, dtype=f32, device=dev)
@@ -2091,7 +2167,7 @@ class _BlockInput(torch.autograd.Function):
             return None, None, None, None
         dev, f32 = x.device, torch.float32
         B, C, T, V = x.shape
-        gs = [g if g.is_contiguous() else _copy(g) for g in gs]
+        gs = [_contig(g) for g in gs]
         douts = [g if g.stride(1) == 1 else _copy(g) for g in douts]       # column slices of the gate inputs' gradient are taken as they are
         while len(gs) > _BLOCK_INPUT_MAXG:                      # more consumers than pointer slots: fold the tail first
             gs = gs[:_BLOCK_INPUT_MAXG - 1] + [_sum_tensors(gs[_BLOCK_INPUT_MAXG - 1:])]
@@ -2107,12 +2183,11 @@ class _BlockInput(torch.autograd.Function):
         gsum = torch.empty_like(x)
         dx = torch.empty_like(x)
         small = torch.empty(2, C, dtype=f32, device=dev)
-        red = _arena(dev).take(2 * C * _lib.STAT_REPLICAS)
+        red = _sums(dev, C)
         t.pq, t.gsum, t.red, t.dx, t.dgamma, t.dbeta = _ptr(pq), gsum.data_ptr(), red.data_ptr(), dx.data_ptr(), small[0].data_ptr(), small[1].data_ptr()
         _lib.call("cg_block_input_bwd", ctypes.byref(t), _stream(x))
         del gs, douts, gsum, pq
-        return (None, dx if ctx.needs_input_grad[1] else None, small[0] if ctx.needs_input_grad[2] else None,
-                small[1] if ctx.needs_input_grad[3] else None)
+        return (None,) + _mask(ctx, (dx, small[0], small[1]), 1)
 
 
 def block_input(x, bn, train, n, stats=None):
@@ -2133,17 +2208,14 @@ class _GateHead(torch.autograd.Function):
     Tensor inputs: per path z, stats, gamma2, beta2, alpha2, Wl, gamma3, beta3, alpha3, W2 (10 each)."""
 
     @staticmethod
-    def _block(cfg, ts, n, train, saves, ys, dev):
+    def _block(cfg, ts, n, saves, ys):
         B, C = ts[0].shape
         S = ts[1].shape[1]
+        train = bool(cfg["train"])
         t = _lib.GateHead()
         t.B, t.C, t.S, t.train, t.n = B, C, S, 1 if train else 0, n
-        p = float(cfg.get("drop_p", 0.0)) if train else 0.0
-        t.drop_p = p
-        if p > 0.0:
-            t.seed = seed_state(dev).data_ptr()
-        for i in range(n):
-            z, stats, g2, b2, a2, wl, g3, b3, a3, w2 = ts[10 * i:10 * i + 10]
+        p = _dropout(t, cfg, ts[0].device)
+        for i, (z, stats, g2, b2, a2, wl, g3, b3, a3, w2) in enumerate(_split(ts, *[10] * n)):
             q = t.p[i]
             q.z, q.stats, q.stats_ld = z.data_ptr(), stats.data_ptr(), stats.stride(0)
             _tail_bn(q.bn2, cfg["bn2"][i], None, saves[i][0], train)
@@ -2163,12 +2235,12 @@ class _GateHead(torch.autograd.Function):
             _chk(z), _chk(stats)
             if not z.is_contiguous() or stats.stride(1) != 1 or not ts[10 * i + 5].is_contiguous() or not ts[10 * i + 9].is_contiguous():
                 raise ValueError("gate_head expects contiguous z / weights and unit-stride statistics rows")
-            if train and B < 2:
-                raise ValueError("Expected more than 1 value per channel when training, got input size %s" % (tuple(z.shape),))
+            if train:
+                _check_train_size(B, z.shape)
         saves = [torch.empty(2, 2, C, dtype=f32, device=dev) for _ in range(n)]
         ys = [torch.empty(B, C, dtype=f32, device=dev) for _ in range(n)]
         ws = [torch.empty(B, C, dtype=f32, device=dev) for _ in range(n)]
-        t, p = _GateHead._block(cfg, ts, n, train, saves, ys, dev)
+        t, p = _GateHead._block(cfg, ts, n, saves, ys)
         taps = cfg.get("taps")
         for i in range(n):
             t.p[i].w = ws[i].data_ptr()
@@ -2176,7 +2248,7 @@ class _GateHead(torch.autograd.Function):
                 taps += [torch.empty(B, C, dtype=f32, device=dev), torch.empty(B, C, dtype=f32, device=dev)]
                 t.p[i].tap2, t.p[i].tap3 = taps[-2].data_ptr(), taps[-1].data_ptr()
         _lib.call("cg_gate_head_fwd", ctypes.byref(t), _stream(ts[0]))
-        ctx.cfg, ctx.n, ctx.p = cfg, n, p
+        ctx.cfg, ctx.n = cfg, n
         ctx.seed_epoch = seed_epoch(dev) if p > 0.0 else None
         ctx.save_for_backward(*ts, *ys, *saves)
         return tuple(ws)
@@ -2184,20 +2256,16 @@ class _GateHead(torch.autograd.Function):
     @staticmethod
     def backward(ctx, *dws):
         n, cfg = ctx.n, ctx.cfg
-        sv = ctx.saved_tensors
-        ts, ys, saves = sv[:10 * n], sv[10 * n:11 * n], sv[11 * n:12 * n]
-        dev, f32, train = ts[0].device, torch.float32, bool(cfg["train"])
+        ts, ys, saves = _split(ctx.saved_tensors, 10 * n, n, n)
+        dev, f32 = ts[0].device, torch.float32
         _check_seed_epoch(ctx, dev, "gate_head")
         B, C = ts[0].shape
         S = ts[1].shape[1]
-        t, _ = _GateHead._block(cfg, ts, n, train, saves, ys, dev)
+        t, _ = _GateHead._block(cfg, ts, n, saves, ys)
         keep, grads = [], []
         nscr = int(_lib.lib().cg_gate_head_scratch_floats(B, C, S))
         for i in range(n):
-            d = dws[i]
-            if d is None:
-                d = _zeros(B * C, dev)[0].view(B, C)
-            d = d if d.is_contiguous() else _copy(d)
+            d = _upstream(dws[i], (B, C), dev)
             dz = torch.empty(B, C, dtype=f32, device=dev)
             dst = torch.empty(B, S, dtype=f32, device=dev)
             zw, _ = _zeros(C * (C + S) + C * C, dev)                         # accumulated with float atomics over the chunks of the batch
@@ -2213,7 +2281,7 @@ class _GateHead(torch.autograd.Function):
                       small[3], small[4], small[5, :1].reshape(1), dw2.view(ts[10 * i + 9].shape)]
         _lib.call("cg_gate_head_bwd", ctypes.byref(t), _stream(ts[0]))
         del keep
-        return (None, None) + tuple(g if ctx.needs_input_grad[2 + k] else None for k, g in enumerate(grads))
+        return (None, None) + _mask(ctx, grads, 2)
 
 
 def gate_head(zs, stats, convs, maps, train, drop_p=0.0, salts=((0, 0), (0, 0)), taps=None):
@@ -2246,14 +2314,12 @@ class _BlockMid(torch.autograd.Function):
     (B,O) or pointwise (B,O,L).  Tensor inputs per item: x, gamma, beta, alpha (or None), W (5 each)."""
 
     @staticmethod
-    def _block(cfg, ts, saves, train, dev):
+    def _block(cfg, ts, saves):
         items = cfg["items"]
+        train = bool(cfg["train"])
         t = _lib.BlockMid()
         t.B, t.train, t.n = ts[0].shape[0], 1 if train else 0, len(items)
-        p = float(cfg.get("drop_p", 0.0)) if train else 0.0
-        t.drop_p = p
-        if p > 0.0:
-            t.seed = seed_state(dev).data_ptr()
+        p = _dropout(t, cfg, ts[0].device)
         for i, it in enumerate(items):
             x, _, _, a, w = ts[5 * i:5 * i + 5]
             q = t.it[i]
@@ -2281,14 +2347,13 @@ class _BlockMid(torch.autograd.Function):
                 raise ValueError("block_mid expects (B,C,L) inputs with dense samples")
             if w.numel() != w.shape[0] * C * (L if it["kind"] == 0 else 1):
                 raise ValueError("block_mid: weight %s does not fit input %s" % (tuple(w.shape), tuple(x.shape)))
-            if not w.is_contiguous():
-                ts[5 * i + 4] = _copy(w)
+            ts[5 * i + 4] = _contig(w)
             if train and it.get("stats") is None:
                 raise ValueError("block_mid needs the producer's channel sums in train mode")
-            if train and B * L < 2:
-                raise ValueError("Expected more than 1 value per channel when training, got input size %s" % (tuple(x.shape),))
+            if train:
+                _check_train_size(B * L, x.shape)
         saves = [torch.empty(2, ts[5 * i].shape[1], dtype=f32, device=dev) for i in range(len(items))]
-        t, p = _BlockMid._block(cfg, ts, saves, train, dev)
+        t, p = _BlockMid._block(cfg, ts, saves)
         taps = cfg.get("taps")
         ys = []
         for i, it in enumerate(items):
@@ -2299,7 +2364,7 @@ class _BlockMid(torch.autograd.Function):
                 taps.append(torch.empty(x.shape, dtype=f32, device=dev) if ts[5 * i + 3] is not None else None)
                 t.it[i].tap = _ptr(taps[-1])
         _lib.call("cg_block_mid_fwd", ctypes.byref(t), _stream(ts[0]))
-        ctx.cfg, ctx.p = cfg, p
+        ctx.cfg = cfg
         ctx.seed_epoch = seed_epoch(dev) if p > 0.0 else None
         ctx.has_alpha = [ts[5 * i + 3] is not None for i in range(len(items))]
         ctx.save_for_backward(*[v for v in ts if v is not None], *saves)
@@ -2310,23 +2375,19 @@ class _BlockMid(torch.autograd.Function):
         cfg = ctx.cfg
         items = cfg["items"]
         n = len(items)
-        sv = list(ctx.saved_tensors)
-        saves = sv[len(sv) - n:]
+        *runs, saves = _split(ctx.saved_tensors, *[5 if h else 4 for h in ctx.has_alpha], n)
         ts = []
-        for i in range(n):
-            ts += [sv.pop(0), sv.pop(0), sv.pop(0), sv.pop(0) if ctx.has_alpha[i] else None, sv.pop(0)]
-        dev, f32, train = ts[0].device, torch.float32, bool(cfg["train"])
+        for r, h in zip(runs, ctx.has_alpha):                                          # x gamma beta [alpha] W: None back where there is no PReLU
+            ts += list(r) if h else [*r[:3], None, r[3]]
+        dev, f32 = ts[0].device, torch.float32
         _check_seed_epoch(ctx, dev, "block_mid")
         B = ts[0].shape[0]
-        t, _ = _BlockMid._block(cfg, ts, saves, train, dev)
+        t, _ = _BlockMid._block(cfg, ts, saves)
         keep, grads = [], []
         for i, it in enumerate(items):
             x, _, _, a, w = ts[5 * i:5 * i + 5]
             C, L, O = x.shape[1], x.shape[2], w.shape[0]
-            d = dys[i]
-            if d is None:
-                d = _zeros(B * O * (1 if it["kind"] == 0 else L), dev)[0]
-            d = d if d.is_contiguous() else _copy(d)
+            d = _upstream(dys[i], (B, O) if it["kind"] == 0 else (B, O, L), dev)
             geo = _mid_geometry(B, it["kind"], C, L, O)
             dx = torch.empty(B, C, L, dtype=f32, device=dev)
             dw = torch.empty(w.shape, dtype=f32, device=dev)
@@ -2341,7 +2402,7 @@ class _BlockMid(torch.autograd.Function):
             grads += [dx, small[0], small[1], small[2, :1].reshape(a.shape) if a is not None else None, dw]
         _lib.call("cg_block_mid_bwd", ctypes.byref(t), _stream(ts[0]))
         del keep
-        return (None,) + tuple(g if (g is not None and ctx.needs_input_grad[1 + k]) else None for k, g in enumerate(grads))
+        return (None,) + _mask(ctx, grads, 1)
 
 
 def block_mid(items, train, drop_p=0.0, taps=None):
@@ -2390,13 +2451,8 @@ class _ContextHeads(torch.autograd.Function):
         t = _ContextHeads._block(x, ts, cfg["bn"], saves, train)
         stream = _stream(x)
         if train:
-            if B * H * W <= 1:
-                raise ValueError("Expected more than 1 value per channel when training, got input size %s" % (tuple(x.shape),))
-            xstats = _arena(dev).take(2 * _lib.STAT_REPLICAS)
-            it = _lib.StatsArgs()
-            it.x, it.xv, it.pre, it.stats = x.data_ptr(), _view4(x), None, xstats.data_ptr()
-            _lib.call("cg_chan_stats_many", (_lib.StatsArgs * 1)(it), 1, stream)
-            t.xstats = xstats.data_ptr()
+            _check_train_size(B * H * W, x.shape)
+            t.xstats = _chan_stats(x).data_ptr()                    # of the one input channel
         y = torch.empty(2, B, C, dtype=f32, device=dev)
         arg = torch.empty(B, C, dtype=torch.int32, device=dev)
         t.y[0], t.y[1], t.arg, t.xsave = y[0].data_ptr(), y[1].data_ptr(), arg.data_ptr(), xsave.data_ptr()
@@ -2413,8 +2469,7 @@ class _ContextHeads(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dy0, dy1):
-        sv = ctx.saved_tensors
-        x, ts, arg, saves, xsave = sv[0], sv[1:9], sv[9], sv[10], sv[11]
+        (x,), ts, (arg, saves, xsave) = _split(ctx.saved_tensors, 1, 8, 3)
         dev, f32, train = x.device, torch.float32, bool(ctx.cfg["train"])
         B, _, H, W = x.shape
         C = ts[0].numel()
@@ -2423,9 +2478,7 @@ class _ContextHeads(torch.autograd.Function):
         t.arg, t.xsave = arg.data_ptr(), xsave.data_ptr()
         dys = []
         for h, d in enumerate((dy0, dy1)):
-            if d is None:                                         # a head that does not reach the loss
-                d = _zeros(B * C, dev)[0].view(B, C)
-            d = d if d.is_contiguous() else _copy(d)
+            d = _upstream(d, (B, C), dev)                        # zeros for a head that does not reach the loss
             dys.append(d)
             t.dy[h] = d.data_ptr()
         red = _arena(dev).take(int(_lib.lib().cg_context_heads_red_doubles(C)))
@@ -2439,7 +2492,7 @@ class _ContextHeads(torch.autograd.Function):
         grads = []
         for h in range(2):
             grads += [small[h, 0].view(ts[4 * h].shape), small[h, 1], small[h, 2], small[h, 3, :1].reshape(1)]
-        return (None, dx if ctx.needs_input_grad[1] else None) + tuple(g if ctx.needs_input_grad[2 + k] else None for k, g in enumerate(grads))
+        return (None,) + _mask(ctx, [dx] + grads, 1)
 
 
 def context_heads(x, head_max, head_mean, train, taps=None):
@@ -2480,19 +2533,47 @@ class _PointwiseMaps(torch.autograd.Function):
         return t
 
     @staticmethod
-    def forward(ctx, want_stats, n, x, *wb):
-        ctx.set_materialize_grads(False)
+    def _launch_fwd(x, ws, bs, want_stats):
+        """The forward `_PointwiseMaps` and `_TowerMaps` share: weights and biases as the kernel reads them, the block, the outputs and
+        (where asked for) their f64 channel sums, the launch.  Returns (weights, biases, outputs, sums)."""
         _chk(x)
         B, C, H, W = x.shape
-        dev, f32 = x.device, torch.float32
-        ws = [w if w.is_contiguous() else _copy(w) for w in wb[:n]]
-        bs = [None if b is None else (b if b.is_contiguous() else _copy(b)) for b in wb[n:]]
+        dev = x.device
+        ws = [_contig(w) for w in ws]
+        bs = [None if b is None else _contig(b) for b in bs]
         t = _PointwiseMaps._block(x, ws, bs)
-        ys = [torch.empty(B, w.shape[0], H, W, dtype=f32, device=dev) for w in ws]
-        stats = [_arena(dev).take(2 * w.shape[0] * _lib.STAT_REPLICAS) for w in ws] if want_stats else [None] * len(ws)
+        ys = [torch.empty(B, w.shape[0], H, W, dtype=torch.float32, device=dev) for w in ws]
+        stats = [_sums(dev, w.shape[0]) for w in ws] if want_stats else [None] * len(ws)
         for i in range(len(ws)):
             t.y[i], t.stats[i] = ys[i].data_ptr(), _ptr(stats[i])
         _lib.call("cg_pointwise_maps_fwd", ctypes.byref(t), _stream(x))
+        return ws, bs, ys, stats
+
+    @staticmethod
+    def _launch_bwd(x, ws, dys, has_bias, undo=None, train=False):
+        """The backward both share: dx, dW_i and (where the map has a bias) db_i in one launch.  `undo[i]` = (raw map y_i, saved mean / rstd,
+        gamma, beta, BatchNorm-backward sums, slope): the BatchNorm (`train`: on batch statistics) and PReLU behind map i are undone while
+        dy_i is loaded (`_TowerMaps`).  Returns (dx, [dW_i], [db_i or None])."""
+        dev = x.device
+        t = _PointwiseMaps._block(x, ws, [None] * len(ws))
+        dx = torch.empty_like(x)
+        dws = [torch.empty_like(w) for w in ws]
+        dbs = [torch.empty(w.shape[0], dtype=torch.float32, device=dev) if hb else None for w, hb in zip(ws, has_bias)]
+        zb, _ = _zeros(int(_lib.lib().cg_pointwise_maps_ws_floats(x.shape[1])), dev)
+        for i in range(len(ws)):
+            t.dy[i], t.dW[i], t.db[i] = dys[i].data_ptr(), dws[i].data_ptr(), _ptr(dbs[i])
+            if undo is not None:
+                t.yraw[i], t.bn_save[i], t.bn_gamma[i], t.bn_beta[i], t.bn_red[i], t.prelu[i] = (v.data_ptr() for v in undo[i])
+        if undo is not None:
+            t.bn_train = 1 if train else 0
+        t.dx, t.dW_ws = dx.data_ptr(), zb.data_ptr()
+        _lib.call("cg_pointwise_maps_bwd", ctypes.byref(t), _stream(x))
+        return dx, dws, dbs
+
+    @staticmethod
+    def forward(ctx, want_stats, n, x, *wb):
+        ctx.set_materialize_grads(False)
+        ws, bs, ys, stats = _PointwiseMaps._launch_fwd(x, wb[:n], wb[n:], want_stats)
         ctx.save_for_backward(x, *ws)
         ctx.has_bias = [b is not None for b in bs]
         if want_stats:
@@ -2506,20 +2587,8 @@ class _PointwiseMaps(torch.autograd.Function):
         dys = grads[:n]
         if any(d is None for d in dys):
             raise RuntimeError("pointwise_maps: every map needs a gradient")
-        dys = [d if d.is_contiguous() else _copy(d) for d in dys]
-        dev, f32 = x.device, torch.float32
-        t = _PointwiseMaps._block(x, ws, [None] * n)
-        dx = torch.empty_like(x)
-        dws = [torch.empty_like(w) for w in ws]
-        dbs = [torch.empty(w.shape[0], dtype=f32, device=dev) if hb else None for w, hb in zip(ws, ctx.has_bias)]
-        zb, _ = _zeros(int(_lib.lib().cg_pointwise_maps_ws_floats(x.shape[1])), dev)
-        for i in range(n):
-            t.dy[i], t.dW[i], t.db[i] = dys[i].data_ptr(), dws[i].data_ptr(), _ptr(dbs[i])
-        t.dx, t.dW_ws = dx.data_ptr(), zb.data_ptr()
-        _lib.call("cg_pointwise_maps_bwd", ctypes.byref(t), _stream(x))
-        del dys
-        return (None, None, dx if ctx.needs_input_grad[2] else None) + tuple(dw if ctx.needs_input_grad[3 + i] else None for i, dw in enumerate(dws)) \
-            + tuple(db if (db is not None and ctx.needs_input_grad[3 + n + i]) else None for i, db in enumerate(dbs))
+        dx, dws, dbs = _PointwiseMaps._launch_bwd(x, ws, [_contig(d) for d in dys], ctx.has_bias)
+        return (None, None) + _mask(ctx, [dx, *dws, *dbs], 2)
 
 
 def pointwise_maps(x, weights, want_stats=False, biases=None):
@@ -2553,19 +2622,10 @@ class _TowerMaps(torch.autograd.Function):
     @staticmethod
     def forward(ctx, cfg, n, x, *ts):
         ctx.set_materialize_grads(False)
-        _chk(x)
-        B, C, H, W = x.shape
         dev, f32, train = x.device, torch.float32, bool(cfg["train"])
-        ws = [w if w.is_contiguous() else _copy(w) for w in ts[:n]]
-        gammas, betas, alphas = ts[n:2 * n], ts[2 * n:3 * n], ts[3 * n:4 * n]
-        bs = [None if b is None else (b if b.is_contiguous() else _copy(b)) for b in ts[4 * n:5 * n]]
-        t = _PointwiseMaps._block(x, ws, bs)
-        ys = [torch.empty(B, w.shape[0], H, W, dtype=f32, device=dev) for w in ws]
-        stats = [_arena(dev).take(2 * w.shape[0] * _lib.STAT_REPLICAS) for w in ws] if train else [None] * n
-        for i in range(n):
-            t.y[i], t.stats[i] = ys[i].data_ptr(), _ptr(stats[i])
+        ws, gammas, betas, alphas, bs = _split(ts, n, n, n, n, n)
+        ws, bs, ys, stats = _PointwiseMaps._launch_fwd(x, ws, bs, train)
         stream = _stream(x)
-        _lib.call("cg_pointwise_maps_fwd", ctypes.byref(t), stream)
         if cfg.get("defer") is not None:
             # the BatchNorm / PReLU of every map is applied by its consumer while it loads (collapse_rows / collapse_cols with `transform`):
             # the outputs handed on are the RAW maps, the consumers fill `save` (mean, rstd) and update the running statistics, and their
@@ -2595,16 +2655,13 @@ class _TowerMaps(torch.autograd.Function):
     @staticmethod
     def backward(ctx, *dhs):
         n, cfg = ctx.n, ctx.cfg
-        sv = ctx.saved_tensors
-        x, ws, gammas, betas, alphas, ys, saves = sv[0], sv[1:1 + n], sv[1 + n:1 + 2 * n], sv[1 + 2 * n:1 + 3 * n], sv[1 + 3 * n:1 + 4 * n], sv[1 + 4 * n:1 + 5 * n], sv[1 + 5 * n:1 + 6 * n]
+        (x,), ws, gammas, betas, alphas, ys, saves = _split(ctx.saved_tensors, 1, n, n, n, n, n, n)
         if any(d is None for d in dhs):
             raise RuntimeError("tower_maps: every map needs a gradient")
         if any(not tr["consumed"] for tr in getattr(ctx, "deferred", ())):
             raise RuntimeError("tower_maps(defer=True): a raw map was not consumed by collapse_rows / collapse_cols with its transform "
                                "(its BatchNorm statistics were never finalised)")
-        dhs = [d if d.is_contiguous() else _copy(d) for d in dhs]
-        dev, f32, train = x.device, torch.float32, bool(cfg["train"])
-        stream = _stream(x)
+        dhs = [_contig(d) for d in dhs]
         # pass 1: channel sums of the gradient in front of the BatchNorm, slope gradients, dgamma / dbeta - only for the maps whose
         # consumer's backward has not left them in the transform record (collapse_rows / collapse_cols form them on the way)
         done = [tr if "red" in tr else None for tr in getattr(ctx, "deferred", ())] or [None] * n
@@ -2612,46 +2669,16 @@ class _TowerMaps(torch.autograd.Function):
         arr = (NormAct * max(1, len(todo)))()
         reds, smalls = [None if d is None else d["red"] for d in done], [None if d is None else d["small"] for d in done]
         for j, i in enumerate(todo):
-            a, bn = arr[j], cfg["bn"][i]
-            M = ws[i].shape[0]
-            a.x, a.xv, a.dy, a.dyv = ys[i].data_ptr(), _view4(ys[i]), dhs[i].data_ptr(), _view4(dhs[i])
-            a.bn_mode = 1 if train else 2
-            a.gamma, a.beta = gammas[i].data_ptr(), betas[i].data_ptr()
-            a.running_mean, a.running_var = bn.running_mean.data_ptr(), bn.running_var.data_ptr()
-            a.momentum, a.eps = bn.momentum, bn.eps
-            a.save_mean, a.save_rstd = saves[i][0].data_ptr(), saves[i][1].data_ptr()
-            nal = alphas[i].numel() if ctx.has_alpha[i] else 0
-            if nal:
-                a.alpha, a.alpha_n = alphas[i].data_ptr(), nal
-            red = _arena(dev).take(2 * M + (_lib.ALPHA_SLOTS if nal <= 1 else nal))
-            small = torch.empty(3, M, dtype=f32, device=dev)
-            a.red, a.dgamma, a.dbeta = red.data_ptr(), small[0].data_ptr(), small[1].data_ptr()
-            if nal:
-                a.dalpha = small[2].data_ptr()
-            reds[i], smalls[i] = red, small
+            _, reds[i], g = _na_fill_bwd(arr[j], ys[i], None, None, gammas[i], betas[i], alphas[i] if ctx.has_alpha[i] else None, saves[i],
+                                         {"bn": cfg["bn"][i], "train": cfg["train"]}, dhs[i], min_slopes=1)
+            smalls[i] = g[3:]                                       # dgamma, dbeta, dalpha: indexed like the (3, M) block of a transform record
         if todo:
-            _lib.call("cg_norm_act_bwd_reduce_many", arr, len(todo), stream)
-        # pass 2: dx and dW_i (db_i) with BatchNorm / PReLU undone on load
-        t = _PointwiseMaps._block(x, ws, [None] * n)
-        dx = torch.empty_like(x)
-        dws = [torch.empty_like(w) for w in ws]
-        dbs = [torch.empty(w.shape[0], dtype=f32, device=dev) if hb else None for w, hb in zip(ws, ctx.has_bias)]
-        zb, _ = _zeros(int(_lib.lib().cg_pointwise_maps_ws_floats(x.shape[1])), dev)
-        for i in range(n):
-            t.dy[i], t.dW[i], t.db[i] = dhs[i].data_ptr(), dws[i].data_ptr(), _ptr(dbs[i])
-            t.yraw[i], t.bn_save[i], t.bn_gamma[i], t.bn_beta[i] = ys[i].data_ptr(), saves[i].data_ptr(), gammas[i].data_ptr(), betas[i].data_ptr()
-            t.bn_red[i], t.prelu[i] = reds[i].data_ptr(), alphas[i].data_ptr()           # slope 1 where there is no PReLU
-        t.bn_train = 1 if train else 0
-        t.dx, t.dW_ws = dx.data_ptr(), zb.data_ptr()
-        _lib.call("cg_pointwise_maps_bwd", ctypes.byref(t), stream)
-        del dhs
-        need = ctx.needs_input_grad
-        grads = [dx if need[2] else None] + [dws[i] if need[3 + i] else None for i in range(n)]
-        grads += [smalls[i][0] if need[3 + n + i] else None for i in range(n)]
-        grads += [smalls[i][1] if need[3 + 2 * n + i] else None for i in range(n)]
-        grads += [smalls[i][2, :1].reshape(alphas[i].shape) if (ctx.has_alpha[i] and need[3 + 3 * n + i]) else None for i in range(n)]
-        grads += [dbs[i] if (dbs[i] is not None and need[3 + 4 * n + i]) else None for i in range(n)]
-        return (None, None) + tuple(grads)
+            _lib.call("cg_norm_act_bwd_reduce_many", arr, len(todo), _stream(x))
+        # pass 2: dx and dW_i (db_i) with BatchNorm / PReLU undone on load (slope 1 where there is no PReLU)
+        undo = [(ys[i], saves[i], gammas[i], betas[i], reds[i], alphas[i]) for i in range(n)]
+        dx, dws, dbs = _PointwiseMaps._launch_bwd(x, ws, dhs, ctx.has_bias, undo, bool(cfg["train"]))
+        dalphas = [smalls[i][2][:1].reshape(alphas[i].shape) if ctx.has_alpha[i] else None for i in range(n)]
+        return (None, None) + _mask(ctx, [dx, *dws, *[sm[0] for sm in smalls], *[sm[1] for sm in smalls], *dalphas, *dbs], 2)
 
 
 def tower_maps_ok(x, weights, prelus):
@@ -2722,8 +2749,11 @@ def collapse_rows_ok(x, w):
     return w.shape[1] == C and w.shape[2] == T and V <= 32 and w.shape[0] <= 64 and (C * T) % 4 == 0
 
 
-class _CollapseRows(torch.autograd.Function):
-    """y[b,o,v] = sum_{c,t} w[o,c,t] x[b,c,t,v] (nn.Conv2d(C, O, (T,1)), CISTGCN.py:138-150 / :331-336), see csrc/collapse_rows.hip"""
+class _Collapse(torch.autograd.Function):
+    """The two collapsing convolutions of csrc/collapse_rows.hip; `axis` names the axis of x (B,C,T,V) that is summed away:
+    2: y[b,o,v] = sum_{c,t} w[o,c,t] x[b,c,t,v] (nn.Conv2d(C, O, (T,1)), CISTGCN.py:138-150 / :331-336), cg_collapse_rows_*;
+    3: y[b,o,t] = sum_{c,v} w[o,c,v] x[b,c,t,v] (nn.Conv2d(C, O, (1,V)), CISTGCN.py:152-163), cg_collapse_cols_*."""
+    KERNEL = {2: "cg_collapse_rows", 3: "cg_collapse_cols"}
 
     @staticmethod
     def _block(x, w, tr=None):
@@ -2732,13 +2762,9 @@ class _CollapseRows(torch.autograd.Function):
         t.B, t.C, t.T, t.V, t.O = B, C, T, V, w.shape[0]
         t.x, t.W = x.data_ptr(), w.data_ptr()
         if tr is not None:                                   # PReLU(BatchNorm(x)) applied on load (`tower_maps(..., defer=True)`)
-            bn = tr["bn"]
             tr["consumed"] = True                            # the consumer fills `save`: the producer's backward checks that there was one
             t.in_on, t.in_train = 1, 1 if tr["train"] else 0
-            t.in_bn.stats, t.in_bn.gamma, t.in_bn.beta = _ptr(tr["stats"]), tr["gamma"].data_ptr(), tr["beta"].data_ptr()
-            t.in_bn.running_mean, t.in_bn.running_var = bn.running_mean.data_ptr(), bn.running_var.data_ptr()
-            t.in_bn.num_batches_tracked = bn.num_batches_tracked.data_ptr()
-            t.in_bn.momentum, t.in_bn.eps, t.in_bn.save = bn.momentum, bn.eps, tr["save"].data_ptr()
+            _tail_bn(t.in_bn, tr["bn"], tr["stats"], tr["save"], tr["train"], tracked=True)
             t.in_alpha = tr["alpha"].data_ptr()
             if tr.get("want_tap") and "tap" not in tr:           # forward only: the activated input, for branch records (tests)
                 tr["tap"] = torch.empty_like(x)
@@ -2753,7 +2779,7 @@ class _CollapseRows(torch.autograd.Function):
         if tr is None or not tr.get("fuse_sums", True):
             return None
         C = x.shape[1]
-        red = _arena(x.device).take(2 * C + _lib.ALPHA_SLOTS)
+        red = _red(x.device, C, 1)
         small = torch.empty(3, C, dtype=torch.float32, device=x.device)
         sums = torch.empty(int(_lib.lib().cg_collapse_sums_ws_floats(C, rows)) // 2, dtype=torch.float64, device=x.device)      # per-slice partials, all written
         t.sums, t.red = sums.data_ptr(), red.data_ptr()
@@ -2762,18 +2788,17 @@ class _CollapseRows(torch.autograd.Function):
         return sums
 
     @staticmethod
-    def forward(ctx, want_stats, tr, x, w):
+    def forward(ctx, axis, want_stats, tr, x, w):
         ctx.set_materialize_grads(False)
         _chk(x)
-        w = w if w.is_contiguous() else _copy(w)
-        B, C, T, V = x.shape
+        w = _contig(w)
         O = w.shape[0]
-        t = _CollapseRows._block(x, w, tr)
-        ctx.tr = tr
-        y = torch.empty(B, O, V, dtype=torch.float32, device=x.device)
-        stats = _arena(x.device).take(2 * O * _lib.STAT_REPLICAS) if want_stats else None
+        t = _Collapse._block(x, w, tr)
+        ctx.tr, ctx.axis = tr, axis
+        y = torch.empty(x.shape[0], O, x.shape[5 - axis], dtype=torch.float32, device=x.device)      # the axis that stays
+        stats = _sums(x.device, O) if want_stats else None
         t.y, t.stats = y.data_ptr(), _ptr(stats)
-        _lib.call("cg_collapse_rows_fwd", ctypes.byref(t), _stream(x))
+        _lib.call(_Collapse.KERNEL[axis] + "_fwd", ctypes.byref(t), _stream(x))
         ctx.save_for_backward(x, w)
         if stats is not None:
             ctx.mark_non_differentiable(stats)
@@ -2783,24 +2808,24 @@ class _CollapseRows(torch.autograd.Function):
     def backward(ctx, dy, _=None):
         x, w = ctx.saved_tensors
         if dy is None:
-            return None, None, None, None
-        dy = dy if dy.is_contiguous() else _copy(dy)
-        B, C, T, V = x.shape
-        t = _CollapseRows._block(x, w, ctx.tr)
+            return None, None, None, None, None
+        dy = _contig(dy)
+        kernel, rows = _Collapse.KERNEL[ctx.axis], x.shape[ctx.axis]
+        t = _Collapse._block(x, w, ctx.tr)
         dx = torch.empty_like(x)
         dw = torch.empty_like(w)
-        zb = torch.empty(int(_lib.lib().cg_collapse_rows_ws_floats(C, T, w.shape[0])), dtype=torch.float32, device=x.device)      # per-slice dW partials, all written
+        zb = torch.empty(int(getattr(_lib.lib(), kernel + "_ws_floats")(x.shape[1], rows, w.shape[0])), dtype=torch.float32, device=x.device)      # per-slice dW partials, all written
         t.dy, t.dx, t.dW, t.ws = dy.data_ptr(), dx.data_ptr(), dw.data_ptr(), zb.data_ptr()
-        zs = _CollapseRows._ask_sums(t, ctx.tr, x, T)
-        _lib.call("cg_collapse_rows_bwd", ctypes.byref(t), _stream(x))
+        zs = _Collapse._ask_sums(t, ctx.tr, x, rows)
+        _lib.call(kernel + "_bwd", ctypes.byref(t), _stream(x))
         del zb, zs
-        return None, None, dx if ctx.needs_input_grad[2] else None, dw if ctx.needs_input_grad[3] else None
+        return (None, None, None) + _mask(ctx, (dx, dw), 3)
 
 
 def collapse_rows(x, w, want_stats=False, transform=None):
     """(y (B,O,V), f64 channel sums or None) of the frame-collapsing convolution w (O,C,T) of x (B,C,T,V); `transform`: x is a raw map of
     `tower_maps(..., defer=True)`, its BatchNorm + PReLU are applied on load."""
-    return _CollapseRows.apply(bool(want_stats), transform, x, w)
+    return _Collapse.apply(2, bool(want_stats), transform, x, w)
 
 
 def collapse_cols_ok(x, w):
@@ -2811,45 +2836,6 @@ def collapse_cols_ok(x, w):
     return w.shape[1] == C and w.shape[2] == V and T <= 64 and w.shape[0] <= 64 and (C * V) % 4 == 0 and C * T * V < 2 ** 31
 
 
-class _CollapseCols(torch.autograd.Function):
-    """y[b,o,t] = sum_{c,v} w[o,c,v] x[b,c,t,v] (nn.Conv2d(C, O, (1,V)), CISTGCN.py:152-163), see csrc/collapse_rows.hip"""
-
-    @staticmethod
-    def forward(ctx, want_stats, tr, x, w):
-        ctx.set_materialize_grads(False)
-        _chk(x)
-        w = w if w.is_contiguous() else _copy(w)
-        B, C, T, V = x.shape
-        O = w.shape[0]
-        t = _CollapseRows._block(x, w, tr)
-        ctx.tr = tr
-        y = torch.empty(B, O, T, dtype=torch.float32, device=x.device)
-        stats = _arena(x.device).take(2 * O * _lib.STAT_REPLICAS) if want_stats else None
-        t.y, t.stats = y.data_ptr(), _ptr(stats)
-        _lib.call("cg_collapse_cols_fwd", ctypes.byref(t), _stream(x))
-        ctx.save_for_backward(x, w)
-        if stats is not None:
-            ctx.mark_non_differentiable(stats)
-        return y, stats
-
-    @staticmethod
-    def backward(ctx, dy, _=None):
-        x, w = ctx.saved_tensors
-        if dy is None:
-            return None, None, None, None
-        dy = dy if dy.is_contiguous() else _copy(dy)
-        B, C, T, V = x.shape
-        t = _CollapseRows._block(x, w, ctx.tr)
-        dx = torch.empty_like(x)
-        dw = torch.empty_like(w)
-        zb = torch.empty(int(_lib.lib().cg_collapse_cols_ws_floats(C, V, w.shape[0])), dtype=torch.float32, device=x.device)      # per-slice dW partials, all written
-        t.dy, t.dx, t.dW, t.ws = dy.data_ptr(), dx.data_ptr(), dw.data_ptr(), zb.data_ptr()
-        zs = _CollapseRows._ask_sums(t, ctx.tr, x, V)
-        _lib.call("cg_collapse_cols_bwd", ctypes.byref(t), _stream(x))
-        del zb, zs
-        return None, None, dx if ctx.needs_input_grad[2] else None, dw if ctx.needs_input_grad[3] else None
-
-
 def collapse_cols(x, w, want_stats=False, transform=None):
     """(y (B,O,T), f64 channel sums or None) of the joint-collapsing convolution w (O,C,V) of x (B,C,T,V); `transform` as in `collapse_rows`."""
-    return _CollapseCols.apply(bool(want_stats), transform, x, w)
+    return _Collapse.apply(3, bool(want_stats), transform, x, w)
