@@ -38,6 +38,9 @@ LIMITS = {
     "CG_PERTURB_MAX_STEPS": 16,  # steps per cg_perturb_sequences launch, and the step kinds of its table:
     "CG_PERTURB_ROTATION": 0, "CG_PERTURB_SCALE": 1, "CG_PERTURB_NOISE": 2, "CG_PERTURB_TRANSLATION": 3, "CG_PERTURB_FLIP": 4,
     "CG_PERTURB_INVERT": 5,
+    # kinds of cg_motion_loss_*, the threads of its workgroups (64 per frame in flight) and the cap of its grid = f64 words of its scratch
+    "CG_LOSS_WEIGHTED_MPJPE": 0, "CG_LOSS_MPJPE_SOFT": 1, "CG_LOSS_WEIGHTED_MPJPE_SOFT": 2, "CG_LOSS_RMPJPE": 3,
+    "CG_LOSS_THREADS": 256, "CG_LOSS_MAX_BLOCKS": 512,
 }
 STAT_REPLICAS = LIMITS["CG_STAT_REPLICAS"]
 ALPHA_SLOTS = LIMITS["CG_ALPHA_SLOTS"]
@@ -224,6 +227,12 @@ class AttackMetricsArgs(ctypes.Structure):
                 ("adv", c_void_p), ("orig", c_void_p), ("out", c_void_p * 33), ("counts", c_void_p), ("gmax", c_void_p), ("ws", c_void_p)]
 
 
+class MotionLoss(ctypes.Structure):
+    _fields_ = [("kind", c_int), ("B", c_int), ("T", c_int), ("V", c_int), ("speed_factor", c_float), ("pad", c_int),
+                ("pred", c_void_p), ("target", c_void_p), ("w_full", c_void_p), ("w_frame", c_void_p), ("speeds", c_void_p),
+                ("part", c_void_p), ("loss", c_void_p), ("mean", c_void_p), ("gloss", c_void_p), ("dpred", c_void_p)]
+
+
 # A class mirrors the header's struct "Cg" + its own name, except these two.
 C_STRUCT_NAMES = {"EvalMetricsArgs": "CgEvalMetrics", "AttackMetricsArgs": "CgAttackMetrics"}
 
@@ -325,6 +334,8 @@ _SIGNATURES = {
     "cg_eval_metrics_ws_doubles": [c_int, c_int, c_int],
     "cg_attack_metrics": [POINTER(AttackMetricsArgs), P],
     "cg_attack_metrics_ws_doubles": [c_int, c_int, c_int],
+    "cg_motion_loss_fwd": [POINTER(MotionLoss), P],
+    "cg_motion_loss_bwd": [POINTER(MotionLoss), P],
     "cg_adam_flat": [P, P, P, P, LL, c_float, c_float, c_float, c_float, c_float, c_float, c_float, LL, P],
 }
 EXPORTS = tuple(sorted(_SIGNATURES))

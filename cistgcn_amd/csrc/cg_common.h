@@ -52,6 +52,8 @@ static inline hipError_t cg_lds_limit(const void* fn, size_t bytes) {
 // dynamic LDS a kernel may take before cg_lds_limit has to raise its limit
 #define CG_GLUE_THREADS 256
 #define CG_MPJPE_MAX_BLOCKS 1024               // cg_mpjpe_fwd: one float atomic per workgroup onto the loss
+// (cg_motion_loss_*, losses.hip: CG_LOSS_MAX_BLOCKS / CG_LOSS_THREADS are in cistgcn_hip.h - the caller sizes the scratch by them)
+#define CG_LOSS_WAVES (CG_LOSS_THREADS / CG_WAVE)     // frames one workgroup of cg_motion_loss_* has in flight
 #define CG_FLAT_MAX_BLOCKS 2048                // cg_adam_flat, cg_scale
 #define CG_ZERO_MAX_BLOCKS 4096                // cg_zero_fill, 16 bytes per thread and pass
 #define CG_SE_THREADS 256

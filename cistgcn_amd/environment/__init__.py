@@ -5,4 +5,5 @@ from .attacks import DEEPFOOL, FGSM, IFGSM, MIFGSM, NOATTACK, DeepFool, NoAttack
 from .checkpoint import load_params_from_model_path, make_checkpoint, save_ckpt  # noqa: F401
 from .evaluation import capture_interpretation, mpjpe_ms_table, save_interpretation  # noqa: F401
 from .evaluation import EvalMetrics  # noqa: F401
+from .losses import TrainingLoss, frame_weights, get_loss  # noqa: F401
 from .input_pipeline import DeviceAugmentation, DevicePrefetcher, RobustnessTest  # noqa: F401

@@ -1651,6 +1651,112 @@ def mpjpe(pred, target):
     return _Mpjpe.apply(pred, target)
 
 
+# kinds of cg_motion_loss_* (include/cistgcn_hip.h: CgMotionLoss); plain "mpjpe" is `mpjpe` above
+LOSS_KINDS = {k: _lib.LIMITS["CG_LOSS_" + k.upper()] for k in ("weighted_mpjpe", "mpjpe_soft", "weighted_mpjpe_soft", "rmpjpe")}
+_WEIGHTED_LOSSES = ("weighted_mpjpe", "weighted_mpjpe_soft")
+
+
+class _MotionLoss(torch.autograd.Function):
+    @staticmethod
+    def _block(kind, pred, target, w, frame_weights, speeds, speed_factor, mean):
+        """what the forward and the backward launch both read"""
+        B, T, V, _ = pred.shape
+        a = _lib.MotionLoss()
+        a.kind, a.B, a.T, a.V, a.speed_factor = kind, B, T, V, speed_factor
+        a.pred, a.target, a.w_full, a.w_frame, a.speeds, a.mean = _ptr(pred), _ptr(target), _ptr(w), _ptr(frame_weights), _ptr(speeds), _ptr(mean)
+        return a
+
+    @staticmethod
+    def forward(ctx, kind, pred, target, w, frame_weights, speeds, speed_factor):
+        stream = _stream(pred)      # refuses host tensors before anything is allocated or launched
+        pred, target, w, frame_weights, speeds = (None if t is None else _contig(t) for t in (pred, target, w, frame_weights, speeds))
+        dev = pred.device
+        loss = torch.empty((), dtype=torch.float32, device=dev)
+        mean = torch.empty(1, dtype=torch.float32, device=dev)
+        part = torch.empty(_lib.LIMITS["CG_LOSS_MAX_BLOCKS"], dtype=torch.float64, device=dev)
+        a = _MotionLoss._block(kind, pred, target, w, frame_weights, speeds, speed_factor, mean)
+        a.part, a.loss = _ptr(part), _ptr(loss)
+        _lib.call("cg_motion_loss_fwd", ctypes.byref(a), stream)
+        ctx.kind, ctx.speed_factor = kind, speed_factor
+        ctx.save_for_backward(pred, target, w, frame_weights, speeds, mean)
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        pred, target, w, frame_weights, speeds, mean = ctx.saved_tensors
+        g = _contig(_chk(g, "upstream gradient").reshape(1))
+        d = torch.empty_like(pred)
+        a = _MotionLoss._block(ctx.kind, pred, target, w, frame_weights, speeds, ctx.speed_factor, mean)
+        a.gloss, a.dpred = _ptr(g), _ptr(d)
+        _lib.call("cg_motion_loss_bwd", ctypes.byref(a), _stream(pred))
+        return None, d, None, None, None, None, None
+
+
+def motion_loss(kind, pred, target, w=None, frame_weights=None, speeds=None, speed_factor=1.0):
+    """The training losses `get_loss` selects besides plain MPJPE (train.py:15-43; losses.py:36-47, :64-76, :241-267) with the weights of
+    train.py:62-71, as one scalar.  kind: a name of `LOSS_KINDS`.  pred / target (B,T,V,3).  The weight of a joint is
+    `base + speed_factor * speeds / (max over the joints of the frame of speeds + 1e-6)` with base = `w` (B,T,V) if given, else
+    `frame_weights[t]` ((T,)) if given, else 0; the speed term is left out without `speeds` ((B,T,V) or (B,T,V,1): `target_gvel`).
+    `weighted_mpjpe` / `weighted_mpjpe_soft` need at least one of the three, `mpjpe_soft` / `rmpjpe` ignore them (as the reference does).
+    The value is symmetric in its first two arguments (train.py:76 passes `(target, output)`); the gradient goes to the one of the two
+    that requires it, the weights and `speeds` get none.  No input is written - the reference divides `target_gvel` by the frame
+    maxima in place (train.py:66), this does not; where torch's gradient of `rmpjpe` is NaN (all errors 0) it is 0 here.  Forward:
+    two launches, no atomics, two calls give the same bits; backward: one launch."""
+    if kind not in LOSS_KINDS:
+        raise ValueError("motion_loss: unknown kind %r (one of %s)" % (kind, ", ".join(sorted(LOSS_KINDS))))
+    _chk(pred, "pred"), _chk(target, "target")
+    if pred.dim() != 4 or pred.shape != target.shape or pred.shape[3] != 3:
+        raise ValueError("motion_loss: expected pred and target of one shape (B,T,V,3), got %s and %s" % (tuple(pred.shape), tuple(target.shape)))
+    B, T, V, _ = pred.shape
+    if B < 1 or T < 1 or V < 1:
+        raise ValueError("motion_loss: empty batch %s" % (tuple(pred.shape),))
+    if kind not in _WEIGHTED_LOSSES:
+        w = frame_weights = speeds = None
+    elif w is None and frame_weights is None and speeds is None:
+        raise ValueError("motion_loss: %s needs w, frame_weights or speeds" % kind)
+    if w is not None and tuple(_chk(w, "w").shape) != (B, T, V):
+        raise ValueError("motion_loss: w must be (B,T,V) = %s, got %s" % ((B, T, V), tuple(w.shape)))
+    if frame_weights is not None and tuple(_chk(frame_weights, "frame_weights").shape) != (T,):
+        raise ValueError("motion_loss: frame_weights must be (T,) = (%d,), got %s" % (T, tuple(frame_weights.shape)))
+    if speeds is not None:
+        if tuple(_chk(speeds, "speeds").shape) not in ((B, T, V), (B, T, V, 1)):
+            raise ValueError("motion_loss: speeds must be (B,T,V) or (B,T,V,1) with (B,T,V) = %s, got %s" % ((B, T, V), tuple(speeds.shape)))
+        speeds = speeds.reshape(B, T, V)
+    for t in (target, w, frame_weights, speeds):
+        if t is not None and t.device != pred.device:
+            raise ValueError("motion_loss: pred is on %s, another operand on %s" % (pred.device, t.device))
+    if target.requires_grad and pred.requires_grad:
+        raise ValueError("motion_loss: only one of the first two arguments may require a gradient")
+    if target.requires_grad:        # the value is symmetric: differentiate with respect to the argument that asks for it
+        pred, target = target, pred
+    target, w, frame_weights, speeds = (None if t is None else t.detach() for t in (target, w, frame_weights, speeds))
+    return _MotionLoss.apply(LOSS_KINDS[kind], pred, target, w, frame_weights, speeds, float(speed_factor))
+
+
+def weighted_mpjpe(pred, target, w):
+    """`losses.weighted_mpjpe` (losses.py:64-76, reduce_axis=[]): mean over all joints of w * |pred - target|, w (B,T,V)."""
+    if w is None:
+        raise ValueError("weighted_mpjpe: w is required")
+    return motion_loss("weighted_mpjpe", pred, target, w=w)
+
+
+def mpjpe_soft(pred, target):
+    """`losses.mpjpe_soft` (losses.py:241-252, reduce_axis=[]): mean over all joints of |SmoothL1(pred - target)|_2."""
+    return motion_loss("mpjpe_soft", pred, target)
+
+
+def weighted_mpjpe_soft(pred, target, w):
+    """`losses.weighted_mpjpe_soft` (losses.py:255-267, reduce_axis=[]): mean over all joints of w * |SmoothL1(pred - target)|_2."""
+    if w is None:
+        raise ValueError("weighted_mpjpe_soft: w is required")
+    return motion_loss("weighted_mpjpe_soft", pred, target, w=w)
+
+
+def rmpjpe(pred, target):
+    """`losses.rmpjpe` (losses.py:36-47, reduce_axis=[]): the square root of the mean over all joints of |pred - target|."""
+    return motion_loss("rmpjpe", pred, target)
+
+
 class _MpjpePerSample(torch.autograd.Function):
     @staticmethod
     def forward(ctx, pred, target):

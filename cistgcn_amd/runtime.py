@@ -267,20 +267,22 @@ class _StepBase:
     """Shared by the step objects: private zero pool (installed only around their own passes), static inputs, guard that
     the parameters still live where the captured launches read them."""
 
-    def _init_common(self, model, x, target, flat):
+    def _init_common(self, model, x, target, flat, loss=None, target_gvel=None):
         self.model, self.flat = model, flat
         self.x, self.target = x, target
+        # `loss`: a callable (pred, target, target_gvel) -> scalar such as `environment.TrainingLoss`; None = plain MPJPE
+        self.loss_fn, self.target_gvel = loss, target_gvel
         self.params = [p for p in model.parameters() if p.requires_grad]
         self._pool = ops.new_step_pool(x.device)
         self._one = torch.ones((), dtype=torch.float32, device=x.device)
         self._param_ptrs = None
 
     def _pass(self):
-        """forward + MPJPE + backward of the static batch"""
+        """forward + loss (MPJPE unless the step was given one) + backward of the static batch"""
         for p in self.params:
             p.grad = None
         pred, = self.model(self.x)
-        loss = ops.mpjpe(pred, self.target)
+        loss = ops.mpjpe(pred, self.target) if self.loss_fn is None else self.loss_fn(pred, self.target, self.target_gvel)
         loss.backward(self._one)            # explicit root gradient: autograd would fill a fresh ones tensor with a stock kernel
         return loss
 
@@ -296,7 +298,9 @@ class _StepBase:
 class GraphedStep(_StepBase):
     """forward + MPJPE + backward of one batch, captured once in a HIP graph and replayed: the ~2 k
     kernel launches of a step collapse into one graph launch, which is what makes the B=16
-    configuration viable.  Inputs live in static device buffers (`x`, `target`).  With `flat`, the
+    configuration viable.  Inputs live in static device buffers (`x`, `target`, `target_gvel`).  `loss`: the training loss as a
+    callable (pred, target, target_gvel) -> scalar (`environment.TrainingLoss`), MPJPE without; `target_gvel` is what it
+    weights the joints by, if it does.  With `flat`, the
     gradients (static buffers under replay) are gathered into the flat all-reduce buffer by one
     kernel launched right after the graph.
 
@@ -304,11 +308,11 @@ class GraphedStep(_StepBase):
     BEFORE the capture; `replay()` raises if a parameter has moved since.  Construction leaves the model state untouched:
     BatchNorm running statistics, `num_batches_tracked` and the dropout seed are restored after warm-up and probing."""
 
-    def __init__(self, model, x, target, warmup=3, flat=None, branches=False, tries=1):
+    def __init__(self, model, x, target, warmup=3, flat=None, branches=False, tries=1, *, loss=None, target_gvel=None):
         """tries > 1: capture that many graphs (each lands in different memory), time a few replays of each and keep the
         median one (the same step replays in 5.27 .. 5.46 ms depending on where the capture's buffers were placed, stable
         for the life of a capture, profiles/README.md); `capture_ms` lists all probes."""
-        self._init_common(model, x.clone(), target.clone(), flat)
+        self._init_common(model, x.clone(), target.clone(), flat, loss, None if target_gvel is None else target_gvel.clone())
         # Optional: the context branch on a forked stream (one fork / join per step, CISTGCN._parallel) -> a parallel graph
         # branch.  Captures and replays correctly on ROCm 7.2 but measured no faster (5.44 vs 5.43 ms at B=16), so it is off.
         model.branch_streams = bool(branches)
@@ -468,10 +472,10 @@ class GraphedAttack:
 
 
 class EagerStep(_StepBase):
-    """Same step without graph capture (debugging / first-iteration reference)."""
+    """Same step without graph capture (debugging / first-iteration reference); `loss` / `target_gvel` as in `GraphedStep`."""
 
-    def __init__(self, model, x, target, flat=None):
-        self._init_common(model, x, target, flat)
+    def __init__(self, model, x, target, flat=None, *, loss=None, target_gvel=None):
+        self._init_common(model, x, target, flat, loss, target_gvel)
 
     def replay(self):
         with ops.step_pool(self._pool):
@@ -492,15 +496,19 @@ class DataParallelStep(_StepBase):
       (output block, context branch, time extrapolator, upper input blocks: their gradients are the tail of the flat
       buffer); its bucket is gathered and all-reduced on a side stream while phase 2 (the remaining input blocks) runs.
       With `graph=True` the two phases are two HIP graphs that share one memory pool.
-    The only collective is the all-reduce (RCCL over xGMI under backend "nccl"; gloo in the CPU tests)."""
+    The only collective is the all-reduce (RCCL over xGMI under backend "nccl"; gloo in the CPU tests).
+    `loss` / `target_gvel` as in `GraphedStep`."""
 
-    def __init__(self, model, x, target, optimizer=None, group=None, cut_block=None, graph=True, warmup=3, flat=None):
+    def __init__(self, model, x, target, optimizer=None, group=None, cut_block=None, graph=True, warmup=3, flat=None, *, loss=None,
+                 target_gvel=None):
         import torch.distributed as dist
         self.group = group
         self.world = dist.get_world_size(group) if dist.is_available() and dist.is_initialized() else 1
         self.optimizer = optimizer
         flat = optimizer.grads if optimizer is not None else (flat if flat is not None else FlatGrads(model.parameters(), x.device))
-        self._init_common(model, x.clone() if graph else x, target.clone() if graph else target, flat)
+        if graph and target_gvel is not None:
+            target_gvel = target_gvel.clone()
+        self._init_common(model, x.clone() if graph else x, target.clone() if graph else target, flat, loss, target_gvel)
         self.weight = shard_weights(x.shape[0], group) if self.world > 1 else 1.0
         nblk = len(model.st_gcnns)
         self.cut_block = (nblk // 2 - 1 if cut_block is None else int(cut_block))

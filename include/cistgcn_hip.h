@@ -6,7 +6,7 @@
  * binds is therefore the set of aten-op groups inside
  *   human_motion_prediction/models/CISTGCN/CISTGCN.py   (CISTGCN.forward, :567-597)
  *   human_motion_prediction/models/layers/SE.py
- *   human_motion_prediction/losses/losses.py:50-61      (mpjpe)
+ *   human_motion_prediction/losses/losses.py:50-61      (mpjpe; :36-47, :64-76, :241-267 the other training losses)
  * Each entry point below names the reference lines it replaces.  INTEGRATION.md shows the ctypes
  * binding that goes into the reference's model file.
  *
@@ -764,6 +764,52 @@ typedef struct CgAttackMetrics {
 } CgAttackMetrics;
 int cg_attack_metrics(const CgAttackMetrics* a, void* stream);
 long long cg_attack_metrics_ws_doubles(int B, int T, int J);
+
+/* ---- training losses other than plain MPJPE (csrc/losses.hip) -----------------------------------------
+ * What `get_loss` (environment/train.py:15-43) selects by `learning_config.loss.type`, with the per-batch weights of train.py:62-71.
+ * With d = pred - target per coordinate and e(b,t,v) the error of a joint, `kind` is
+ *   CG_LOSS_WEIGHTED_MPJPE       losses.weighted_mpjpe (losses/losses.py:64-76)        e = |d|_2,  loss = mean(w e) over all B*T*V joints
+ *                                                                                      (a plain mean: not divided by the sum of w)
+ *   CG_LOSS_MPJPE_SOFT           losses.mpjpe_soft (:241-252)                          e = |s|_2, s_c = SmoothL1(d_c) with beta = 1
+ *                                                                                      (0.5 d^2 if |d| < 1, else |d| - 0.5),  loss = mean(e)
+ *   CG_LOSS_WEIGHTED_MPJPE_SOFT  losses.weighted_mpjpe_soft (:255-267)                 e as mpjpe_soft,  loss = mean(w e)
+ *   CG_LOSS_RMPJPE               losses.rmpjpe (:36-47, reduce_axis=[])                e = |d|_2,  loss = sqrt(mean(e))
+ * (plain `mpjpe` stays cg_mpjpe_fwd / cg_mpjpe_bwd).  The unweighted kinds ignore the weights, as the reference does.  The weight is
+ *   w(b,t,v) = base(b,t,v) + speed_factor * speeds(b,t,v) / (max_v speeds(b,t,.) + 1e-6)
+ * in fp32 and in the order of train.py:64-70: base = w_full[b,t,v] if w_full is given, else w_frame[t] if w_frame is given, else 0
+ * (train.py:68, the weights string "speed"); the speed term is left out when speeds is NULL.  A weighted kind with none of the
+ * three: CG_EARG.
+ * Forward, two launches: one wavefront per (b,t) frame with the lanes over the joints (the frame maximum is a wave reduction; V > 64
+ * loops), at most CG_LOSS_MAX_BLOCKS workgroups of CG_LOSS_THREADS that loop over the frames beyond one pass; each workgroup
+ * leaves one f64 partial sum in `part`, a finishing launch adds them in a fixed order and stores `loss` and `mean` (the mean the
+ * backward of rmpjpe needs).  No floating-point atomics: two calls give the same bits.
+ * Backward, one launch: dpred = gloss[0] * dloss/dpred, gloss read from device memory; the frame maximum is recomputed.  target,
+ * the weights and speeds get no gradient.  As torch: the gradient of a norm at 0 is 0 (a joint with e = 0 gets exact zeros),
+ * SmoothL1' = d for |d| < 1, else sign(d); rmpjpe is gloss / (2 sqrt(mean)) times the gradient of the mean.
+ * Deviations from the reference: (1) for mean = 0 torch's rmpjpe gradient is NaN, here it is 0; (2) every input is read-only - the
+ * reference normalises `target_gvel` in place (`speeds /= ...` on a view of it, train.py:66), here speeds is never written.
+ * pred / target (B,T,V,3), w_full / speeds (B,T,V), w_frame (T,), all contiguous; B, T, V >= 1 and kind one of the four, else CG_ESHAPE. */
+#define CG_LOSS_WEIGHTED_MPJPE 0
+#define CG_LOSS_MPJPE_SOFT 1
+#define CG_LOSS_WEIGHTED_MPJPE_SOFT 2
+#define CG_LOSS_RMPJPE 3
+#define CG_LOSS_THREADS 256      /* per workgroup: CG_LOSS_THREADS / 64 frames in flight */
+#define CG_LOSS_MAX_BLOCKS 512   /* workgroups of a launch = f64 words of `part` */
+typedef struct CgMotionLoss {
+  int kind, B, T, V;
+  float speed_factor; int pad;
+  const float* pred; const float* target;
+  const float* w_full;      /* (B,T,V) or NULL */
+  const float* w_frame;     /* (T,) or NULL; ignored when w_full is given */
+  const float* speeds;      /* (B,T,V) or NULL */
+  double* part;             /* forward scratch: CG_LOSS_MAX_BLOCKS doubles */
+  float* loss;              /* forward out: one float */
+  float* mean;              /* forward out, backward in: mean(e) resp. mean(w e), one float */
+  const float* gloss;       /* backward in: the upstream gradient, one float */
+  float* dpred;             /* backward out: (B,T,V,3) */
+} CgMotionLoss;
+int cg_motion_loss_fwd(const CgMotionLoss* a, void* stream);
+int cg_motion_loss_bwd(const CgMotionLoss* a, void* stream);
 
 #ifdef __cplusplus
 }
