@@ -41,6 +41,9 @@ LIMITS = {
     # kinds of cg_motion_loss_*, the threads of its workgroups (64 per frame in flight) and the cap of its grid = f64 words of its scratch
     "CG_LOSS_WEIGHTED_MPJPE": 0, "CG_LOSS_MPJPE_SOFT": 1, "CG_LOSS_WEIGHTED_MPJPE_SOFT": 2, "CG_LOSS_RMPJPE": 3,
     "CG_LOSS_THREADS": 256, "CG_LOSS_MAX_BLOCKS": 512,
+    # cg_forward_kinematics: joints of a tree (and of `select`), the cap of its grid, the threads of a workgroup (64 per one or two frames
+    # in flight) and its two conventions
+    "CG_FK_MAX_JOINTS": 64, "CG_FK_MAX_BLOCKS": 1024, "CG_FK_THREADS": 256, "CG_FK_EXPMAP_CHAIN": 0, "CG_FK_SMPL": 1,
 }
 STAT_REPLICAS = LIMITS["CG_STAT_REPLICAS"]
 ALPHA_SLOTS = LIMITS["CG_ALPHA_SLOTS"]
@@ -233,6 +236,17 @@ class MotionLoss(ctypes.Structure):
                 ("part", c_void_p), ("loss", c_void_p), ("mean", c_void_p), ("gloss", c_void_p), ("dpred", c_void_p)]
 
 
+class ForwardKinematics(ctypes.Structure):
+    _fields_ = [("convention", c_int), ("J", c_int), ("J_pose", c_int), ("J_out", c_int), ("N", c_longlong), ("scale", c_float), ("pad", c_int),
+                ("angles", c_void_p), ("parent", c_void_p), ("rest", c_void_p), ("select", c_void_p), ("out", c_void_p)]
+
+
+class GatherWindows(ctypes.Structure):
+    _fields_ = [("B", c_int), ("L", c_int), ("J_src", c_int), ("J", c_int), ("W", c_int), ("up_hi", c_int), ("up_lo", c_int), ("pad", c_int),
+                ("F", c_longlong), ("mean", c_float), ("std", c_float),
+                ("frames", c_void_p), ("starts", c_void_p), ("items", c_void_p), ("select", c_void_p), ("raw", c_void_p)]
+
+
 # A class mirrors the header's struct "Cg" + its own name, except these two.
 C_STRUCT_NAMES = {"EvalMetricsArgs": "CgEvalMetrics", "AttackMetricsArgs": "CgAttackMetrics"}
 
@@ -336,6 +350,8 @@ _SIGNATURES = {
     "cg_attack_metrics_ws_doubles": [c_int, c_int, c_int],
     "cg_motion_loss_fwd": [POINTER(MotionLoss), P],
     "cg_motion_loss_bwd": [POINTER(MotionLoss), P],
+    "cg_forward_kinematics": [POINTER(ForwardKinematics), P],
+    "cg_gather_windows": [POINTER(GatherWindows), P],
     "cg_adam_flat": [P, P, P, P, LL, c_float, c_float, c_float, c_float, c_float, c_float, c_float, LL, P],
 }
 EXPORTS = tuple(sorted(_SIGNATURES))

@@ -1619,6 +1619,134 @@ def attack_metrics(adv, orig, return_counts=False):
     return out
 
 
+# ----------------------------------------------------------------------------------------------
+# forward kinematics and the window gather of the motion bank (csrc/kinematics.hip): what the reference's loaders do before a
+# window exists (utils/data_utils.py::load_data_h36m / ::load_data_amass); no autograd
+# ----------------------------------------------------------------------------------------------
+FK_CONVENTIONS = {"expmap_chain": _lib.LIMITS["CG_FK_EXPMAP_CHAIN"], "smpl": _lib.LIMITS["CG_FK_SMPL"]}
+FK_MAX_JOINTS = _lib.LIMITS["CG_FK_MAX_JOINTS"]
+
+
+def _int_operand(t, name, device):
+    """a device int32 vector: an integer tensor on `device` is taken as it is (cast to int32 if need be), anything else is refused"""
+    if not torch.is_tensor(t) or t.dtype not in (torch.int32, torch.int64) or t.dim() != 1:
+        raise TypeError("%s must be a 1-D int32 / int64 tensor" % name)
+    if t.device != device:
+        raise ValueError("%s is on %s, the data on %s" % (name, t.device, device))
+    return t.to(torch.int32).contiguous()
+
+
+def forward_kinematics(angles, parent, rest, convention="expmap_chain", select=None, scale=1.0):
+    """Joint angles -> joint positions for all N frames in one launch (cistgcn_hip.h: CgForwardKinematics): (N, J_out, 3) fp32.
+    convention "expmap_chain": `fkl_torch` of the reference (forward_kinematics.py:219-241), angles (N, 3 + 3J), first three columns
+    ignored, with its quirk that a joint whose parent is joint 0 composes nothing; "smpl": `ang2joint` (ang2joint.py:11-58), angles
+    = pose (N, J_pose, 3) with J_pose >= J, without the reference's noise (a zero rotation vector is the identity exactly).
+    parent: J ints on the host, parent[0] = -1 and -1 <= parent[i] < i (checked here, ValueError); rest (J,3): offsets / rest
+    positions (a device tensor, or host numbers that are uploaded); select: the joints to return (host ints in [0, J), repeats
+    allowed, at most 64; None: all); the result is multiplied by `scale`.  1 <= J <= 64.  No input is written and none may require a
+    gradient; two calls give the same bits."""
+    if convention not in FK_CONVENTIONS:
+        raise ValueError("forward_kinematics: unknown convention %r (one of %s)" % (convention, ", ".join(sorted(FK_CONVENTIONS))))
+    if not torch.is_tensor(angles):
+        raise TypeError("forward_kinematics: angles must be a tensor")
+    stream = _stream(angles)        # refuses host tensors before anything is allocated or launched
+    _chk(angles, "angles")
+    if angles.requires_grad or (torch.is_tensor(rest) and rest.requires_grad):
+        raise ValueError("forward_kinematics: no autograd - detach the inputs")
+    par = np.asarray(parent.cpu() if torch.is_tensor(parent) else parent).astype(np.int64).reshape(-1)
+    J = int(par.shape[0])
+    if J < 1 or J > FK_MAX_JOINTS:
+        raise ValueError("forward_kinematics: 1 <= J <= %d joints, got %d" % (FK_MAX_JOINTS, J))
+    if par[0] != -1 or any(not (-1 <= int(par[i]) < i) for i in range(1, J)):
+        raise ValueError("forward_kinematics: parent[0] must be -1 and -1 <= parent[i] < i for every other joint")
+    if convention == "expmap_chain":
+        if angles.dim() != 2 or angles.shape[1] != 3 + 3 * J:
+            raise ValueError("forward_kinematics: expmap_chain takes angles (N, 3 + 3J) = (N, %d), got %s" % (3 + 3 * J, tuple(angles.shape)))
+        J_pose = J
+    else:
+        if angles.dim() != 3 or angles.shape[2] != 3 or angles.shape[1] < J:
+            raise ValueError("forward_kinematics: smpl takes pose (N, J_pose, 3) with J_pose >= %d, got %s" % (J, tuple(angles.shape)))
+        J_pose = int(angles.shape[1])
+    dev = angles.device
+    if not torch.is_tensor(rest):
+        rest = torch.tensor(np.asarray(rest, dtype=np.float32), device=dev)
+    _chk(rest, "rest")
+    if tuple(rest.shape) != (J, 3):
+        raise ValueError("forward_kinematics: rest must be (J,3) = (%d,3), got %s" % (J, tuple(rest.shape)))
+    if rest.device != dev:
+        raise ValueError("forward_kinematics: angles are on %s, rest on %s" % (dev, rest.device))
+    if select is not None:
+        select = [int(v) for v in (select.tolist() if hasattr(select, "tolist") else select)]
+        if not select or len(select) > FK_MAX_JOINTS:
+            raise ValueError("forward_kinematics: select names 1 .. %d joints, got %d" % (FK_MAX_JOINTS, len(select)))
+        if min(select) < 0 or max(select) >= J:
+            raise IndexError("forward_kinematics: select out of range for %d joints" % J)
+    J_out = J if select is None else len(select)
+    N = int(angles.shape[0])
+    out = torch.empty(N, J_out, 3, dtype=torch.float32, device=dev)
+    if N == 0:
+        return out
+    angles, rest = _contig(angles), _contig(rest)
+    host_parent = (ctypes.c_int * J)(*[int(v) for v in par])
+    a = _lib.ForwardKinematics()
+    a.convention, a.J, a.J_pose, a.J_out, a.N, a.scale = FK_CONVENTIONS[convention], J, J_pose, J_out, N, float(scale)
+    a.angles, a.parent, a.rest, a.out = _ptr(angles), ctypes.cast(host_parent, _vp), _ptr(rest), _ptr(out)
+    a.select = _ptr(_index_tensor(select, dev)) if select is not None else None
+    _lib.call("cg_forward_kinematics", ctypes.byref(a), stream)
+    return out
+
+
+def gather_windows(frames, starts, items, L, select=None, mean=0.0, std=1.0, up_joints=None):
+    """One batch of windows out of a bank of distinct frames (cistgcn_hip.h: CgGatherWindows): raw (B, L, J, 3) with
+    raw[b, t] = (frames[starts[items[b]] + t][select] - mean) / std, `the_sequence[fs_sel]`, `target[:, :, dim_used]` and the
+    normalisation of the reference's loaders for the windows of one batch.  frames (F, J_src, 3) fp32; starts (W) and items (B):
+    int32 / int64 tensors on the device of `frames`, never read back: the kernel clamps ids and starts so that nothing is read out of
+    bounds, a caller with host ids validates them first (`MotionBank.windows`).  select: host ints in [0, J_src) or None.
+    up_joints = (hi, lo), joints in the selected numbering: a window whose first frame has y[hi] - y[lo] < 0 gets y := c - y, c the
+    mean of the window's y (h36m_motion_3d.py:70-74); None: no check.  frames is never written, two calls give the same bits."""
+    if not torch.is_tensor(frames):
+        raise TypeError("gather_windows: frames must be a tensor")
+    stream = _stream(frames)
+    _chk(frames, "frames")
+    if frames.requires_grad:
+        raise ValueError("gather_windows: no autograd - detach the frames")
+    if frames.dim() != 3 or frames.shape[2] != 3:
+        raise ValueError("gather_windows: expected frames (F, J_src, 3), got %s" % (tuple(frames.shape),))
+    F, J_src = int(frames.shape[0]), int(frames.shape[1])
+    L = int(L)
+    if L < 1 or F < L or J_src < 1:
+        raise ValueError("gather_windows: windows of %d frames out of %d frames of %d joints" % (L, F, J_src))
+    dev = frames.device
+    starts, items = _int_operand(starts, "starts", dev), _int_operand(items, "items", dev)
+    W, B = int(starts.shape[0]), int(items.shape[0])
+    if W < 1:
+        raise ValueError("gather_windows: no windows")
+    if select is not None:
+        select = [int(v) for v in (select.tolist() if hasattr(select, "tolist") else select)]
+        if not select:
+            raise ValueError("gather_windows: empty select")
+        if min(select) < 0 or max(select) >= J_src:
+            raise IndexError("gather_windows: select out of range for %d joints" % J_src)
+    J = J_src if select is None else len(select)
+    if float(std) == 0.0:
+        raise ValueError("gather_windows: std must not be 0")
+    up_hi = up_lo = -1
+    if up_joints is not None:
+        up_hi, up_lo = (int(v) for v in up_joints)
+        if not (0 <= up_hi < J and 0 <= up_lo < J):
+            raise IndexError("gather_windows: up_joints %s out of range for %d selected joints" % ((up_hi, up_lo), J))
+    raw = torch.empty(B, L, J, 3, dtype=torch.float32, device=dev)
+    if B == 0:
+        return raw
+    frames = _contig(frames)
+    a = _lib.GatherWindows()
+    a.B, a.L, a.J_src, a.J, a.W, a.up_hi, a.up_lo, a.F, a.mean, a.std = B, L, J_src, J, W, up_hi, up_lo, F, float(mean), float(std)
+    a.frames, a.starts, a.items, a.raw = _ptr(frames), _ptr(starts), _ptr(items), _ptr(raw)
+    a.select = _ptr(_index_tensor(select, dev)) if select is not None else None
+    _lib.call("cg_gather_windows", ctypes.byref(a), stream)
+    return raw
+
+
 def cumsum_time(x):
     """cumulative sum over axis 1 of a 4-D (possibly strided) tensor"""
     return _Cumsum.apply(x)

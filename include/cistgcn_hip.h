@@ -811,6 +811,72 @@ typedef struct CgMotionLoss {
 int cg_motion_loss_fwd(const CgMotionLoss* a, void* stream);
 int cg_motion_loss_bwd(const CgMotionLoss* a, void* stream);
 
+/* ---- forward kinematics and the device-resident motion bank (csrc/kinematics.hip) -------------------------
+ * What utils/data_utils.py::load_data_h36m (:843-942) and ::load_data_amass (:738-839) do before a window reaches a loader:
+ * joint angles -> joint positions, one launch for all frames of a file.  The tree is data: parent[i] is the parent of joint i
+ * (-1: a root; joint 0 must be one) with parent[i] < i for i >= 1, rest (J,3) the offsets (chain) / rest positions (SMPL),
+ * select (J_out) the joints written (NULL: all J, in order), out (N,J_out,3) = scale * position.  `convention`:
+ *   CG_FK_EXPMAP_CHAIN  utils/forward_kinematics.py::fkl_torch (:219-241) with data_utils.expmap2rotmat_torch (:1175-1194):
+ *                       angles (N, 3 + 3J), joint i reads columns 3 + 3i .. 5 + 3i (the first three columns are ignored).
+ *                       theta = |r|, r0 = r / (theta + 1e-7), K = skew(r0) (K[0][1] = -r0z, K[0][2] = r0y, K[1][2] = -r0x),
+ *                       R_i = I + sin(theta) K + (1 - cos(theta)) K^2; p_i = rest_i; then for i >= 1 in index order and ONLY IF
+ *                       parent[i] > 0:  R_i = R_i R_parent,  p_i = rest_i R_parent + p_parent (row vector times matrix).
+ *                       A joint whose parent is joint 0 (or that has none) keeps its local rotation and p = rest - joint 0's own
+ *                       rotation never reaches anything.  That is the reference's `if parent[i] > 0` and not the usual recursion;
+ *                       what its loaders emit depends on it, so it is reproduced.
+ *   CG_FK_SMPL          utils/ang2joint.py::ang2joint (:11-58) with rodrigues (:64-91): angles = pose (N, J_pose, 3), J_pose >= J,
+ *                       the first J joints are read.  theta = |r|, k = r / theta, R = cos(theta) I + (1 - cos(theta)) k k^T +
+ *                       sin(theta) skew(k); G_i = G_parent [R_i | rest_i - rest_parent] (a root: [R_i | rest_i]); the position is
+ *                       the translation of G_i.  The reference adds N(0, 1e-8) noise to r before the norm so that theta != 0;
+ *                       nothing is drawn here: theta = |r| and theta == 0 gives R = I exactly, the reference's result for r = 0.
+ * The kernel reads fp32, composes in f64 and rounds each coordinate to fp32 once; angles, rest and the tables are never written,
+ * nothing is accumulated with atomics: two calls give the same bits.  One lane per joint, two frames per wavefront while J and
+ * J_out <= 32, the frame's global rotations and positions in LDS, one pass per tree level; at most CG_FK_MAX_BLOCKS workgroups,
+ * each walking the frame groups beyond one pass, so N is not bounded.
+ * `parent` is a HOST array (like the step table of cg_perturb_sequences it is validated here without reading device memory and
+ * copied into the launch; the call stays capturable); every other pointer is a device pointer.
+ * Returns -1 for a missing angles / parent / rest / out; -2 for J or J_out outside [1, CG_FK_MAX_JOINTS], an unknown convention,
+ * J_pose < J (SMPL), N < 0, parent[0] != -1 or a parent[i] outside [-1, i).  An entry of `select` outside [0, J) is clamped into
+ * it (the host path raises first).  N == 0: nothing is launched. */
+#define CG_FK_MAX_JOINTS 64
+#define CG_FK_MAX_BLOCKS 1024    /* workgroups of a launch; one holds CG_FK_THREADS / 64 wavefronts of one or two frames */
+#define CG_FK_THREADS 256
+#define CG_FK_EXPMAP_CHAIN 0
+#define CG_FK_SMPL 1
+typedef struct CgForwardKinematics {
+  int convention, J, J_pose, J_out;   /* J_pose: joints per input row (SMPL; ignored by the chain convention) */
+  long long N;                        /* frames */
+  float scale; int pad;
+  const float* angles;                /* (N, 3 + 3J) | (N, J_pose, 3) */
+  const int* parent;                  /* HOST (J) */
+  const float* rest;                  /* (J,3) */
+  const int32_t* select;              /* (J_out) or NULL (then J_out == J) */
+  float* out;                         /* (N, J_out, 3) */
+} CgForwardKinematics;
+int cg_forward_kinematics(const CgForwardKinematics* a, void* stream);
+
+/* One batch of sliding windows cut out of a bank of distinct frames: `the_sequence[fs_sel]` (data_utils.py:891-896, :812-817),
+ * `self.target[:, :, dim_used]` and `(all_seqs - data_mean) / data_std` (loaders/h36m_motion_3d.py:62-68) and the pose-inversion fix
+ * of H36m_Motion3D.__init__ (:70-74 with :79-89), for the windows a batch names - the (n, seq_len, J, 3) array of every window is
+ * never built.  frames (F,J_src,3); starts (W) the first frame of every window; items (B) window ids; raw (B,L,J,3):
+ *   raw[b,t,j,:] = (frames[starts[items[b]] + t, select[j], :] - mean) / std        (fp32; mean 0 and std 1: the bits of frames)
+ * Inversion check (up_hi, up_lo >= 0, joints in the SELECTED numbering - the loader's head and hip): a window with
+ * y[0, up_hi] - y[0, up_lo] < 0 (strictly, in fp32, as `np.sign(...) == -1`) has y := c - y on every frame, c the mean of its L*J
+ * normalised y values accumulated in f64 in a fixed order and rounded to fp32 once (the reference takes an fp32 mean).  Both -1: off.
+ * One workgroup per window; no atomics, two calls give the same bits; frames, starts and items are never written.
+ * items[b] is clamped into [0, W) and starts[.] into [0, F - L], an entry of select into [0, J_src): a bad id cannot read out of
+ * bounds (the host path validates and raises first).
+ * Returns -1 for a missing frames / starts / items / raw; -2 for B, L, J, J_src or W < 1, F < L, std == 0, select == NULL with
+ * J != J_src, or up_hi / up_lo that are neither both -1 nor both in [0, J). */
+typedef struct CgGatherWindows {
+  int B, L, J_src, J, W, up_hi, up_lo, pad;
+  long long F;
+  float mean, std;
+  const float* frames; const int32_t* starts; const int32_t* items; const int32_t* select;
+  float* raw;
+} CgGatherWindows;
+int cg_gather_windows(const CgGatherWindows* a, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
