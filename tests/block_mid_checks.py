@@ -40,6 +40,8 @@ CASES = {
     "limits": (3, [(FULL, 64, 64, 64, True), (PW, 64, 64, 64, False)], False),
 }
 MODES = {"train-drop": (True, 0.1), "train": (True, 0.0), "eval-drop": (False, 0.1)}
+# channels 0 and 1 of both items with a variance comparable to eps (checks.LOW_VAR_BATCH / LOW_VAR_RUNNING): check_low_variance
+LOW_VAR_CASE = (37, [(FULL, 5, 22, 10, True), (PW, 6, 22, 22, True)], False)
 
 
 def geometry(B, item):
@@ -72,9 +74,10 @@ def assert_properties():
     assert lib.cg_block_mid_supported(3, 2, 4, 4, 4) == 0 and lib.cg_block_mid_supported(0, 0, 4, 4, 4) == 0
 
 
-def make_inputs(name, seed=5):
-    """CPU f32 operands of a case"""
-    B, items, stacked = CASES[name]
+def make_inputs(name, seed=5, low_var=False):
+    """CPU f32 operands of a case (a name of CASES or a case itself).  low_var: channels 0 and 1 of every x centred and scaled to the
+    variances checks.LOW_VAR_BATCH, their running variances checks.LOW_VAR_RUNNING, their beta 0 (|u| stays above KINK)."""
+    B, items, stacked = CASES[name] if isinstance(name, str) else name
     g = torch.Generator().manual_seed(seed)
     data = []
     for kind, C, L, O, act in items:
@@ -87,6 +90,12 @@ def make_inputs(name, seed=5):
                  gamma=(0.7 + 0.6 * torch.rand(C, generator=g)).float(), beta=(-0.2 + 0.4 * torch.rand(C, generator=g)).float(),
                  rm=(-0.03 + 0.06 * torch.rand(C, generator=g)).float(), rv=(1.0 + 0.6 * torch.rand(C, generator=g)).float(),
                  alpha=torch.tensor([0.25]))
+        if low_var:
+            import checks
+            d["x"] = checks._low_var_input(d["x"])
+            d["rv"][:2] = torch.tensor(checks.LOW_VAR_RUNNING)
+            d["rm"][:2] *= 1e-3
+            d["beta"][:2] = 0.0
         data.append(d)
     return B, data, stacked
 
@@ -255,6 +264,29 @@ def check_operator(device, name, mode):
         if train:
             assert bool(((new[i]["rm"].double() - ref["mean"]).abs() <= 2.0 ** -20 * ref["mean"].abs().clamp_min(1e-2)).all()), what + ": batch mean"
     assert not failures, "\n".join(failures)
+
+
+def check_low_variance(device):
+    """two BatchNorm channels whose variance is comparable to eps (make_inputs(low_var=True)), both item kinds, train and eval mode.  The
+    condition of check_operator compares two routes that share csrc/cg_bn.h, so a wrong eps passes it; here the new route is held to the
+    fp64 evaluation itself: the PReLU taps (BatchNorm + PReLU, element for element) to the 2^-20 * max |tap| of check_operator, outputs to
+    2e-5 * max(1, max |ref|), gradients to 5e-5 * max(1e-3, max |ref|) - the bounds of the other fused BatchNorm families (tests/checks.py)."""
+    from helpers import assert_close
+    B, data, stacked = make_inputs(LOW_VAR_CASE, low_var=True)
+    salts = [11 + 3 * i for i in range(len(data))]
+    for mode in ("train", "eval-drop"):
+        train, p = MODES[mode]
+        new = run_route(device, B, data, stacked, True, train, p, salts)
+        for i, d in enumerate(data):
+            ref = reference(d, torch.ones(d["x"].shape, dtype=torch.float64), train)
+            what = "block_mid low variance %s item %d" % (mode, i)
+            if train:
+                var = ref["var"][:2].tolist()
+                assert 0.8e-5 < var[0] < 1.0e-5 and 0.08e-5 < var[1] < 0.12e-5, var
+            assert float((new[i]["tap"].double() - ref["tap"]).abs().max()) <= 2.0 ** -20 * float(ref["tap"].abs().max()), what + ": tap"
+            assert_close(new[i]["y"].reshape(ref["y"].shape), ref["y"], what + " y", rel=2e-5)
+            for k in ("dx", "dgamma", "dbeta", "dalpha", "dW"):
+                assert_close(new[i][k].reshape(ref[k].shape), ref[k], "%s %s" % (what, k), rel=5e-5, floor=max(1e-3, float(ref[k].abs().max())))
 
 
 def _guarded(n, dtype, device):

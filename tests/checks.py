@@ -33,6 +33,46 @@ def _leaf(t, device):
     return t.detach().clone().to(device).requires_grad_(True)
 
 
+# ---- channels whose variance is comparable to eps -------------------------------------------------------------------------------
+# The families' own data has channel variances of 0.5 .. 9: against those the eps = 1e-5 of a BatchNorm is a 5e-6 effect, below every bound,
+# and a kernel that drops it passes (tests/MUTANTS.md).  `low_var=True` of a family's check gives channels 0 and 1 of every BatchNorm a batch
+# variance of about 0.9 eps and 0.1 eps (train) and these running variances (eval); references and bounds stay the family's.
+LOW_VAR_BATCH = (0.9e-5, 0.1e-5)
+LOW_VAR_RUNNING = (2e-5, 3e-6)
+LOW_VAR_ROWS = (3e-3, 1e-3)          # a map of O(1) rows in front of the BatchNorm, where its output is not at hand to be measured
+
+
+def _low_var_input(x, dim=1):
+    """a copy of the data tensor x whose channels 0 and 1 (along `dim`) are centred (no cancellation in the float32 values) and scaled to
+    the biased variances LOW_VAR_BATCH"""
+    x = x.clone().movedim(dim, 0)
+    for c, var in enumerate(LOW_VAR_BATCH):
+        v = x[c].double()
+        v = v - v.mean()
+        x[c] = (v * (var / float(v.pow(2).mean())) ** 0.5).float()
+    return x.movedim(0, dim).contiguous()
+
+
+def _low_var_rows(weight, y=None, bias=None):
+    """in place: rows 0 and 1 of the weight of a map in front of a BatchNorm (never its input) scaled so that the map's output channels get
+    the variances LOW_VAR_BATCH - y: that output (channels along dim 1) with the weight as it is, in float64; without it by LOW_VAR_ROWS -
+    and the bias entries with them"""
+    with torch.no_grad():
+        for c in range(2):
+            s = LOW_VAR_ROWS[c] if y is None else (LOW_VAR_BATCH[c] / float(y.transpose(0, 1)[c].double().var(unbiased=False))) ** 0.5
+            weight[c] *= s
+            if bias is not None:
+                bias[c] *= s
+
+
+def _low_var_running(bn):
+    """in place: running_var of channels 0 and 1 = LOW_VAR_RUNNING, their running_mean of the size of such a channel"""
+    with torch.no_grad():
+        for c, var in enumerate(LOW_VAR_RUNNING):
+            bn.running_var[c] = var
+            bn.running_mean[c] *= 1e-3
+
+
 class BranchLog:
     """PReLU of a CPU reference on the branches the HIP run took, for tensors of millions of elements.
 
@@ -243,10 +283,13 @@ def check_contract(device, quick=False):
         assert_close(_chan_sums(st), torch.stack((rw.sum((0, 2, 3)), (rw * rw).sum((0, 2, 3))), 1).reshape(-1), "contract wide sums K=%d" % K_, rel=1e-5)
 
 
-def _check_norm_act_shape(device, quick, T, V, trains=(True, False), B=4, C=6, replay=False):
-    """replay: the stock-PyTorch reference takes the PReLU branches of the HIP run (BranchLog; for tensors of millions of elements)"""
+def _check_norm_act_shape(device, quick, T, V, trains=(True, False), B=4, C=6, replay=False, low_var=False):
+    """replay: the stock-PyTorch reference takes the PReLU branches of the HIP run (BranchLog; for tensors of millions of elements).
+    low_var: two channels whose variance is comparable to eps (LOW_VAR_BATCH above), the reference in float64."""
     g = _gen(2)
     x = _rand(g, B, C, T, V, scale=3.0) + 1.5
+    if low_var:
+        x = _low_var_input(x)
     add = _rand(g, B, C, T, V)
     pre = _rand(g, B, C)
 
@@ -255,6 +298,8 @@ def _check_norm_act_shape(device, quick, T, V, trains=(True, False), B=4, C=6, r
         with torch.no_grad():
             bn.weight.copy_(1 + 0.3 * _rand(g, C)); bn.bias.copy_(0.3 * _rand(g, C))
             bn.running_mean.copy_(_rand(g, C)); bn.running_var.copy_(torch.rand(C, generator=g) + 0.5)
+        if low_var:
+            _low_var_running(bn)
         return bn
 
     for train in trains:
@@ -266,6 +311,8 @@ def _check_norm_act_shape(device, quick, T, V, trains=(True, False), B=4, C=6, r
                     bn_dev.load_state_dict(bn_ref.state_dict())
                     bn_dev.to(device)
                     bn_ref.train(train)
+                    if low_var:
+                        bn_ref.double()
                     pr_ref = nn.PReLU(alpha_n) if alpha_n else None
                     pr_dev = None
                     if pr_ref is not None:
@@ -276,6 +323,8 @@ def _check_norm_act_shape(device, quick, T, V, trains=(True, False), B=4, C=6, r
                         pr_dev = nn.PReLU(alpha_n)
                         pr_dev.load_state_dict(pr_ref.state_dict())
                         pr_dev.to(device)
+                        if low_var:
+                            pr_ref.double()
                     ins = [x] + ([pre] if use_pre else []) + ([add] if add_mode else [])
 
                     def split(ts):
@@ -303,10 +352,11 @@ def _check_norm_act_shape(device, quick, T, V, trains=(True, False), B=4, C=6, r
                             u = u + a_
                         return u
 
-                    what = "norm_act train=%s pre=%s add=%s alpha=%d" % (train, use_pre, add_mode, alpha_n)
+                    what = "norm_act%s train=%s pre=%s add=%s alpha=%d" % (" low variance" if low_var else "", train, use_pre, add_mode, alpha_n)
                     dev_ps = list(bn_dev.parameters()) + (list(pr_dev.parameters()) if pr_dev is not None else [])
                     ref_ps = list(bn_ref.parameters()) + (list(pr_ref.parameters()) if pr_ref is not None else [])
-                    _run(dev, ref, ins, device, what=what, ref_sees_dev_out=True, log=log if replay else None, params=(dev_ps, ref_ps))
+                    _run(dev, ref, ins, device, what=what, ref_sees_dev_out=True, log=log if replay else None, params=(dev_ps, ref_ps),
+                         ref_dtype=torch.float64 if low_var else None)
                     log.settle(what)
                     for (n1, pd), (_, pr) in zip(bn_dev.named_parameters(), bn_ref.named_parameters()):
                         if not replay:
@@ -428,8 +478,9 @@ def check_batched_ops(device):
     assert_close(_chan_sums(outs[0][1]), torch.stack((y0.sum((0, 2, 3)), (y0 * y0).sum((0, 2, 3))), 1).reshape(-1), "emitted sums", rel=1e-6)
 
 
-def check_dropout(device):
-    """Dropout cannot match the CPU RNG stream; check rate, scale and fwd/bwd mask agreement."""
+def check_dropout(device, mask=False):
+    """Dropout cannot match the CPU RNG stream; check rate, scale and fwd/bwd mask agreement.  mask=True: also that the mask is the host
+    restatement of the kernels' hash bit for bit, and its statistics (_check_dropout_mask)."""
     p = 0.3
     ops.manual_seed(123, device)
     x = torch.ones(8, 16, 10, 22, device=device, requires_grad=True)
@@ -463,6 +514,56 @@ def check_dropout(device):
     assert torch.equal(x2.grad.cpu(), y6.detach().cpu())
     y7 = ops.norm_act(torch.ones(3, 5, 6, 4, device=device).permute(0, 3, 1, 2), train=True, drop_p=p, salt=11)
     assert torch.equal(y7.cpu(), y6.detach().cpu())
+    if mask:
+        _check_dropout_mask(device, p)
+
+
+DROP_MASK_SHAPES = ((8, 16, 32, 32), (8, 16, 33, 34), (8, 16, 33, 33))      # rows of 1024 / 1122 / 1089 floats: float4, float2, scalar path; >= 2^17 elements each
+DROP_MASK_SEEDS, DROP_MASK_SALTS = (20240607, 77), (7, 1234567)
+
+
+def dropout_mask_statistics(kept, shape, q):
+    """[(what, observed rate, expected rate, 5 sigma)] of a keep mask (flat bool array of the logical (B, C, H, W) tensor) whose elements are
+    kept with probability q: keep rate of every sample and every channel, and the rate at which elements i and i + lag agree, each against
+    the binomial 5 sigma of its own count - sqrt(r (1 - r) / n) with r the expected rate."""
+    B, C = shape[0], shape[1]
+    m = kept.reshape(B, C, -1)
+    out = []
+    sig = lambda r, n: 5.0 * (r * (1.0 - r) / n) ** 0.5
+    for b in range(B):
+        out.append(("keep rate of sample %d" % b, float(m[b].mean()), q, sig(q, m[b].size)))
+    for c in range(C):
+        out.append(("keep rate of channel %d" % c, float(m[:, c].mean()), q, sig(q, m[:, c].size)))
+    agree = q * q + (1.0 - q) * (1.0 - q)
+    for lag in (1, 4, 16384):
+        out.append(("agreement of elements i and i + %d" % lag, float((kept[:-lag] == kept[lag:]).mean()), agree, sig(agree, kept.size - lag)))
+    return out
+
+
+def _check_dropout_mask(device, p):
+    """The mask the row kernels draw IS the host restatement (helpers.hip_keep_scale), bit for bit, on tensors of at least 2^17 elements (a
+    mask that repeats after 16 384 elements or whose 16-bit draws overlap passes every assertion above): two seeds x two salts on the
+    float4, float2 and scalar paths, forward and backward; and that mask has the statistics of independent draws
+    (dropout_mask_statistics; the seeds are fixed, so is the result)."""
+    from helpers import hip_keep_scale
+    q = 1.0 - int(np.float32(p) * np.float32(65536.0)) / 65536.0
+    for shape in DROP_MASK_SHAPES:
+        n = int(np.prod(shape))
+        assert n >= 1 << 17
+        for seed in DROP_MASK_SEEDS:
+            for salt in DROP_MASK_SALTS:
+                ops.manual_seed(seed, device)
+                ops.begin_step(device)
+                word = int(ops.seed_state(device)[0].item())
+                x = torch.ones(*shape, device=device, requires_grad=True)
+                y = ops.norm_act(x, train=True, drop_p=p, salt=salt)
+                y.backward(torch.ones_like(y))
+                want = hip_keep_scale(word, salt, p, n)
+                what = "dropout mask %s seed %d salt %d" % (shape, seed, salt)
+                assert np.array_equal(y.detach().cpu().numpy().reshape(-1), want), what + ": not the host restatement"
+                assert np.array_equal(x.grad.cpu().numpy().reshape(-1), want), what + ": backward mask is not the host restatement"
+                for name, rate, expect, bound in dropout_mask_statistics(y.detach().cpu().numpy().reshape(-1) != 0, shape, q):
+                    assert abs(rate - expect) <= bound, "%s: %s %.5f, expected %.5f +- %.5f" % (what, name, rate, expect, bound)
 
 
 def check_reduce_and_gate(device):
@@ -620,9 +721,10 @@ def check_copies(device):
     _run(lambda t: sum(ops.fanout(t, 2)), lambda t: 2.0 * t, [_rand(g, 3, 6)], device, what="fanout 2-D")
 
 
-def check_dilated_convs(device, shapes=((2, 5, 4, 10, 7), (3, 6, 5, 4, 6), (2, 25, 25, 10, 22), (2, 50, 25, 10, 22), (2, 25, 25, 10, 25), (2, 3, 4, 5, 5))):
+def check_dilated_convs(device, shapes=((2, 5, 4, 10, 7), (3, 6, 5, 4, 6), (2, 25, 25, 10, 22), (2, 50, 25, 10, 22), (2, 25, 25, 10, 25), (2, 3, 4, 5, 5), (2, 50, 25, 5, 5))):
     """(B, Cin, Cout, H, W): odd H * W takes the generic contraction, the others the whole-sample kernels (csrc/fpn_conv.hip; float2 rows when
-    H * W % 4 == 2: 10 x 7, 10 x 25)"""
+    H * W % 4 == 2: 10 x 7, 10 x 25).  (2, 50, 25, 5, 5): K = 450 with a bias, the split-K plan the model takes at T = 50
+    (audit_checks.check_contract_edges asserts that plan)."""
     floor, ops._FPN_MIN_BATCH = ops._FPN_MIN_BATCH, 1          # the whole-sample kernels are switched on by batch size in production
     try:
         for shape in shapes:
@@ -1340,13 +1442,15 @@ def _assert_tail_grads(got, ref_leaves, params, gamma_floor, what, log=None, fp3
         assert_close(g, r, "%s grad fp64 %s" % (what, k), rel=5e-5, floor=fl)
 
 
-def check_dstd_tail(device, shapes=((3, 20, 7, 9), (2, 8, 10, 22), (5, 64, 6, 11), (3, 32, 5, 8), (4, 16, 6, 6), (2, 40, 4, 5)), replay=False):      # widths of every instantiation of the matrix phases: (1,1) (1,2) (2,4) (4,8) and the run-time form (20, 40)
+def check_dstd_tail(device, shapes=((3, 20, 7, 9), (2, 8, 10, 22), (5, 64, 6, 11), (3, 32, 5, 8), (4, 16, 6, 6), (2, 40, 4, 5)), replay=False, low_var=False):      # widths of every instantiation of the matrix phases: (1,1) (1,2) (2,4) (4,8) and the run-time form (20, 40)
     """ops.dstd_tail (phase kernels of csrc/dstd_tail.hip) against (a) the same chain built from the row kernels and the generic
     contraction: identical dropout draws (same seed word and site ids; exact to rounding, which pins the dropout site ids) and (b) the
     same chain in stock PyTorch in fp64 on the CPU (_dstd_tail_ref; its dropout sites multiply by helpers.hip_keep_scale): train and
     eval mode, output, emitted channel sums, every input / parameter gradient, running statistics.  shapes: (B, C, T, V).
     replay (tensors of millions of elements): the fp64 reference takes the PReLUs on the branches of the fused run and the elements whose
-    backward took the other branch are accounted for (BranchLog, assert_grads_at_kinks)."""
+    backward took the other branch are accounted for (BranchLog, assert_grads_at_kinks).
+    low_var: channels 0 and 1 of all five BatchNorms see a variance comparable to eps (LOW_VAR_BATCH; the two behind the gates w1 / w2 and
+    the one behind the compressor through small gate columns / weight rows)."""
     from cistgcn_amd.models.layers.SE import SELayer2d
     g = _gen(31)
     for (B, C, T, V) in shapes:
@@ -1366,11 +1470,19 @@ def check_dstd_tail(device, shapes=((3, 20, 7, 9), (2, 8, 10, 22), (5, 64, 6, 11
                 se = SELayer2d(C, reduction=8)
                 with torch.no_grad():
                     conv.weight.copy_(0.3 * torch.randn(conv.weight.shape, generator=gg))
+                    if low_var:
+                        _low_var_rows(conv.weight)
+                        for bn in bns:
+                            _low_var_running(bn)
                     se.w1.copy_(0.5 * torch.randn(se.w1.shape, generator=gg)); se.w2.copy_(0.5 * torch.randn(se.w2.shape, generator=gg))
                 mods = nn.ModuleList(bns + al + [conv, se]).to(device)
                 return list(mods[:5]), list(mods[5:10]), mods[10], mods[11], mods
             data = [_rand(g, B, C, T, V), _rand(g, B, C, T, V), _rand(g, B, C, T, V), _rand(g, B, C, T, V), _rand(g, B, C), _rand(g, B, C),
                     _rand(g, B, C, T, V)]
+            if low_var:
+                data[0], data[1] = _low_var_input(data[0]), _low_var_input(data[1])
+                for w in (data[4], data[5]):
+                    w[:, 0] *= LOW_VAR_ROWS[0]; w[:, 1] *= LOW_VAR_ROWS[1]
             gout = _rand(g, B, C, T, V).to(device)
             rparams, rbufs = _ref_state(make()[4])
             results = []
@@ -1404,7 +1516,7 @@ def check_dstd_tail(device, shapes=((3, 20, 7, 9), (2, 8, 10, 22), (5, 64, 6, 11
                 out.backward(gout)
                 grads = [t.grad for t in (y1, y2, r1, r2, w1, w2, bres)] + [p_.grad for p_ in mods.parameters()]
                 results.append((out.detach(), _chan_sums(ost) if (train or not fused) else None, grads, [b.clone() for b in mods.buffers()], acts))
-            what = "dstd_tail B%d C%d T%d V%d %s" % (B, C, T, V, "train" if train else "eval")
+            what = "dstd_tail%s B%d C%d T%d V%d %s" % (" low variance" if low_var else "", B, C, T, V, "train" if train else "eval")
             assert_close(results[0][0], results[1][0], what + " out", rel=2e-5)
             if train:
                 assert_close(results[0][1], results[1][1], what + " sums", rel=1e-6)
@@ -1442,12 +1554,13 @@ def check_dstd_tail(device, shapes=((3, 20, 7, 9), (2, 8, 10, 22), (5, 64, 6, 11
                                   what + " fused | chain", log if replay else None, leaves, both_ways=True)
 
 
-def check_map2adj_tail(device, shapes=((3, 7, 9), (2, 10, 22), (4, 25, 6), (2, 40, 6), (2, 6, 36)), replay=False):
+def check_map2adj_tail(device, shapes=((3, 7, 9), (2, 10, 22), (4, 25, 6), (2, 40, 6), (2, 6, 36)), replay=False, low_var=False):
     """ops.map2adj_tail (phase kernels of csrc/map2adj_tail.hip) against (a) the same chain built from the rank-1 kernel, the
     generic contraction and the row kernels: identical dropout draws (exact to rounding, which pins the dropout site ids) and (b) the
     same chain in stock PyTorch in fp64 on the CPU (_map2adj_tail_ref; its dropout sites multiply by helpers.hip_keep_scale): train and
     eval mode, both adjacencies, the PReLU taps, every input / parameter gradient, running statistics.  shapes: (B, T, V).
-    replay: as in check_dstd_tail (tensors of millions of elements, see BranchLog)."""
+    replay: as in check_dstd_tail (tensors of millions of elements, see BranchLog).  low_var: rows 0 and 1 of the first convolution of both
+    expansors scaled so that their BatchNorm channels see the variances LOW_VAR_BATCH."""
     from cistgcn_amd.models.CISTGCN.CISTGCN import Stage, _conv
     g = _gen(47)
     for (B, T, V) in shapes:
@@ -1462,6 +1575,10 @@ def check_map2adj_tail(device, shapes=((3, 7, 9), (2, 10, 22), (4, 25, 6), (2, 4
                         e[1].weight.copy_(1 + 0.3 * torch.randn(ch, generator=gg)); e[1].bias.copy_(0.3 * torch.randn(ch, generator=gg))
                         e[1].running_mean.copy_(0.2 * torch.randn(ch, generator=gg)); e[1].running_var.copy_(0.5 + torch.rand(ch, generator=gg))
                         e[3].weight.fill_(0.2 + 0.1 * len(exps))
+                    if low_var:
+                        seed_ = torch.einsum("bvt,bxv->bvtx", data[0], data[1]) if len(exps) == 0 else torch.einsum("bvt,btw->btvw", data[2], data[3])
+                        _low_var_rows(e[0].weight, F.conv2d(seed_.double(), e[0].weight.detach().double()))
+                        _low_var_running(e[1])
                     exps.append(e)
                 mods = nn.ModuleList(exps).to(device)
                 return list(mods), mods
@@ -1489,7 +1606,7 @@ def check_map2adj_tail(device, shapes=((3, 7, 9), (2, 10, 22), (4, 25, 6), (2, 4
                 torch.autograd.backward(list(adj), gouts)
                 grads = [t.grad for t in (s0, q0, s1, q1)] + [p_.grad for p_ in mods.parameters()]
                 results.append(([a.detach() for a in adj], [t.detach() for t in taps], grads, [b.clone() for b in mods.buffers()]))
-            what = "map2adj_tail B%d T%d V%d %s" % (B, T, V, "train" if train else "eval")
+            what = "map2adj_tail%s B%d T%d V%d %s" % (" low variance" if low_var else "", B, T, V, "train" if train else "eval")
             for k in range(2):
                 assert_close(results[0][0][k], results[1][0][k], "%s adj[%d]" % (what, k), rel=2e-5)
                 assert_close(results[0][1][k], results[1][1][k], "%s tap[%d]" % (what, k), rel=2e-5)
@@ -1521,11 +1638,12 @@ def check_map2adj_tail(device, shapes=((3, 7, 9), (2, 10, 22), (4, 25, 6), (2, 4
                                   what + " fused | chain", log if replay else None, leaves, both_ways=True)
 
 
-def check_gate_head(device, shapes=((5, 8, 10, 2), (37, 64, 102, 2), (4, 3, 46, 2), (20, 10, 22, 1))):
+def check_gate_head(device, shapes=((5, 8, 10, 2), (37, 64, 102, 2), (4, 3, 46, 2), (20, 10, 22, 1)), low_var=False):
     """ops.gate_head (csrc/gate_head.hip) against stock PyTorch in fp64: BatchNorm2d -> Dropout(0) -> PReLU -> cat(statistics) -> Linear ->
     BatchNorm1d -> PReLU -> Linear per gate path (CISTGCN.py:337-352): gates, both PReLU taps, dz, the statistics' gradient, every
     parameter gradient, running statistics; train and eval mode; the statistics handed over as column slices of a wider tensor.
-    Dropout: keep factors of helpers.hip_keep_scale applied in the reference.  shapes: (B, C, S, paths)."""
+    Dropout: keep factors of helpers.hip_keep_scale applied in the reference.  shapes: (B, C, S, paths).  low_var: channels 0 and 1 of z
+    have the variances LOW_VAR_BATCH (BatchNorm2d), rows 0 and 1 of the first Linear are small (BatchNorm1d)."""
     from cistgcn_amd.models.CISTGCN.CISTGCN import Stage
     from helpers import hip_keep_scale
     g = _gen(91)
@@ -1543,14 +1661,19 @@ def check_gate_head(device, shapes=((5, 8, 10, 2), (37, 64, 102, 2), (4, 3, 46, 
                             bn.running_mean.copy_(0.2 * torch.randn(C, generator=gg)); bn.running_var.copy_(0.5 + torch.rand(C, generator=gg))
                         mp[0].weight.copy_(torch.randn(mp[0].weight.shape, generator=gg) * 0.3); mp[4].weight.copy_(torch.randn(C, C, generator=gg) * 0.3)
                         conv[7].weight.fill_(0.1 + 0.1 * k); mp[3].weight.fill_(0.3 - 0.1 * k)
+                    if low_var:
+                        _low_var_rows(mp[0].weight)
+                        _low_var_running(conv[5]); _low_var_running(mp[1])
                     convs.append(conv); maps.append(mp)
                 return nn.ModuleList(convs).to(dt), nn.ModuleList(maps).to(dt)
             z0 = [0.5 + 1.5 * _rand(g, B, C) for _ in range(n)]
+            if low_var:
+                z0 = [_low_var_input(t) for t in z0]
             wide = _rand(g, B, S + 5)
             gw = [_rand(g, B, C) for _ in range(n)]
             salts = [(3 + k, 11 + k) for k in range(n)]
             seed = 987654321
-            what = "gate_head B%d C%d S%d x%d %s p=%.2f" % (B, C, S, n, "train" if train else "eval", pdrop)
+            what = "gate_head%s B%d C%d S%d x%d %s p=%.2f" % (" low variance" if low_var else "", B, C, S, n, "train" if train else "eval", pdrop)
             # fp64 reference (the keep factors of the kernels' hash)
             rc, rm = make(torch.float64)
             rc.train(train); rm.train(train)
@@ -1586,17 +1709,22 @@ def check_gate_head(device, shapes=((5, 8, 10, 2), (37, 64, 102, 2), (4, 3, 46, 
                     floor = max(1e-3, float(pb.grad.abs().max()))
                     if train and kname.endswith("0.weight"):      # Linear in front of a train-mode BatchNorm1d: remainder of cancelling sums
                         floor = max(floor, float(mods_r[int(kname.split(".")[0])][1].weight.grad.abs().max()))
+                    if low_var and train and mods_d is dm and kname.endswith("3.weight"):
+                        # the slope gradient behind the BatchNorm1d: one number, the sum of B * C cancelling terms (8.3e-3 here).  Measured on
+                        # (5, 8, 10, 2), p = 0.25, path 1, against float64: stock float32 PyTorch on the CPU 3.922e-7, the kernel 2.047e-7 on the
+                        # shim and 8.775e-7 on the MI355X, with the bound above at 4.167e-7; the bound is 4 x the stock error
+                        floor = max(floor, 4.0 * 3.922e-7 / 5e-5)
                     assert_close(pa.grad, pb.grad, "%s grad %s" % (what, kname), rel=5e-5, floor=floor)
                 for (kname, ba), (_, bb) in zip(mods_d.named_buffers(), mods_r.named_buffers()):
                     assert_close(ba.float(), bb.float(), "%s buffer %s" % (what, kname), rel=1e-5)
 
 
 def check_tower_maps(device, shapes=((3, 10, (5, 5, 5, 5), 7, 8), (2, 20, (10, 16), 6, 6), (2, 12, (16, 5, 7), 3, 14), (3, 64, (32, 32, 32, 32), 5, 12), (2, 32, (16, 16, 16, 16), 5, 8)),
-                     replay=False):
+                     replay=False, low_var=False):
     """ops.tower_maps (pointwise maps + BatchNorm2d + PReLU as one operator; backward: cg_norm_act_bwd_reduce_many + cg_pointwise_maps_bwd
     undoing BatchNorm / PReLU on load) against stock PyTorch in fp64: outputs, dx, every dW / dgamma / dbeta / dalpha, running statistics,
     train and eval mode.  shapes: (B, Cin, (M_i), T, V).  replay: the reference takes the PReLU branches of the HIP run (BranchLog; for
-    tensors of millions of elements)."""
+    tensors of millions of elements).  low_var: rows 0 and 1 of every map scaled so that its BatchNorm channels see LOW_VAR_BATCH."""
     g = _gen(83)
     for (B, C, Ms, T, V) in shapes:
         for train in (True, False):
@@ -1615,11 +1743,14 @@ def check_tower_maps(device, shapes=((3, 10, (5, 5, 5, 5), 7, 8), (2, 20, (10, 1
                         bn.running_mean.copy_(0.2 * torch.randn(M, generator=gg)); bn.running_var.copy_(0.5 + torch.rand(M, generator=gg))
                         if not plain:
                             pr.weight.fill_(0.1 + 0.1 * k)
+                    if low_var:
+                        _low_var_rows(conv.weight, F.conv2d(x0.double(), conv.weight.detach().double()), conv.bias if plain else None)
+                        _low_var_running(bn)
                     mods.append(nn.Sequential(conv, bn, pr))
                 return nn.ModuleList(mods).to(dt)
             x0 = 0.3 + _rand(g, B, C, T, V)
             gs = [_rand(g, B, M, T, V) for M in Ms]
-            what = "tower_maps B%d C%d M%s T%d V%d %s" % (B, C, Ms, T, V, "train" if train else "eval")
+            what = "tower_maps%s B%d C%d M%s T%d V%d %s" % (" low variance" if low_var else "", B, C, Ms, T, V, "train" if train else "eval")
             net = make(torch.float32).to(device).train(train)
             xd = _leaf(x0, device)
             ops.begin_step(device)
@@ -1639,6 +1770,11 @@ def check_tower_maps(device, shapes=((3, 10, (5, 5, 5, 5), 7, 8), (2, 20, (10, 1
                 floor = max(1e-3, float(pb.grad.abs().max()))
                 if train and (k.endswith("0.weight") or k.endswith("0.bias")):           # in front of a train-mode BatchNorm: the remainder of cancelling sums
                     floor = max(floor, float(ref[int(k.split(".")[0])][1].weight.grad.abs().max()))
+                if low_var and train and k.endswith("0.bias"):
+                    # analytically zero, and its cancelling sums carry the 1 / sqrt(var + eps) ~ 950 of a channel of variance 0.1 eps.  Measured
+                    # on (3, 10, (5, 5, 5, 5), 7, 8) against float64: stock float32 PyTorch on the CPU 9.766e-4, the kernel 1.709e-3 (shim) with
+                    # the bound above at 6.327e-4; the bound is 4 x the stock error, the factor of the kinematics checks
+                    floor = max(floor, 4.0 * 9.766e-4 / 5e-5)
                 names.append(k); got.append(pa.grad); leaves.append(pb); floors.append(floor)
             assert_grads_at_kinks(got, [t.grad for t in leaves], floors, names, what, log if replay else None, leaves)
             for (k, ba), (_, bb) in zip(net.named_buffers(), ref.named_buffers()):
@@ -1646,12 +1782,13 @@ def check_tower_maps(device, shapes=((3, 10, (5, 5, 5, 5), 7, 8), (2, 20, (10, 1
 
 
 def check_tower_collapse(device, shapes=((3, 10, (8, 8, 8, 8), 6, 8, 5), (2, 64, (32, 32, 32, 32), 50, 22, 32), (3, 16, (8, 8, 8, 8), 10, 18, 20), (2, 12, (16, 12), 5, 6, 7)),
-                         replay=False):
+                         replay=False, low_var=False):
     """The first tower level DEFERRED into its collapsing convolutions (`ops.tower_maps(defer=True)` + `ops.collapse_rows / collapse_cols`
     with `transform`: BatchNorm2d + PReLU applied on load, the activated maps never stored) against stock PyTorch in fp64: collapsed outputs,
     their channel sums, dx, every gradient (map weights, BatchNorm, PReLU slope, collapsing weights), running statistics; train and eval.
     Maps alternate between the frame-collapsing (T,1) and the joint-collapsing (1,V) convolution.  shapes: (B, Cin, (M_i), T, V, O).
-    replay: the reference takes the PReLU branches of the HIP run (BranchLog; the activated maps are written out as branch records then)."""
+    replay: the reference takes the PReLU branches of the HIP run (BranchLog; the activated maps are written out as branch records then).
+    low_var: as in check_tower_maps - here the BatchNorm is the deferred transform of the collapsing kernels."""
     g = _gen(89)
     for (B, C, Ms, T, V, O) in shapes:
         for train in (True, False):
@@ -1667,11 +1804,14 @@ def check_tower_collapse(device, shapes=((3, 10, (8, 8, 8, 8), 6, 8, 5), (2, 64,
                         bn.weight.copy_(1 + 0.3 * torch.randn(M, generator=gg)); bn.bias.copy_(0.3 * torch.randn(M, generator=gg))
                         bn.running_mean.copy_(0.2 * torch.randn(M, generator=gg)); bn.running_var.copy_(0.5 + torch.rand(M, generator=gg))
                         pr.weight.fill_(0.1 + 0.1 * k)
+                    if low_var:
+                        _low_var_rows(conv.weight, F.conv2d(x0.double(), conv.weight.detach().double()))
+                        _low_var_running(bn)
                     mods.append(nn.Sequential(conv, bn, pr, col))
                 return nn.ModuleList(mods).to(dt)
             x0 = 0.3 + _rand(g, B, C, T, V)
             gs = [_rand(g, B, O, 1, V) if k % 2 == 0 else _rand(g, B, O, T, 1) for k in range(len(Ms))]
-            what = "tower_collapse B%d C%d M%s T%d V%d O%d %s" % (B, C, Ms, T, V, O, "train" if train else "eval")
+            what = "tower_collapse%s B%d C%d M%s T%d V%d O%d %s" % (" low variance" if low_var else "", B, C, Ms, T, V, O, "train" if train else "eval")
             net = make(torch.float32).to(device).train(train)
             xd = _leaf(x0, device)
             ops.begin_step(device)
@@ -1712,11 +1852,11 @@ def check_tower_collapse(device, shapes=((3, 10, (8, 8, 8, 8), 6, 8, 5), (2, 64,
                 assert_close(ba.float(), bb.float(), "%s buffer %s" % (what, k), rel=1e-5)
 
 
-def check_block_input(device, shapes=((3, 5, 4, 6, 3), (2, 10, 10, 22, 7), (4, 64, 5, 22, 8), (2, 6, 5, 5, 2), (3, 3, 22, 25, 4))):
+def check_block_input(device, shapes=((3, 5, 4, 6, 3), (2, 10, 10, 22, 7), (4, 64, 5, 22, 8), (2, 6, 5, 5, 2), (3, 3, 22, 25, 4)), low_var=False):
     """ops.block_input (csrc/block_input.hip) against stock PyTorch BatchNorm2d + the oracle's block statistics (CISTGCN.py:360-379):
     the aliases of xn, the statistics, running statistics; backward with a different gradient on every alias and on both statistics
     outputs: dx, dgamma, dbeta.  Train and eval mode, with and without channel sums handed over by the producer, plane sizes of
-    16-, 8- and 4-byte alignment.  shapes: (B, C, T, V, n aliases)."""
+    16-, 8- and 4-byte alignment.  shapes: (B, C, T, V, n aliases).  low_var: channels 0 and 1 of x have the variances LOW_VAR_BATCH."""
     g = _gen(71)
     for (B, C, T, V, n) in shapes:
         for train in (True, False):
@@ -1727,11 +1867,15 @@ def check_block_input(device, shapes=((3, 5, 4, 6, 3), (2, 10, 10, 22, 7), (4, 6
                     with torch.no_grad():
                         bn.weight.copy_(1 + 0.3 * torch.randn(C, generator=gg)); bn.bias.copy_(0.3 * torch.randn(C, generator=gg))
                         bn.running_mean.copy_(0.2 * torch.randn(C, generator=gg)); bn.running_var.copy_(0.5 + torch.rand(C, generator=gg))
+                    if low_var:
+                        _low_var_running(bn)
                     return bn.to(dt)
                 x0 = 0.7 + 2.0 * _rand(g, B, C, T, V)
+                if low_var:
+                    x0 = _low_var_input(x0)
                 gxs = [_rand(g, B, C, T, V) if i != 1 else None for i in range(n)]          # one consumer without a gradient
                 gst = [_rand(g, B, 2 + 2 * T), _rand(g, B, 7 + 2 * T)[:, 3:5 + 2 * T]]         # the second one: a column slice (the gate inputs' gradient)
-                what = "block_input B%d C%d T%d V%d %s%s" % (B, C, T, V, "train" if train else "eval", " (sums given)" if given_stats else "")
+                what = "block_input%s B%d C%d T%d V%d %s%s" % (" low variance" if low_var else "", B, C, T, V, "train" if train else "eval", " (sums given)" if given_stats else "")
                 # reference in fp64
                 ref = make(torch.float64).train(train)
                 xr = _leaf(x0.double(), "cpu")
@@ -1780,10 +1924,11 @@ def check_block_input(device, shapes=((3, 5, 4, 6, 3), (2, 10, 10, 22, 7), (4, 6
         assert_close(xd.grad, xr.grad, "block_input dx (%s only)" % only, rel=5e-5, floor=max(1e-3, float(xr.grad.abs().max())))
 
 
-def check_context_heads(device, shapes=((3, 5, 12, 7), (4, 25, 66, 64), (2, 3, 10, 33))):
+def check_context_heads(device, shapes=((3, 5, 12, 7), (4, 25, 66, 64), (2, 3, 10, 33)), low_var=False):
     """ops.context_heads (csrc/context_heads.hip) against stock PyTorch modules Conv2d(1, C, 1) -> BatchNorm2d -> PReLU and the
     reference's reductions (CISTGCN.py:465, :467): outputs, the PReLU taps, input gradient, every parameter gradient, running
-    statistics; train and eval mode.  shapes: (B, H, W, C)."""
+    statistics; train and eval mode.  shapes: (B, H, W, C).  low_var: w[0] and w[1] of both heads small enough for the variances
+    LOW_VAR_BATCH of w[c] * x."""
     from cistgcn_amd.models.CISTGCN.CISTGCN import Stage, _conv
     g = _gen(61)
     for (B, H, W, C) in shapes:
@@ -1798,11 +1943,14 @@ def check_context_heads(device, shapes=((3, 5, 12, 7), (4, 25, 66, 64), (2, 3, 1
                         hd[1].weight.copy_(1 + 0.3 * torch.randn(C, generator=gg)); hd[1].bias.copy_(0.3 * torch.randn(C, generator=gg))
                         hd[1].running_mean.copy_(0.2 * torch.randn(C, generator=gg)); hd[1].running_var.copy_(0.5 + torch.rand(C, generator=gg))
                         hd[2].weight.fill_(0.15 + 0.2 * k)
+                    if low_var:
+                        _low_var_rows(hd[0].weight, F.conv2d(x0.double(), hd[0].weight.detach().double()))
+                        _low_var_running(hd[1])
                     heads.append(hd)
                 return nn.ModuleList(heads)
             x0 = 1.5 + 3.0 * _rand(g, B, 1, H, W)
             g0, g1 = _rand(g, B, C), _rand(g, B, C)
-            what = "context_heads B%d H%d W%d C%d %s" % (B, H, W, C, "train" if train else "eval")
+            what = "context_heads%s B%d H%d W%d C%d %s" % (" low variance" if low_var else "", B, H, W, C, "train" if train else "eval")
             # stock PyTorch in fp64: the weight of a convolution in front of a train-mode BatchNorm has a gradient that is the small
             # remainder of cancelling sums; the stock fp32 path is 1e-4 .. 3e-4 off its own fp64 run there (B16 H25 W75), the kernel
             # (f64 channel sums, closed form) 2e-6 .. 3e-5

@@ -13,6 +13,8 @@ INCLUDE = os.path.join(ROOT, "include")      # cistgcn_hip.h, which csrc/cg_comm
 # with ASAN_OPTIONS=detect_leaks=0); the GPU pool offers no device sanitizer, this is where out-of-bounds indexing is hunted.
 SANITIZE = os.environ.get("HIPEMU_SANITIZE", "0") == "1"
 OUT = os.path.join(HERE, "_build", "libcistgcn_emu_asan.so" if SANITIZE else "libcistgcn_emu.so")
+# tools/mutants.py points CSRC, INCLUDE and OUT at an edited copy of the sources; the objects of such a build go next to its library, never
+# into the cache of the real one
 
 
 def build(force=False):
@@ -41,7 +43,7 @@ def _build_locked(force):
 
     def compile_one(s):
         # one object per source, reused while neither the source nor a header changed
-        o = os.path.join(HERE, "_build", os.path.basename(s) + (".asan.o" if SANITIZE else ".o"))
+        o = os.path.join(os.path.dirname(OUT), os.path.basename(s) + (".asan.o" if SANITIZE else ".o"))
         if not force and os.path.exists(o) and os.path.getmtime(o) > max(os.path.getmtime(s), hdr_time):
             return o, None
         cmd = ["g++", "-x", "c++", "-std=c++17", "-O1", "-g", "-fPIC", "-pthread", "-Wno-unknown-pragmas", "-Wno-attributes",
