@@ -429,7 +429,7 @@ __global__ __launch_bounds__(CG_TAIL_THREADS, 2) void cg_tail_f2_kernel(CgDstdTa
       // per lane, combined over the four lanes l15 + 16 * slot of a channel by two exchanges
       const int co = 16 * mt + l15;
       const bool cok = co < C;
-      float s1 = 0.f, s2 = 0.f;
+      double s1 = 0.0, s2 = 0.0;                               // f64 per element, as in cg_tail_f1_kernel: h0 has no bias, but its inputs carry betas
 #pragma unroll
       for (int h = 0; h < 2; ++h) {
         const int pq = (h ? n1 : n0) + 4 * slot;
@@ -441,17 +441,17 @@ __global__ __launch_bounds__(CG_TAIL_THREADS, 2) void cg_tail_f2_kernel(CgDstdTa
           for (int q = 0; q < 4; ++q) {
             if (pq + q < np) {
               if (!vec) dst[q] = cc[q];
-              s1 += cc[q]; s2 += cc[q] * cc[q];
+              s1 += (double)cc[q]; s2 += (double)cc[q] * (double)cc[q];
             }
           }
         }
       }
       if (t.train) {
-        if (MT_) { fsum[MT_ ? ti : 0][0] += (double)s1; fsum[MT_ ? ti : 0][1] += (double)s2; }      // known widths: task ti of a wave is the same channel tile in every tile
+        if (MT_) { fsum[MT_ ? ti : 0][0] += s1; fsum[MT_ ? ti : 0][1] += s2; }      // known widths: task ti of a wave is the same channel tile in every tile
         else {
           s1 += __shfl_xor(s1, 16, 64); s2 += __shfl_xor(s2, 16, 64);
           s1 += __shfl_xor(s1, 32, 64); s2 += __shfl_xor(s2, 32, 64);
-          if (slot == 0 && cok) { atomicAdd(&sStat[2 * co], (double)s1); atomicAdd(&sStat[2 * co + 1], (double)s2); }
+          if (slot == 0 && cok) { atomicAdd(&sStat[2 * co], s1); atomicAdd(&sStat[2 * co + 1], s2); }
         }
       }
     }

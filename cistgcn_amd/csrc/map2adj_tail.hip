@@ -127,7 +127,7 @@ __device__ __forceinline__ void cg_adj_m1_body(const CgAdjTail& t, const CgAdjGe
   const int mt = wave % MT, u = 16 * mt + l15;
   const bool uok = u < t.Kc;
   const float* ap = cg_tfrag_ptr<0>(sW + 16 * mt * K::WS, K::WS, l15, slot);
-  float s1 = 0.f, s2 = 0.f;
+  double s1 = 0.0, s2 = 0.0;                                             // f64 per element (cg_bn.h), over every group of this wave
   for (int w = wave; w < ngroups * MT; w += CG_ADJ_THREADS / 64) {       // (group of 32 positions, u tile)
     const int grp = w / MT, p0 = P0 + 32 * grp;
     const int pa = p0 + l15, pb = p0 + 16 + l15;
@@ -156,17 +156,20 @@ __device__ __forceinline__ void cg_adj_m1_body(const CgAdjTail& t, const CgAdjGe
         if (vec) {
           if (pq < g.Pn) {
             *reinterpret_cast<float4*>(dst) = make_float4(c[0], c[1], c[2], c[3]);
-            s1 += (c[0] + c[1]) + (c[2] + c[3]); s2 += (c[0] * c[0] + c[1] * c[1]) + (c[2] * c[2] + c[3] * c[3]);
+            if (t.train) {
+#pragma unroll
+              for (int q = 0; q < 4; ++q) { s1 += (double)c[q]; s2 += (double)c[q] * (double)c[q]; }
+            }
           }
         } else {
 #pragma unroll
           for (int q = 0; q < 4; ++q)
-            if (pq + q < g.Pn) { dst[q] = c[q]; s1 += c[q]; s2 += c[q] * c[q]; }
+            if (pq + q < g.Pn) { dst[q] = c[q]; s1 += (double)c[q]; s2 += (double)c[q] * (double)c[q]; }
         }
       }
     }
   }
-  if (t.train && uok) { atomicAdd(&sStat[2 * u], (double)s1); atomicAdd(&sStat[2 * u + 1], (double)s2); }
+  if (t.train && uok) { atomicAdd(&sStat[2 * u], s1); atomicAdd(&sStat[2 * u + 1], s2); }
   if (t.train) {
     __syncthreads();
     double* rep = t.bn.stats + (long long)(blockIdx.x % CG_STAT_REPLICAS) * 2 * t.Kc;

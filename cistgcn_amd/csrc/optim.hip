@@ -11,7 +11,7 @@ __global__ void cg_adam_flat_kernel(float* __restrict__ p, const float* __restri
                                     float bc1, float bc2_sqrt) {
   for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
     float gi = g[i] * gscale;
-    if (clip > 0.f) gi = fminf(fmaxf(gi, -clip), clip);
+    if (clip > 0.f) gi = gi < -clip ? -clip : (gi > clip ? clip : gi);          // clamp_: a NaN gradient stays NaN (fminf / fmaxf would return the bound)
     const float pi = p[i];
     gi += wd * pi;
     const float mi = b1 * m[i] + (1.f - b1) * gi;

@@ -345,10 +345,10 @@ __global__ __launch_bounds__(256) void cg_stgcn_domain_fwd_mfma_kernel(const flo
         const bool ok = co < g.Cout && pos_ok;
         const float v = ok ? acc[q] + (bias ? bias[co] : 0.f) : 0.f;
         if (ok) yb[co * TV + cg_dom_off<DOMAIN>(g, g0 + grp, o)] = v;
-        if (ystats) {          // the 16 lanes of a row hold the same channel: reduce them before touching LDS
-          float s1 = v, s2 = v * v;
+        if (ystats) {          // the 16 lanes of a row hold the same channel: reduce them (f64 per element: cg_bn.h) before touching LDS
+          double s1 = (double)v, s2 = (double)v * (double)v;
           s1 = cg_row16_sum(s1); s2 = cg_row16_sum(s2);
-          if (l15 == 0 && co < g.Cout) { atomicAdd(&sStat[2 * co], (double)s1); atomicAdd(&sStat[2 * co + 1], (double)s2); }
+          if (l15 == 0 && co < g.Cout) { atomicAdd(&sStat[2 * co], s1); atomicAdd(&sStat[2 * co + 1], s2); }
         }
       }
     }

@@ -428,10 +428,10 @@ __global__ __launch_bounds__(CG_DOMM_THREADS, 2) void cg_stgcn_domain_fwd_mfma2_
         const float v0 = (ok0 && cok) ? c0[q] + bv : 0.f, v1 = (ok1 && cok) ? c1[q] + bv : 0.f;
         if (ok0 && cok) yb[co * TV + a0] = v0;
         if (ok1 && cok) yb[co * TV + a1] = v1;
-        if (ystats) {          // the 16 lanes of a slot hold the same channel: reduce them before touching LDS
-          float s1 = v0 + v1, s2 = v0 * v0 + v1 * v1;
+        if (ystats) {          // the 16 lanes of a slot hold the same channel: reduce them (f64 per element: cg_bn.h) before touching LDS
+          double s1 = (double)v0 + (double)v1, s2 = (double)v0 * (double)v0 + (double)v1 * (double)v1;
           s1 = cg_row16_sum(s1); s2 = cg_row16_sum(s2);
-          if (l15 == 0 && cok) { atomicAdd(&sStat[2 * co], (double)s1); atomicAdd(&sStat[2 * co + 1], (double)s2); }
+          if (l15 == 0 && cok) { atomicAdd(&sStat[2 * co], s1); atomicAdd(&sStat[2 * co + 1], s2); }
         }
       }
     }

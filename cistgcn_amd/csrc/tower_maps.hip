@@ -178,7 +178,7 @@ __global__ __launch_bounds__(CG_PWM_THREADS) void cg_pwm_fwd_kernel(CgPwArgs a) 
       }
       const int i = g.tile_map[nt], m = g.tile_row0[nt] + l15;
       if (m < t.M[i]) {
-        float s1 = 0.f, s2 = 0.f;
+        double s1 = 0.0, s2 = 0.0;                               // f64 per element (cg_bn.h): a channel riding on its bias has |mean| >> std
         const float bv = sBias[16 * nt + l15];
 #pragma unroll
         for (int h = 0; h < 2; ++h) {
@@ -188,12 +188,15 @@ __global__ __launch_bounds__(CG_PWM_THREADS) void cg_pwm_fwd_kernel(CgPwArgs a) 
           if (pq < np) {
             cg_pwm_store_quad(g, t.y[i] + ((long long)b * t.M[i] + m) * t.P + p0, pq, np, c);
             if (pq + 2 >= np) { c[2] = 0.f; c[3] = 0.f; }        // half quad at the end of a row (P % 4 == 2)
-            s1 += (c[0] + c[1]) + (c[2] + c[3]); s2 += (c[0] * c[0] + c[1] * c[1]) + (c[2] * c[2] + c[3] * c[3]);
+            if (stats) {
+#pragma unroll
+              for (int q = 0; q < 4; ++q) { s1 += (double)c[q]; s2 += (double)c[q] * (double)c[q]; }
+            }
           }
         }
         if (stats) {
-          if (kKeepSums) { keep1 += (double)s1; keep2 += (double)s2; }       // one channel per lane over every task and tile of this wave
-          else { atomicAdd(&sStat[2 * (16 * nt + l15)], (double)s1); atomicAdd(&sStat[2 * (16 * nt + l15) + 1], (double)s2); }
+          if (kKeepSums) { keep1 += s1; keep2 += s2; }       // one channel per lane over every task and tile of this wave
+          else { atomicAdd(&sStat[2 * (16 * nt + l15)], s1); atomicAdd(&sStat[2 * (16 * nt + l15) + 1], s2); }
         }
       }
     }

@@ -189,17 +189,17 @@ def keep_masks(device, B, data, p, salts, seed=1234):
     return [k.cpu().reshape(d["x"].shape).double() for k, d in zip(ks, data)]
 
 
-def reference(d, keep, train):
-    """fp64 on the CPU: outputs and gradients of one item"""
-    x = d["x"].detach().double().requires_grad_(True)
-    gamma, beta = d["gamma"].double().requires_grad_(True), d["beta"].double().requires_grad_(True)
-    alpha, w = d["alpha"].double().requires_grad_(True), d["w"].double().requires_grad_(True)
+def reference(d, keep, train, dtype=torch.float64):
+    """fp64 on the CPU: outputs and gradients of one item (dtype: the same chain in float32, the yardstick of check_off_centre)"""
+    x = d["x"].detach().clone().to(dtype).requires_grad_(True)
+    gamma, beta = d["gamma"].detach().clone().to(dtype).requires_grad_(True), d["beta"].detach().clone().to(dtype).requires_grad_(True)
+    alpha, w = d["alpha"].detach().clone().to(dtype).requires_grad_(True), d["w"].detach().clone().to(dtype).requires_grad_(True)
     C = x.shape[1]
     if train:
         mean, var = x.mean((0, 2)), x.var((0, 2), unbiased=False)
     else:
-        mean, var = d["rm"].double(), d["rv"].double()
-    u = ((x - mean.view(1, C, 1)) / torch.sqrt(var.view(1, C, 1) + 1e-5) * gamma.view(1, C, 1) + beta.view(1, C, 1)) * keep
+        mean, var = d["rm"].to(dtype), d["rv"].to(dtype)
+    u = ((x - mean.view(1, C, 1)) / torch.sqrt(var.view(1, C, 1) + 1e-5) * gamma.view(1, C, 1) + beta.view(1, C, 1)) * keep.to(dtype)
     if d["act"]:
         live = u.detach().abs()[keep > 0]
         assert float(live.min()) >= KINK, "an input sits at a PReLU kink: min |u| = %g" % float(live.min())
@@ -207,7 +207,7 @@ def reference(d, keep, train):
     else:
         h = u
     y = torch.einsum("ocl,bcl->bo", w, h) if d["kind"] == FULL else torch.einsum("oc,bcl->bol", w, h)
-    (y * d["dy"].double()).sum().backward()
+    (y * d["dy"].to(dtype)).sum().backward()
     r = dict(y=y.detach(), dx=x.grad, dgamma=gamma.grad, dbeta=beta.grad, dW=w.grad, mean=mean.detach(), var=var.detach())
     if d["act"]:
         r["dalpha"] = alpha.grad
@@ -287,6 +287,66 @@ def check_low_variance(device):
             assert_close(new[i]["y"].reshape(ref["y"].shape), ref["y"], what + " y", rel=2e-5)
             for k in ("dx", "dgamma", "dbeta", "dalpha", "dW"):
                 assert_close(new[i][k].reshape(ref[k].shape), ref[k], "%s %s" % (what, k), rel=5e-5, floor=max(1e-3, float(ref[k].abs().max())))
+
+
+OFF_CENTRE_CASES = (LOW_VAR_CASE, (37, [(FULL, 6, 22, 50, True), (PW, 32, 50, 22, False)], False))
+
+
+def check_off_centre(device):
+    """channels 0 and 1 of every item far off centre (checks.OFF_CENTRE), both item kinds, train and eval mode.  As in check_low_variance the
+    new route is held to the fp64 evaluation itself (both routes of check_operator share csrc/cg_bn.h); the bound is
+    checks.assert_within_stock: 4 x the error of `reference` in float32, on top of the bounds of check_low_variance.  The forward takes the
+    producer's f64 sums; the backward forms dgamma / dbeta and the two means of the BatchNorm backward itself.  Cases: the one of
+    check_low_variance, and the widest full item with the pointwise item of the longest rows of CASES["six"]."""
+    import checks
+    for case in OFF_CENTRE_CASES:
+        B, base, stacked = make_inputs(case)
+        salts = [11 + 3 * i for i in range(len(base))]
+        for mode in ("train", "eval-drop"):
+            train, p = MODES[mode]
+
+            def build(ratios):
+                data = []
+                for d in base:
+                    d = dict(d)
+                    d["x"] = checks._off_centre_input(d["x"], ratios=ratios)
+                    d["rm"], d["rv"] = d["rm"].clone(), d["rv"].clone()
+                    for c, r in enumerate(ratios):
+                        if r:
+                            d["rv"][c] = float(d["x"][:, c].double().var(unbiased=False))
+                            d["rm"][c] = r * float(d["rv"][c].double().sqrt())
+                    data.append(d)
+                return data
+
+            def stock(dtype, ratios):
+                res = {}
+                for i, d in enumerate(build(ratios)):
+                    ref = reference(d, torch.ones(d["x"].shape, dtype=torch.float64), train, dtype)
+                    res.update({"item %d %s" % (i, k): ref[k] for k in ("y", "dx", "dgamma", "dbeta", "dalpha", "dW", "tap") if k in ref})
+                    if train:
+                        res["item %d mean" % i] = ref["mean"]
+                return res
+
+            def kernel():
+                data = build(checks.OFF_CENTRE)
+                new = run_route(device, B, data, stacked, True, train, p, salts)
+                res = {}
+                for i, d in enumerate(data):
+                    res.update({"item %d %s" % (i, k): new[i][k].reshape(d["dy"].shape if k == "y" else new[i][k].shape) for k in ("y", "dx", "dgamma", "dbeta", "dalpha", "dW", "tap") if k in new[i]})
+                    if train:
+                        res["item %d mean" % i] = new[i]["rm"]          # momentum 1: the running mean is the batch mean the forward saved
+                return res
+
+            def family(name, refs):
+                ref = refs[name].double()
+                k = name.split()[-1]
+                if k == "tap":          # 2^-20 * max|tap| in check_low_variance: a float32 mean of a channel at 300 std is itself 2^-24 * 300 std off, 9e-6 here - stock alone
+                    return None
+                if k in ("y", "mean"):
+                    return 2e-5 * max(1.0, float(ref.abs().max()))
+                return 5e-5 * max(1e-3, float(ref.abs().max()))
+
+            checks.assert_within_stock("block_mid off centre B%d %s %s" % (B, [it[:4] for it in case[1]], mode), kernel, stock, family)
 
 
 def _guarded(n, dtype, device):

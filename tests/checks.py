@@ -73,6 +73,167 @@ def _low_var_running(bn):
             bn.running_mean[c] *= 1e-3
 
 
+# ---- channels far off centre ----------------------------------------------------------------------------------------------------
+# Every BatchNorm statistic of the library is E[x^2] - E[x]^2 from {sum, sum of squares} (csrc/cg_bn.h), which is safe only while both sums
+# are carried in float64 per element: an f32 partial sum of squares of a channel at |mean| / std = r loses r^2 * 6e-8 of the variance.  The
+# families' own data is centred (|mean| / std < 1) and cannot tell.  `off_centre` cases put channels 0 and 1 of every BatchNorm at the
+# ratios OFF_CENTRE (opposite signs; every other channel stays as generated: the control) and hold the kernel to 4 x the error of stock
+# float32 PyTorch against float64 on the same float32 values (assert_within_stock), on top of the family's own bound.
+OFF_CENTRE = (30.0, -300.0)
+OFF_CENTRE_NONE = (0.0, 0.0)          # "the same case with offsets 0": the second measurement of the stock error
+
+
+def _ratio_ok(v, ratio, what):
+    """precondition of a case: the float32 channel v has |mean| / std within 10 % of the target (a target of 0 asks nothing)"""
+    if ratio == 0.0:
+        return
+    v = v.detach().double()
+    got = float(v.mean()) / float(v.std(unbiased=False))
+    assert abs(got - ratio) <= 0.1 * abs(ratio), "%s: mean / std = %.2f, wanted %.1f" % (what, got, ratio)
+
+
+def _off_centre_input(x, dim=1, ratios=OFF_CENTRE):
+    """a copy of the data tensor x with ratios[c] * std(channel c) added to channels 0 and 1 (along `dim`) in float64, rounded to float32 once"""
+    x = x.clone().movedim(dim, 0)
+    for c, ratio in enumerate(ratios):
+        v = x[c].double()
+        x[c] = (v + ratio * float(v.std(unbiased=False))).float()
+        _ratio_ok(x[c], ratio, "off-centre input channel %d" % c)
+    return x.movedim(0, dim).contiguous()
+
+
+def _map_fwd(conv):
+    w = conv.weight.detach().double()
+    bias = None if conv.bias is None else conv.bias.detach().double()
+    return (lambda t: F.linear(t, w, bias)) if w.dim() == 2 else (lambda t: F.conv2d(t, w, bias))
+
+
+def _off_centre_pair(conv, x, ratios=OFF_CENTRE, candidates=None, pair=None):
+    """(k0, d0, k1, d1): the constants d0 / d1 which, added to the input channels k0 / k1 of the bias-free map `conv` with the input x,
+    put its output channels 0 and 1 on the ratios - solved in float64.  The pair (among `candidates`, default every input channel) is the
+    one whose 2 x 2 matrix of weight sums over the kernel taps (the shift of output channels 0 and 1 per unit constant) has the largest
+    determinant, so no column sum near zero is divided by."""
+    w = conv.weight.detach().double()
+    y = _map_fwd(conv)(x.double())
+    s = w.flatten(2).sum(-1) if w.dim() > 2 else w          # [O, Cin]
+    if pair is None:
+        cand = list(range(s.shape[1])) if candidates is None else list(candidates)
+        best = None
+        for i, k0 in enumerate(cand):
+            for k1 in cand[i + 1:]:
+                det = float(s[0, k0] * s[1, k1] - s[0, k1] * s[1, k0])
+                if best is None or abs(det) > abs(best[0]):
+                    best = (det, k0, k1)
+        pair = best[1:]
+    k0, k1 = pair
+    det = float(s[0, k0] * s[1, k1] - s[0, k1] * s[1, k0])
+    assert abs(det) > 1e-3 * float(s[:2].abs().max()) ** 2, "no pair of input channels moves output channels 0 and 1 independently"
+    t = []
+    for c in range(2):
+        v = y.transpose(0, 1)[c]
+        t.append(ratios[c] * float(v.std(unbiased=False)) - float(v.mean()) if ratios[c] else 0.0)
+    d0 = (t[0] * float(s[1, k1]) - t[1] * float(s[0, k1])) / det
+    d1 = (t[1] * float(s[0, k0]) - t[0] * float(s[1, k0])) / det
+    return k0, d0, k1, d1
+
+
+def _off_centre_rows(conv, y=None, ratios=OFF_CENTRE, x=None, candidates=None):
+    """in place, for a BatchNorm behind the map `conv` (nn.Conv2d / nn.Linear; its input is x, its output with the parameters as they are is
+    y, channels along dim 1).  With a bias: bias[c] = ratios[c] * std(y channel c) in float64, the input untouched.  Without one: returns a
+    copy of x with the constants of _off_centre_pair added to two input channels; the other output channels move with them.  The float32
+    result is measured through the map in float64."""
+    fwd = _map_fwd(conv)
+    if conv.bias is not None:
+        y = fwd(x.double()) if y is None else y.double()
+        with torch.no_grad():
+            for c in range(2):
+                conv.bias[c] = ratios[c] * float(y.transpose(0, 1)[c].std(unbiased=False))
+        if x is not None:
+            for c in range(2):
+                _ratio_ok(_map_fwd(conv)(x.double()).transpose(0, 1)[c], ratios[c], "off-centre map output channel %d" % c)
+        return x
+    k0, d0, k1, d1 = _off_centre_pair(conv, x, ratios, candidates)
+    x = x.clone()
+    x[:, k0] = (x[:, k0].double() + d0).float()
+    x[:, k1] = (x[:, k1].double() + d1).float()
+    for c in range(2):
+        _ratio_ok(fwd(x.double()).transpose(0, 1)[c], ratios[c], "off-centre map output channel %d" % c)
+    return x
+
+
+def _off_centre_running(bn, ratios=OFF_CENTRE, y=None):
+    """in place, for the eval passes: running_mean[c] = ratios[c] * sqrt(running_var[c]) of channels 0 and 1.  y: the tensor the BatchNorm
+    normalises (channels along dim 1) - running_var[c] is then that channel's variance first, so that the running statistics describe the
+    off-centre channel they meet (as after training on it) and `v - mean` cancels as it does in a trained model."""
+    with torch.no_grad():
+        for c, ratio in enumerate(ratios):
+            if ratio:
+                if y is not None:
+                    bn.running_var[c] = float(y.transpose(0, 1)[c].double().var(unbiased=False))
+                bn.running_mean[c] = ratio * float(bn.running_var[c].double().sqrt())
+                assert abs(float(bn.running_mean[c]) / float(bn.running_var[c].double().sqrt()) - ratio) <= 0.1 * abs(ratio)
+
+
+def _max_err(a, b):
+    a, b = a.detach().cpu().double(), b.detach().cpu().double()
+    assert a.shape == b.shape, (a.shape, b.shape)
+    return float((a - b).abs().max()) if a.numel() else 0.0
+
+
+STOCK_FACTOR = 4.0
+# a tensor of ONE element (the gradient of a shared PReLU slope) is one draw of the kernel's error against one draw of stock's: two
+# zero-mean errors of equal size are more than 4 x apart in 2 / pi * atan(1 / 4) = 16 % of all draws, more than 32 x apart in 2 %
+# (measured: context_heads 5.3 x, gate_head 16 x with float64 sums throughout); the max over a tensor of many elements is no such draw
+STOCK_FACTOR_ONE = 32.0
+STOCK_MISSES = None        # a list: a measuring script collects every miss of every case here, and the case goes on instead of stopping
+
+
+def assert_within_stock(what, kernel, stock, family, ratios=OFF_CENTRE, factors=None):
+    """The bound of the off-centre cases.  stock(dtype, ratios) -> {name: tensor}: the stock PyTorch chain of the case in `dtype` on the
+    float32 values of the case built with `ratios`; kernel() -> the same names from the HIP run of the case with `ratios`; family(name,
+    refs) -> the absolute bound the family's own check holds that quantity to, from the float64 results `refs` of the case (None: the
+    family itself holds the quantity to stock float32 alone).
+    For every name: e_stock = max(stock float32 against float64 on the case, the same with ratios 0); the kernel must be within
+    min(family bound, STOCK_FACTOR * e_stock) of float64 (STOCK_FACTOR_ONE for a tensor of one element), and equal where e_stock is 0.  A non-zero e_stock counts as at least half an ulp
+    of the largest float32 element of the tensor: neither run can be held below the rounding of its own float32 result, a stock error
+    under it is the luck of a few numbers (running_var of three channels), and a correctly rounded kernel would miss 4 x that.
+    factors: {name: factor} for the quantities whose recorded cause (tests/MUTANTS.md) puts them above STOCK_FACTOR.
+    Before the kernel runs: stock float32 itself is inside the family's bound on the case, or the case would test float32."""
+    from helpers import WORST
+    r64, r32 = stock(torch.float64, ratios), stock(torch.float32, ratios)
+    z64, z32 = stock(torch.float64, OFF_CENTRE_NONE), stock(torch.float32, OFF_CENTRE_NONE)
+    e_stock, fam = {}, {}
+    for name, ref in r64.items():
+        e_off = _max_err(r32[name], ref)
+        e_stock[name] = max(e_off, _max_err(z32[name], z64[name]))
+        if e_stock[name] > 0.0:
+            e_stock[name] = max(e_stock[name], 2.0 ** -24 * float(ref.detach().abs().max()))
+        fam[name] = family(name, r64)
+        if fam[name] is None:
+            fam[name] = float("inf")
+        assert e_off <= fam[name], "%s %s: precondition: stock float32 is %.3e off float64, the family's bound is %.3e (ratios %s)" % (what, name, e_off, fam[name], ratios)
+    got = kernel()
+    assert set(got) == set(r64), (sorted(got), sorted(r64))
+    misses = []
+    for name, ref in r64.items():
+        err = _max_err(got[name], ref)
+        if e_stock[name] == 0.0:
+            if err != 0.0:
+                misses.append((float("inf"), "%s %s: stock float32 is exact, the kernel is %.3e off" % (what, name, err)))
+            continue
+        factor = STOCK_FACTOR if ref.numel() > 1 else STOCK_FACTOR_ONE
+        bound = min(fam[name], max(factor, (factors or {}).get(name, 0.0)) * e_stock[name])
+        print("%s %s: kernel %.3e, stock float32 %.3e (x %.2f), family bound %.3e" % (what, name, err, e_stock[name], err / e_stock[name], fam[name]))
+        if err > bound:
+            misses.append((err / bound, "%s %s: max err %.3e > bound %.3e (%.1f x stock float32)" % (what, name, err, bound, err / e_stock[name])))
+        elif err / bound > WORST[0]:
+            WORST[:] = [err / bound, "%s %s" % (what, name), err, bound]
+    if STOCK_MISSES is not None:
+        STOCK_MISSES.extend(m for _, m in misses)
+    elif misses:
+        raise AssertionError(max(misses)[1] + ("" if len(misses) == 1 else " and %d more" % (len(misses) - 1)))
+
+
 class BranchLog:
     """PReLU of a CPU reference on the branches the HIP run took, for tensors of millions of elements.
 

@@ -302,6 +302,122 @@ def check_flat_adam(device):
     assert torch.equal(xd.cpu(), x * s), "cg_scale"
 
 
+ADAM_CLIPS, ADAM_SCALES = (0.0, 0.5), (1.0, 0.5)
+ADAM_SPECIALS = (float("nan"), float("inf"), float("-inf"))
+
+
+def _adam_clip_places(n_weight, n_bias):
+    """(tensor, flat index) of the first element of the flat buffer, of one past the first grid stride of cg_adam_flat_kernel and of the
+    last element; the weight of G.ADAM_LINEAR alone is longer than one grid (G.assert_properties)"""
+    grid = G.glue_geometry()["flat_grid"]
+    assert n_weight > grid + 101
+    return ((0, 0), (0, grid + 101), (1, n_bias - 1))
+
+
+def _adam_clip_run(device, clip, gscale, grads, special):
+    """two steps of FlatAdam (lr 1e-2, weight decay 0.5) on G.ADAM_LINEAR; grads[step][tensor]: float32 CPU gradients; special: {(tensor,
+    flat index): value} written into the gradients of the first step.  -> after every step, per tensor, (p, exp_avg, exp_avg_sq) on the CPU"""
+    from cistgcn_amd.runtime import FlatAdam
+    torch.manual_seed(5)
+    dev = nn.Linear(*G.ADAM_LINEAR).to(device)
+    opt = FlatAdam(dev, lr=1e-2, weight_decay=0.5, clip_value=clip)
+    out = []
+    for step in range(2):
+        for t, pd in enumerate(dev.parameters()):
+            gr = grads[step][t].clone()
+            if step == 0:
+                for (tt, i), v in special.items():
+                    if tt == t:
+                        gr.view(-1)[i] = v
+            pd.grad = gr.view(pd.shape).to(device)
+        opt.step(grad_scale=gscale)
+        state = []
+        for pd, off in zip(opt.params, opt.grads.offsets[:-1]):
+            n, off = pd.numel(), int(off)
+            state.append(tuple(t.detach().cpu().reshape(-1).clone() for t in (pd, opt.exp_avg[off:off + n], opt.exp_avg_sq[off:off + n])))
+        out.append(state)
+    return out
+
+
+def _adam_clip_ref(clip, gscale, grads, special):
+    """the same two steps by torch.optim.Adam in float64: the gradient scaled, then torch.nn.utils.clip_grad_value_, then the step"""
+    torch.manual_seed(5)
+    ref = nn.Linear(*G.ADAM_LINEAR).double()
+    opt = torch.optim.Adam(ref.parameters(), lr=1e-2, weight_decay=0.5)
+    out = []
+    for step in range(2):
+        for t, pr in enumerate(ref.parameters()):
+            gr = grads[step][t].clone()
+            if step == 0:
+                for (tt, i), v in special.items():
+                    if tt == t:
+                        gr.view(-1)[i] = v
+            pr.grad = gr.view(pr.shape).double() * gscale
+        if clip > 0:
+            torch.nn.utils.clip_grad_value_(ref.parameters(), clip)
+        opt.step()
+        out.append([tuple(t.detach().reshape(-1).clone() for t in (pr, opt.state[pr]["exp_avg"], opt.state[pr]["exp_avg_sq"])) for pr in ref.parameters()])
+    return out
+
+
+def check_flat_adam_clip(device):
+    """cg_adam_flat with clip_grad_value_ and the gradient pre-scale on values random gradients never hold: gradients exactly at +-clip, one
+    float32 step beyond, and at +-clip / grad_scale (scaled first, clipped second); one NaN, one +Inf and one -Inf in the gradient of the
+    first of two steps, at the first element of the flat buffer, the last one and one past the first grid stride, every value at every
+    place in turn.  torch.nn.utils.clip_grad_value_ is clamp_: a NaN stays a NaN and reaches the parameter, +-Inf is clipped.  Against
+    torch.optim.Adam in float64 on the same values: the same NaN, +Inf and -Inf positions in p, exp_avg and exp_avg_sq, every finite
+    element at the rel = 1e-5 of check_flat_adam (1 - beta2 in float32 is 4.7e-5 off 0.001, so exp_avg_sq has no tighter bound of its own),
+    and every element that had no special gradient bit for bit what a run
+    without the special values gives."""
+    n_in, n_out = G.ADAM_LINEAR
+    sizes = (n_in * n_out, n_out)
+    places = _adam_clip_places(*sizes)
+    g = _gen(421)
+    grads = [[torch.randn(n, generator=g) for n in sizes] for _ in range(2)]
+    one = torch.tensor(1.0)
+    for gscale in ADAM_SCALES:           # the boundary values of every (clip, scale) pair stand in every run; 0.5 is the only clip > 0
+        c = torch.tensor(0.5)
+        vals = [c, torch.nextafter(c, one), c / gscale, torch.nextafter(c / gscale, 2 * one / gscale)]
+        vals = [float(s * v) for v in vals for s in (1.0, -1.0)]
+        base = 16 if gscale == 1.0 else 48
+        for step in range(2):
+            for t, n in enumerate(sizes):
+                for k, v in enumerate(vals):
+                    grads[step][t][base + k] = v if step == 0 else -v
+                    grads[step][t][n - 8 - base - k] = v
+    for clip in ADAM_CLIPS:
+        for gscale in ADAM_SCALES:
+            plain = _adam_clip_run(device, clip, gscale, grads, {})
+            for turn in range(3):
+                special = {places[k]: ADAM_SPECIALS[(k + turn) % 3] for k in range(3)}
+                what = "adam clip=%g scale=%g turn %d" % (clip, gscale, turn)
+                got, ref = _adam_clip_run(device, clip, gscale, grads, special), _adam_clip_ref(clip, gscale, grads, special)
+                for step in range(2):
+                    for t in range(2):
+                        touched = torch.zeros(sizes[t], dtype=torch.bool)
+                        for (tt, i), v in special.items():
+                            if tt == t:
+                                touched[i] = True
+                        for name, a, r, b in zip(("p", "exp_avg", "exp_avg_sq"), got[step][t], ref[step][t], plain[step][t]):
+                            w = "%s step %d tensor %d %s" % (what, step, t, name)
+                            for kind, f in (("NaN", torch.isnan), ("+Inf", torch.isposinf), ("-Inf", torch.isneginf)):
+                                assert torch.equal(f(a), f(r)), "%s: %s at %s, the reference has it at %s" % (
+                                    w, kind, f(a).nonzero().flatten().tolist()[:8], f(r).nonzero().flatten().tolist()[:8])
+                            for (tt, i), v in special.items():
+                                if tt != t:
+                                    continue
+                                if v != v:
+                                    assert bool(torch.isnan(a[i])), "%s: a NaN gradient at %d gave %r" % (w, i, float(a[i]))
+                                elif clip > 0:
+                                    assert bool(torch.isfinite(a[i])), "%s: an infinite gradient at %d was not clipped: %r" % (w, i, float(a[i]))
+                            fin = torch.isfinite(r)
+                            zero = torch.zeros((), dtype=a.dtype)
+                            assert_close(torch.where(fin, a, zero), torch.where(fin, r, zero.double()), w, rel=1e-5)
+                            same = (a.view(torch.int32) == b.view(torch.int32)) | touched
+                            assert bool(same.all()), "%s: %d elements without a special gradient differ from the run without special values, first at %d" % (
+                                w, int((~same).sum()), int((~same).nonzero()[0]))
+
+
 def check_se_gate(device):
     g = _gen(43)
     for B, C, H in G.SE_GATE:
@@ -485,5 +601,5 @@ def check_eval_scatter(device):
     assert_close(frames, E.mpjpe_frames(ref.double(), tgt.double()), "per-frame MPJPE J32=%d" % J32, rel=1e-5)
 
 
-KERNEL_CHECKS = (check_mpjpe, check_flat_adam, check_se_gate, check_reduce_bc, check_cumsum, check_feature_lift, check_dstd_stats, check_fanout,
+KERNEL_CHECKS = (check_mpjpe, check_flat_adam, check_flat_adam_clip, check_se_gate, check_reduce_bc, check_cumsum, check_feature_lift, check_dstd_stats, check_fanout,
                  check_cat_split, check_zero, check_norm_act_alignment, check_eval_scatter)

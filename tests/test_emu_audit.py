@@ -1,13 +1,15 @@
 """The checks that came out of the seeded-error audit of the kernels (tools/mutants.py, tests/MUTANTS.md) on the CPU-only box, the kernel
 sources through the test-only HIP shim (tests/hipemu): plan branches of the generic contraction, equal maxima in the fused context heads,
-BatchNorm channels whose variance is comparable to eps in every family that applies one, and the dropout mask against its host
-restatement.  tests/test_gpu_audit.py runs the same checks on the MI355X."""
+BatchNorm channels whose variance is comparable to eps in every family that applies one, channels far off centre in every operator that
+sums BatchNorm statistics (tests/off_centre_checks.py), and the dropout mask against its host restatement.  tests/test_gpu_audit.py runs
+the same checks on the MI355X."""
 import pytest
 
 import audit_checks
 import checks
 import emu
 import helpers
+import off_centre_checks
 
 
 @pytest.fixture(scope="module", autouse=True)
@@ -34,6 +36,12 @@ def test_context_heads_equal_maxima():
 @pytest.mark.parametrize("family", [name for name, _ in audit_checks.LOW_VARIANCE])
 def test_low_variance_channels(family):
     _report("low_variance " + family, audit_checks.check_low_variance, family)
+
+
+@pytest.mark.parametrize("name", [name for name, _ in off_centre_checks.OFF_CENTRE_CASES])
+def test_off_centre_channels(name):
+    """channels at |mean| / std = 30 and 300 in every operator that sums BatchNorm statistics: within 4 x stock float32 of float64"""
+    _report("off_centre " + name, off_centre_checks.check_off_centre, name)
 
 
 def test_stgcn_rows_wider_than_a_wave():

@@ -1,5 +1,6 @@
 """The checks of tests/test_emu_audit.py on the MI355X (real libcistgcn_hip.so): plan branches of the generic contraction, equal maxima in
-the fused context heads, BatchNorm channels whose variance is comparable to eps, the dropout mask against its host restatement.  Run with
+the fused context heads, BatchNorm channels whose variance is comparable to eps or which lie far off centre, the dropout mask against its
+host restatement.  Run with
 `-m gpu`; every test prints the comparison that came closest to its bound."""
 import pytest
 import torch
@@ -7,6 +8,7 @@ import torch
 import audit_checks
 import checks
 import helpers
+import off_centre_checks
 
 pytestmark = pytest.mark.gpu
 
@@ -39,6 +41,12 @@ def test_context_heads_equal_maxima():
 @pytest.mark.parametrize("family", [name for name, _ in audit_checks.LOW_VARIANCE])
 def test_low_variance_channels(family):
     _report("low_variance " + family, audit_checks.check_low_variance, family)
+
+
+@pytest.mark.parametrize("name", [name for name, _ in off_centre_checks.OFF_CENTRE_CASES])
+def test_off_centre_channels(name):
+    """channels at |mean| / std = 30 and 300 in every operator that sums BatchNorm statistics: within 4 x stock float32 of float64"""
+    _report("off_centre " + name, off_centre_checks.check_off_centre, name)
 
 
 def test_stgcn_rows_wider_than_a_wave():

@@ -99,7 +99,14 @@ EDGES, TIES, DROPOUT = "audit_checks.check_contract_edges", "audit_checks.check_
 LOWVAR = [("audit_checks.check_low_variance", (family,)) for family in (
     "norm_act", "norm_act_many", "dstd_tail", "map2adj_tail", "block_input", "gate_head", "block_mid", "tower_maps", "tower_collapse", "context_heads")]
 ADAM = ["checks.check_flat_adam", "glue_checks.check_flat_adam"]
+ADAM_CLIP = "glue_checks.check_flat_adam_clip"
+
+
 FPN = ("checks.check_dilated_convs", (), {"shapes": ((3, 6, 5, 4, 6), (2, 5, 4, 10, 7))})
+
+def off_centre(name):
+    return ("off_centre_checks.check_off_centre", (name,))
+
 
 ROWS = [
     # ---- the ten trials of the audit (one edit each: the two-place edits of the issue are two rows) ----
@@ -116,6 +123,24 @@ ROWS = [
     dict(id="adam-decoupled-decay", file="optim.hip", old="const float pi = p[i];\n    gi += wd * pi;", new="const float pi = p[i] * (1.f - lr * wd);", checks=ADAM),
     dict(id="adam-eps-inside-sqrt", file="optim.hip", old="sqrtf(vi) / bc2_sqrt + eps;", new="sqrtf(vi + eps) / bc2_sqrt;", checks=ADAM),
     dict(id="adam-second-moment-raw-grad", file="optim.hip", old="(1.f - b2) * gi * gi;", new="(1.f - b2) * (g[i] * gscale) * (g[i] * gscale);", checks=ADAM),
+    dict(id="adam-clip-swallows-nan", file="optim.hip", old="gi = gi < -clip ? -clip : (gi > clip ? clip : gi);", new="gi = fminf(fmaxf(gi, -clip), clip);", checks=ADAM + [ADAM_CLIP]),
+    dict(id="adam-clip-before-scale", file="optim.hip", old="float gi = g[i] * gscale;\n    if (clip > 0.f) gi = gi < -clip ? -clip : (gi > clip ? clip : gi);",
+         new="float gi = g[i];\n    if (clip > 0.f) gi = gi < -clip ? -clip : (gi > clip ? clip : gi);\n    gi *= gscale;", checks=ADAM + [ADAM_CLIP]),
+    # ---- a float64-per-element BatchNorm sum demoted to float32 squares or a float32 quad: the family's own check first (it must pass), then its off-centre case ----
+    dict(id="rows-stats-f32-quad", file="rowops.hip",
+         old="s += ((double)v[0] + (double)v[1]) + ((double)v[2] + (double)v[3]);\n      q += ((double)v[0] * v[0] + (double)v[1] * v[1]) + ((double)v[2] * v[2] + (double)v[3] * v[3]);",
+         new="s += (double)((v[0] + v[1]) + (v[2] + v[3]));\n      q += (double)((v[0] * v[0] + v[1] * v[1]) + (v[2] * v[2] + v[3] * v[3]));",
+         checks=["checks.check_norm_act", off_centre("norm_act")]),
+    dict(id="contract-stats-f32-square", file="contract.hip", count=2, old="s += (double)v; q += (double)v * (double)v;", new="s += (double)v; q += (double)(v * v);",
+         checks=["checks.check_contract", off_centre("contract_stats")]),
+    dict(id="contract-stream-stats-f32-quad", file="contract.hip", old="double s2 = ok ? ((double)v.x * v.x + (double)v.y * v.y) + ((double)v.z * v.z + (double)v.w * v.w) : 0.0;",
+         new="double s2 = ok ? (double)((v.x * v.x + v.y * v.y) + (v.z * v.z + v.w * v.w)) : 0.0;", checks=["checks.check_contract_stream", off_centre("contract_stats")]),
+    dict(id="stgcn-tile-stats-f32-square", file="stgcn_domain.hip", old="s += (double)v; sq += (double)v * (double)v;", new="s += (double)v; sq += (double)(v * v);",
+         checks=["mutants_table.stgcn_tiles", off_centre("stgcn_stats_tile")]),
+    dict(id="dstd-f1-stats-f32-square", file="dstd_tail.hip", old="const double z = (double)(wv * xv[j]);\n          s += z; q += z * z; ",
+         new="const float zf = wv * xv[j];\n          const double z = (double)zf;\n          s += z; q += (double)(zf * zf); ", checks=["checks.check_dstd_tail", off_centre("dstd_tail")]),
+    dict(id="collapse-rows-stats-f32-square", file="collapse_rows.hip", old="{ const double y = (double)sY[o * 33 + v]; s1 += y; s2 += y * y; }",
+         new="{ const float y = sY[o * 33 + v]; s1 += (double)y; s2 += (double)(y * y); }", checks=["checks.check_collapse_rows", off_centre("collapse_rows_stats")]),
     # ---- two rows for every other source ----
     dict(id="attack-momentum-factor-dropped", file="attack.hip", old="const float m = a.mu * a.g[base + i];", new="const float m = a.g[base + i];", checks=["mutants_table.attack_steps"]),
     dict(id="attack-sample-grad-N-dropped", file="attack.hip", old="w[blockIdx.y] / ((float)N * n)", new="w[blockIdx.y] / n", checks=["mutants_table.attack_mpjpe"]),
