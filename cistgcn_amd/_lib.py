@@ -44,6 +44,9 @@ LIMITS = {
     # cg_forward_kinematics: joints of a tree (and of `select`), the cap of its grid, the threads of a workgroup (64 per one or two frames
     # in flight) and its two conventions
     "CG_FK_MAX_JOINTS": 64, "CG_FK_MAX_BLOCKS": 1024, "CG_FK_THREADS": 256, "CG_FK_EXPMAP_CHAIN": 0, "CG_FK_SMPL": 1,
+    # cg_draw_augmentation: the first salt of its generator (dropout site ids stay below it), its two table layouts, the threads of a
+    # workgroup and the cap of its grid
+    "CG_DRAW_SALT": 0x800000, "CG_DRAW_TABLE24": 0, "CG_DRAW_STEPS4": 1, "CG_DRAW_THREADS": 256, "CG_DRAW_MAX_BLOCKS": 4096,
 }
 STAT_REPLICAS = LIMITS["CG_STAT_REPLICAS"]
 ALPHA_SLOTS = LIMITS["CG_ALPHA_SLOTS"]
@@ -247,6 +250,10 @@ class GatherWindows(ctypes.Structure):
                 ("frames", c_void_p), ("starts", c_void_p), ("items", c_void_p), ("select", c_void_p), ("raw", c_void_p)]
 
 
+class DrawStep(ctypes.Structure):
+    _fields_ = [("kind", c_int), ("prob_threshold", c_float), ("lo", c_float * 3), ("hi", c_float * 3)]
+
+
 # A class mirrors the header's struct "Cg" + its own name, except these two.
 C_STRUCT_NAMES = {"EvalMetricsArgs": "CgEvalMetrics", "AttackMetricsArgs": "CgAttackMetrics"}
 
@@ -352,6 +359,9 @@ _SIGNATURES = {
     "cg_motion_loss_bwd": [POINTER(MotionLoss), P],
     "cg_forward_kinematics": [POINTER(ForwardKinematics), P],
     "cg_gather_windows": [POINTER(GatherWindows), P],
+    "cg_gather_windows_at": [POINTER(GatherWindows), P, P, P],
+    "cg_cursor_advance": [P, c_int, P],
+    "cg_draw_augmentation": [POINTER(DrawStep), c_int, P, c_int, c_int, c_int, c_int, P, P, P],
     "cg_adam_flat": [P, P, P, P, LL, c_float, c_float, c_float, c_float, c_float, c_float, c_float, LL, P],
 }
 EXPORTS = tuple(sorted(_SIGNATURES))

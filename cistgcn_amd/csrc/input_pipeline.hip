@@ -6,6 +6,7 @@
 // The random draws are made on the host in the reference's order (environment/input_pipeline.py) and arrive as one
 // parameter row per sequence; everything that depends on the data (centroids, per-axis extent) is computed here.
 #include "cg_common.h"
+#include "cg_rotvec.h"
 
 #define CG_AUG_NPAR 24      // flip x,y,z | rot_on | R[3][3] (row vector times matrix) | scale x,y,z | translation rate x,y,z | noise | invert | pad
 
@@ -174,28 +175,7 @@ __device__ __forceinline__ float cg_perturb_weight(int t, int s0, int s1, int co
   return n > 1 ? (float)(t - s0) / (float)(n - 1) : 0.f;
 }
 
-// Rotation matrix of a rotation vector in degrees (scipy's Rotation.from_rotvec(., degrees=True).as_matrix(), :69): Rodrigues' formula
-// in f64, operation by operation what environment/input_pipeline.py::_rotvec_matrix does on the host for cg_augment_sequences (no
-// contraction into FMAs), rounded to f32 at the end; row-major, used as p' = p R.
-__device__ __forceinline__ void cg_rotvec_matrix(float dx, float dy, float dz, float* R) {
-#pragma clang fp contract(off)
-  const double rad = 3.14159265358979323846 / 180.0;
-  const double v[3] = {(double)dx * rad, (double)dy * rad, (double)dz * rad};
-  const double th = sqrt(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]);
-  if (!(th > 0.0)) {
-    for (int i = 0; i < 9; ++i) R[i] = (i % 4 == 0) ? 1.f : 0.f;
-    return;
-  }
-  const double k[3] = {v[0] / th, v[1] / th, v[2] / th};
-  const double K[3][3] = {{0.0, -k[2], k[1]}, {k[2], 0.0, -k[0]}, {-k[1], k[0], 0.0}};
-  const double sn = sin(th), c1 = 1.0 - cos(th);
-  for (int i = 0; i < 3; ++i)
-    for (int j = 0; j < 3; ++j) {
-      double kk = 0.0;
-      for (int m = 0; m < 3; ++m) kk += K[i][m] * K[m][j];
-      R[3 * i + j] = (float)(((i == j ? 1.0 : 0.0) + sn * K[i][j]) + c1 * kk);
-    }
-}
+// (rotation matrix of a rotation vector in degrees: cg_rotvec_matrix, cg_rotvec.h)
 
 __global__ void cg_perturb_sequences_kernel(const float* __restrict__ raw, const CgPerturbSteps steps, const float* __restrict__ params,
                                             const float* __restrict__ noise_tab, const int* __restrict__ perm, float* __restrict__ sample,

@@ -9,7 +9,9 @@
 //                              the levels and the grid-stride loop over the frame groups have workgroup-uniform trip counts, so every
 //                              barrier is reached by all threads.  No dynamic register indexing (nothing goes to scratch), no atomics.
 //   cg_gather_windows_kernel   one workgroup per window: copy, joint selection, normalisation; a window whose first frame is upside
-//                              down gets its y mirrored about the window's own mean (f64, fixed order).
+//                              down gets its y mirrored about the window's own mean (f64, fixed order).  cg_gather_windows_at_kernel
+//                              is the same with the window ids read at a device-resident cursor into a permutation, which
+//                              cg_cursor_advance moves: a captured step walks an epoch without the host naming a batch.
 // The composition runs in f64 on the fp32 inputs and is rounded once per coordinate: the chains are up to ~10 joints deep in the loaders'
 // trees (63 at the limit) and fp32 products would carry the rounding of every level (the reference's own fp32 output is 1.5e-4 .. 5e-4
 // off at coordinates of 1100 .. 2600, recorded per case in tests/golden/aug_kinematics.npz).
@@ -176,12 +178,13 @@ __device__ __forceinline__ float cg_gather_norm(float v, bool on, float mean, fl
   return on ? (v - mean) / std : v;
 }
 
-__global__ __launch_bounds__(CG_GATHER_THREADS) void cg_gather_windows_kernel(CgGatherWindows a) {
+// window `item` (clamped into [0, W)) -> raw[b]; called by every thread of the workgroup (barriers inside)
+__device__ __forceinline__ void cg_gather_window(const CgGatherWindows& a, int b, int item) {
   __shared__ double red[16];
   __shared__ double centre;
-  const int tid = threadIdx.x, b = blockIdx.x;
+  const int tid = threadIdx.x;
   const int L = a.L, J = a.J, Js = a.J_src;
-  const int w = min(max(a.items[b], 0), a.W - 1);
+  const int w = min(max(item, 0), a.W - 1);
   const long long s = min(max((long long)a.starts[w], 0LL), a.F - L);          // F >= L (launcher)
   const float* src = a.frames + s * Js * 3;
   float* dst = a.raw + (long long)b * L * J * 3;
@@ -215,15 +218,54 @@ __global__ __launch_bounds__(CG_GATHER_THREADS) void cg_gather_windows_kernel(Cg
   }
 }
 
-// include/cistgcn_hip.h : cg_gather_windows
-extern "C" int cg_gather_windows(const CgGatherWindows* a, void* stream_) {
-  if (!a || !a->frames || !a->starts || !a->items || !a->raw) return CG_EARG;
+__global__ __launch_bounds__(CG_GATHER_THREADS) void cg_gather_windows_kernel(CgGatherWindows a) {
+  cg_gather_window(a, blockIdx.x, a.items[blockIdx.x]);
+}
+
+// the window ids at a device-resident cursor: order[min(*cursor + b, W - 1)] - a cursor past W - B repeats the last entry of `order`
+__global__ __launch_bounds__(CG_GATHER_THREADS) void cg_gather_windows_at_kernel(CgGatherWindows a, const int32_t* __restrict__ order,
+                                                                                 const int32_t* __restrict__ cursor) {
+  const long long at = (long long)max(*cursor, 0) + blockIdx.x;
+  cg_gather_window(a, blockIdx.x, order[min(at, (long long)a.W - 1)]);
+}
+
+// the checks cg_gather_windows and cg_gather_windows_at share (everything but the source of the window ids)
+static int cg_gather_check(const CgGatherWindows* a) {
+  if (!a || !a->frames || !a->starts || !a->raw) return CG_EARG;
   if (a->B < 1 || a->L < 1 || a->J < 1 || a->J_src < 1 || a->W < 1 || a->F < a->L || a->std == 0.f) return CG_ESHAPE;
   if ((long long)a->L * a->J * 3 > 0x7fffffffLL) return CG_ESHAPE;
   if (!a->select && a->J != a->J_src) return CG_ESHAPE;
   const bool off = a->up_hi == -1 && a->up_lo == -1;
   const bool on = a->up_hi >= 0 && a->up_hi < a->J && a->up_lo >= 0 && a->up_lo < a->J;
   if (!off && !on) return CG_ESHAPE;
+  return CG_OK;
+}
+
+// include/cistgcn_hip.h : cg_gather_windows
+extern "C" int cg_gather_windows(const CgGatherWindows* a, void* stream_) {
+  if (a && !a->items) return CG_EARG;
+  const int bad = cg_gather_check(a);
+  if (bad) return bad;
   hipLaunchKernelGGL(cg_gather_windows_kernel, dim3((unsigned)a->B), dim3(CG_GATHER_THREADS), 0, (hipStream_t)stream_, *a);
+  return cg_launch_status();
+}
+
+// include/cistgcn_hip.h : cg_gather_windows_at
+extern "C" int cg_gather_windows_at(const CgGatherWindows* a, const int32_t* order, const int32_t* cursor, void* stream_) {
+  if (!order || !cursor) return CG_EARG;
+  const int bad = cg_gather_check(a);
+  if (bad) return bad;
+  hipLaunchKernelGGL(cg_gather_windows_at_kernel, dim3((unsigned)a->B), dim3(CG_GATHER_THREADS), 0, (hipStream_t)stream_, *a, order, cursor);
+  return cg_launch_status();
+}
+
+// include/cistgcn_hip.h : cg_cursor_advance
+__global__ void cg_cursor_advance_kernel(int32_t* cursor, int by) {
+  if (threadIdx.x == 0 && blockIdx.x == 0) *cursor = *cursor + by;
+}
+
+extern "C" int cg_cursor_advance(int32_t* cursor, int by, void* stream_) {
+  if (!cursor) return CG_EARG;
+  hipLaunchKernelGGL(cg_cursor_advance_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream_, cursor, by);
   return cg_launch_status();
 }

@@ -7,4 +7,4 @@ from .evaluation import capture_interpretation, mpjpe_ms_table, save_interpretat
 from .evaluation import EvalMetrics  # noqa: F401
 from .losses import TrainingLoss, frame_weights, get_loss  # noqa: F401
 from .input_pipeline import DeviceAugmentation, DevicePrefetcher, RobustnessTest  # noqa: F401
-from .datasets import MotionBank, amass_bank, find_indices_256, h36m_bank  # noqa: F401
+from .datasets import BankFeed, MotionBank, amass_bank, find_indices_256, h36m_bank  # noqa: F401

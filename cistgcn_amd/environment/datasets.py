@@ -131,6 +131,56 @@ class MotionBank:
                 return
             yield {"raw": self.windows(item), "item": item}
 
+    def feed(self, batch_size, shuffle=True, generator=None):
+        """A `BankFeed`: the epoch's permutation and a cursor into it in static device buffers, for a step that gathers its own batch
+        (`runtime.BankStep`)."""
+        return BankFeed(self, batch_size, shuffle=shuffle, generator=generator)
+
+
+class BankFeed:
+    """The batches of a `MotionBank` epoch named on the device: `order` (W,) int32, the epoch's permutation of the window ids, and
+    `cursor` (1,) int32, the position of the next batch in it.  Both are allocated once; `ops.gather_windows_at` reads them and
+    `ops.cursor_advance` moves the cursor, so a captured step takes batch after batch without the host naming one.
+
+    `len(feed)` = W // batch_size batches per epoch: the partial last batch is DROPPED (a captured step has one batch size).
+    `start_epoch()` draws a new permutation into the same `order` buffer (`torch.randperm(device=...)`; `arange` without `shuffle`)
+    and zeroes the cursor - no synchronisation, no reallocation.  `taken` counts, on the host, the batches taken since: the step
+    that moves the cursor (`ops.cursor_advance`, or the replay of a graph that holds it) adds one."""
+
+    def __init__(self, bank, batch_size, shuffle=True, generator=None):
+        self.bank, self.batch_size, self.shuffle, self.generator = bank, int(batch_size), bool(shuffle), generator
+        W = len(bank)
+        if self.batch_size < 1 or self.batch_size > W:
+            raise ValueError("BankFeed: batch_size %d for a bank of %d windows" % (self.batch_size, W))
+        self.order = torch.empty(W, dtype=torch.int32, device=bank.device)
+        self.cursor = torch.zeros(1, dtype=torch.int32, device=bank.device)
+        self.taken = 0
+        self.start_epoch()
+
+    def __len__(self):
+        return len(self.bank) // self.batch_size
+
+    def start_epoch(self):
+        W = len(self.bank)
+        if self.shuffle:
+            self.order.copy_(torch.randperm(W, dtype=torch.int32, device=self.bank.device, generator=self.generator))
+        else:
+            self.order.copy_(torch.arange(W, dtype=torch.int32, device=self.bank.device))
+        self.cursor.zero_()
+        self.taken = 0
+        return self
+
+    def items(self):
+        """the window ids of the batch the next step takes: a view of `order` (for `MotionBank.labels_of`)"""
+        at = self.taken * self.batch_size
+        return self.order[at:at + self.batch_size]
+
+    def gather(self, out=None):
+        """raw (batch_size, seq_len, J, 3) of the batch at the cursor (`ops.gather_windows_at`); the cursor is not moved"""
+        b = self.bank
+        return ops.gather_windows_at(b.frames, b.starts_dev, self.order, self.cursor, self.batch_size, b.seq_len, select=b.select, mean=b.mean,
+                                     std=b.std, up_joints=b.up_joints, out=out)
+
 
 def find_indices_256(frame_num1, frame_num2, seq_len, input_n=10):
     """First frames of the 2 x 128 evaluation windows of the `original_test` split (data_utils.py:77-106): RandomState(1234567890),

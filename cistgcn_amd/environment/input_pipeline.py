@@ -54,6 +54,54 @@ def _rotvec_matrix(deg):
     return np.eye(3) + np.sin(th) * K + (1.0 - np.cos(th)) * (K @ K)
 
 
+def _item_tensors(raw, input_n, keep_processed, out):
+    """the five output tensors of a batch (new ones, or the dictionary `out` of an earlier call after a shape check) and `processed`"""
+    B, L, J, _ = raw.shape
+    dev, f32, To = raw.device, torch.float32, L - input_n
+    shapes = {"sample": (B, input_n, J, 3), "target": (B, To, J, 3), "target_vel": (B, To, J, 3), "target_gvel": (B, To, J, 1),
+              "sample_vel": (B, input_n, J, 3)}
+    if out is None:
+        out = {k: torch.empty(shp, dtype=f32, device=dev) for k, shp in shapes.items()}
+    else:
+        for k, shp in shapes.items():
+            t = out.get(k)
+            if t is None or tuple(t.shape) != shp or t.dtype != f32 or t.device != dev or not t.is_contiguous():
+                raise ValueError("out[%r] must be a contiguous float32 %s tensor on %s" % (k, shp, dev))
+        out = {k: out[k] for k in shapes}
+    proc = torch.empty(B, L, J, 3, dtype=f32, device=dev) if keep_processed else None
+    return out, proc
+
+
+def _draw_device(steps, layout, batch, joints, device, stream, out):
+    """the step list as descriptors of `ops.draw_augmentation`, one launch, the result in the form of the host `draw`"""
+    desc = []
+    for st in steps:
+        if st.kind == "flip":
+            lo, hi = [1.0 if a else 0.0 for a in st.ranges], (0.0, 0.0, 0.0)
+        elif st.kind == "noise":
+            lo, hi = (float(st.ranges), 0.0, 0.0), (0.0, 0.0, 0.0)
+        elif st.kind == "invert":
+            lo = hi = (0.0, 0.0, 0.0)
+        else:
+            lo, hi = [r[0] for r in st.ranges], [r[1] for r in st.ranges]
+        desc.append((st.kind, st.prob_threshold, lo, hi))
+    n_noise = sum(st.kind == "noise" for st in steps)
+    if n_noise and joints is None:
+        raise ValueError("draw_device: RandomNoise draws one number per joint and axis: pass joints=")
+    tab = noise = None
+    if out is not None:
+        tab, noise = (out["params"], out["noise"]) if isinstance(out, dict) else (out, None)
+        if noise is not None and layout == "table24":
+            noise = noise.view(int(batch), 1, int(joints), 3)
+    if tab is None and noise is None:
+        tab, noise = ops.draw_augmentation(desc, batch, joints, layout, stream=stream, device=device)
+    else:
+        tab, noise = ops.draw_augmentation(desc, batch, joints, layout, stream=stream, out=tab, noise_out=noise)
+    if not n_noise:
+        return tab
+    return {"params": tab, "noise": noise.view(int(batch), int(joints), 3) if layout == "table24" else noise}
+
+
 class _Step:
     def __init__(self, kind, ranges, prob_threshold):
         self.kind, self.ranges, self.prob_threshold = kind, ranges, float(prob_threshold)
@@ -151,6 +199,24 @@ class DeviceAugmentation:
                 raise ValueError("augmentation order %s is not the reference's flip/rotation/scale/noise/translation/inversion order" % seen)
         return {"params": out, "noise": noise} if has_noise else out
 
+    def _check_order(self):
+        """what `draw` checks per sample, once per call for the device draws"""
+        seen = [st.kind for st in self.steps]
+        for k in seen:
+            if seen.count(k) > 1:
+                raise ValueError("augmentation '%s' configured twice (random_* and explicit): not supported on device" % k)
+        order = [k for k in ("flip", "rotation", "scale", "noise", "translation", "invert") if k in seen]
+        if seen != order:
+            raise ValueError("augmentation order %s is not the reference's flip/rotation/scale/noise/translation/inversion order" % seen)
+
+    def draw_device(self, batch, joints=None, device="cuda", stream=0, out=None):
+        """What `draw` returns, as device tensors drawn on the device from the seed word of `ops.seed_state` (one launch,
+        capturable; `ops.draw_augmentation`): a DIFFERENT random stream than `draw`, which reproduces the reference's `np.random`
+        order.  The seed is read, not advanced; `stream` (0 .. 65535) separates independent draws under one seed.  `out`: what an
+        earlier call returned, to be filled again (the static buffers of a captured step)."""
+        self._check_order()
+        return _draw_device(self.steps, "table24", batch, joints, device, stream, out)
+
     def _perm(self, J, device):
         """joint permutation the reference's sequential pair swaps compose to: output joint j shows joint perm[j]"""
         for st in self.steps:
@@ -161,13 +227,15 @@ class DeviceAugmentation:
                         raise IndexError("RandomPoseInvers: joint pair (%d, %d) out of range for %d joints (the reference indexes the "
                                          "same way and fails the same way)" % (x, y, J))
                     idx[x], idx[y] = idx[y], idx[x]
-                return torch.tensor(idx, dtype=torch.int32, device=device)
+                return ops._index_tensor(idx, device)          # uploaded once per permutation and device: the call stays capturable
         return None
 
-    def __call__(self, raw, input_n, params=None, keep_processed=False):
+    def __call__(self, raw, input_n, params=None, keep_processed=False, out=None, stream=0):
         """raw: (B, L, J, 3) float32 on the HIP device (un-augmented windows of input_n + output_n frames).  Returns the dict
         of `H36m_Motion3D.__getitem__` / `Amass_Motion3D.__getitem__` (the two are the same code) for the batch: sample, sample_vel,
-        target, target_vel, target_gvel (and processed on request; "original" is the caller's `raw`, "item" its indices)."""
+        target, target_vel, target_gvel (and processed on request; "original" is the caller's `raw`, "item" its indices).
+        params: what `draw` or `draw_device` returned; None: `draw` (host, the reference's stream); "device": `draw_device` with
+        `stream`.  out: a dictionary an earlier call returned, written again instead of new tensors."""
         ops._chk(raw, "raw")
         if raw.dim() != 4 or raw.shape[3] != 3:
             raise ValueError("expected windows of shape (B, L, J, 3), got %s" % (tuple(raw.shape),))
@@ -175,6 +243,10 @@ class DeviceAugmentation:
         B, L, J, _ = raw.shape
         if params is None:
             params = self.draw(B, joints=J)
+        elif isinstance(params, str):
+            if params != "device":
+                raise ValueError("params: a table, None (host draws) or \"device\", got %r" % params)
+            params = self.draw_device(B, joints=J, device=raw.device, stream=stream)
         noise = None
         if isinstance(params, dict):
             params, noise = params["params"], params["noise"]
@@ -187,12 +259,7 @@ class DeviceAugmentation:
             params = torch.from_numpy(np.ascontiguousarray(params, dtype=np.float32)).to(raw.device, non_blocking=True)
         if tuple(params.shape) != (B, NPAR):
             raise ValueError("expected a (%d, %d) parameter table" % (B, NPAR))
-        dev, f32 = raw.device, torch.float32
-        To = L - input_n
-        out = {"sample": torch.empty(B, input_n, J, 3, dtype=f32, device=dev), "target": torch.empty(B, To, J, 3, dtype=f32, device=dev),
-               "target_vel": torch.empty(B, To, J, 3, dtype=f32, device=dev), "target_gvel": torch.empty(B, To, J, 1, dtype=f32, device=dev),
-               "sample_vel": torch.empty(B, input_n, J, 3, dtype=f32, device=dev)}
-        proc = torch.empty(B, L, J, 3, dtype=f32, device=dev) if keep_processed else None
+        out, proc = _item_tensors(raw, int(input_n), keep_processed, out)
         _lib.call("cg_augment_sequences", ops._ptr(raw), ops._ptr(params), ops._ptr(out["sample"]), ops._ptr(out["target"]),
                   ops._ptr(out["target_vel"]), ops._ptr(out["target_gvel"]), ops._ptr(proc), ops._ptr(out["sample_vel"]), ops._ptr(noise), ops._ptr(perm),
                   B, L, J, int(input_n), ops._stream(raw))
@@ -321,6 +388,12 @@ class RobustnessTest:
 
     _perm = DeviceAugmentation._perm
 
+    def draw_device(self, batch, joints=None, device="cuda", stream=0, out=None):
+        """What `draw` returns, as device tensors drawn on the device (`DeviceAugmentation.draw_device`: another random stream than
+        `draw`; the seed is read, not advanced)."""
+        self._check_count()
+        return _draw_device(self.steps, "steps4", batch, joints, device, stream, out)
+
     def step_table(self, L):
         """(n_steps, 6) int32 [kind, s0, s1, continuous, keep, noise slot] for sequences of L frames; ValueError for a window that
         does not satisfy 0 <= s0 < s1 <= L"""
@@ -335,8 +408,9 @@ class RobustnessTest:
             slot += st.kind == "noise"
         return tab
 
-    def __call__(self, raw, input_n, params=None, keep_processed=False):
-        """raw: (B, L, J, 3) float32 on the HIP device.  Returns the dictionary `DeviceAugmentation.__call__` returns."""
+    def __call__(self, raw, input_n, params=None, keep_processed=False, out=None, stream=0):
+        """raw: (B, L, J, 3) float32 on the HIP device.  Returns the dictionary `DeviceAugmentation.__call__` returns; `params`, `out`
+        and `stream` as there."""
         ops._chk(raw, "raw")
         if not raw.is_cuda and not _lib._host_pointers_ok:
             raise ValueError("RobustnessTest runs on MI355X only: got a %s tensor (no CPU path exists)" % raw.device)
@@ -348,6 +422,10 @@ class RobustnessTest:
         n_steps, n_noise = len(self.steps), self.n_noise
         if params is None:
             params = self.draw(B, joints=J)
+        elif isinstance(params, str):
+            if params != "device":
+                raise ValueError("params: a table, None (host draws) or \"device\", got %r" % params)
+            params = self.draw_device(B, joints=J, device=raw.device, stream=stream)
         noise = None
         if isinstance(params, dict):
             params, noise = params["params"], params["noise"]
@@ -363,12 +441,7 @@ class RobustnessTest:
             params = torch.from_numpy(np.ascontiguousarray(params, dtype=np.float32)).to(raw.device, non_blocking=True)
         if tuple(params.shape) != (B, n_steps, 4):
             raise ValueError("expected a (%d, %d, 4) parameter table" % (B, n_steps))
-        dev, f32 = raw.device, torch.float32
-        To = L - input_n
-        out = {"sample": torch.empty(B, input_n, J, 3, dtype=f32, device=dev), "target": torch.empty(B, To, J, 3, dtype=f32, device=dev),
-               "target_vel": torch.empty(B, To, J, 3, dtype=f32, device=dev), "target_gvel": torch.empty(B, To, J, 1, dtype=f32, device=dev),
-               "sample_vel": torch.empty(B, input_n, J, 3, dtype=f32, device=dev)}
-        proc = torch.empty(B, L, J, 3, dtype=f32, device=dev) if keep_processed else None
+        out, proc = _item_tensors(raw, int(input_n), keep_processed, out)
         steps = (ctypes.c_int * max(1, tab.size))(*[int(v) for v in tab.reshape(-1)])
         _lib.call("cg_perturb_sequences", ops._ptr(raw), steps, ops._ptr(params) if n_steps else None, ops._ptr(noise) if n_noise else None,
                   ops._ptr(perm), ops._ptr(out["sample"]), ops._ptr(out["target"]), ops._ptr(out["target_vel"]), ops._ptr(out["target_gvel"]),

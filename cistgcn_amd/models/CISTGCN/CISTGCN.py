@@ -20,6 +20,9 @@ import torch.nn as nn
 from ... import ops
 from ..layers.SE import SELayer1d, SELayer2d
 
+# Dropout site ids and the salts of ops.draw_augmentation share the salt field of the seed hash: the ids stay below the first draw salt
+_DRAW_SALT = ops._lib.LIMITS["CG_DRAW_SALT"]
+
 
 class Stage(nn.Module):
     """Numbered parameter slots of one reference `nn.Sequential` (gaps = parameter-free steps)."""
@@ -379,6 +382,7 @@ class CISTGCN(nn.Module):
             drop = kw.pop("drop", False)
             if kw.get("salt") is None:
                 self._site += 1
+                assert self._site < _DRAW_SALT, "dropout site ids must stay below the salts of the augmentation draws"
                 kw["salt"] = self._site
                 if drop and self.drop_trace is not None:
                     self.drop_trace[kw.get("bn") if kw.get("bn") is not None else kw.get("prelu")] = self._site
@@ -509,6 +513,7 @@ class CISTGCN(nn.Module):
         def take(n):
             ids = tuple(range(self._site + 1, self._site + 1 + n))
             self._site += n
+            assert self._site < _DRAW_SALT, "dropout site ids must stay below the salts of the augmentation draws"
             return ids
         doms = (m.dsgn, m.tsgn)
         s = SimpleNamespace()

@@ -241,9 +241,16 @@ def begin_step(device, bump_seed=False):
         if pool is not None:
             pool.begin_step()
     if bump_seed:
-        s = seed_state(device)
-        _lib.call("cg_seed_bump", _ptr(s), _stream(s))
-        _seed_epochs[device] = _seed_epochs.get(device, 0) + 1
+        advance_seed(device)
+
+
+def advance_seed(device):
+    """Advance the device-resident seed word by one kernel (capturable) and count the change, as `begin_step(bump_seed=True)` does:
+    for a step that draws from the seed before its forward pass (`runtime.BankStep`)."""
+    device = _dev(device)
+    s = seed_state(device)
+    _lib.call("cg_seed_bump", _ptr(s), _stream(s))
+    _seed_epochs[device] = _seed_epochs.get(device, 0) + 1
 
 
 def _sums(dev, C):
@@ -1704,6 +1711,20 @@ def gather_windows(frames, starts, items, L, select=None, mean=0.0, std=1.0, up_
     bounds, a caller with host ids validates them first (`MotionBank.windows`).  select: host ints in [0, J_src) or None.
     up_joints = (hi, lo), joints in the selected numbering: a window whose first frame has y[hi] - y[lo] < 0 gets y := c - y, c the
     mean of the window's y (h36m_motion_3d.py:70-74); None: no check.  frames is never written, two calls give the same bits."""
+    stream, frames, starts, a = _gather_block(frames, starts, L, select, mean, std, up_joints)
+    items = _int_operand(items, "items", frames.device)
+    B = int(items.shape[0])
+    raw = torch.empty(B, a.L, a.J, 3, dtype=torch.float32, device=frames.device)
+    if B == 0:
+        return raw
+    a.B, a.items, a.raw = B, _ptr(items), _ptr(raw)
+    _lib.call("cg_gather_windows", ctypes.byref(a), stream)
+    return raw
+
+
+def _gather_block(frames, starts, L, select, mean, std, up_joints):
+    """What `gather_windows` and `gather_windows_at` check and fill alike: (stream, frames, starts, the CgGatherWindows block
+    without B / items / raw); the two returned operands have to outlive the launch."""
     if not torch.is_tensor(frames):
         raise TypeError("gather_windows: frames must be a tensor")
     stream = _stream(frames)
@@ -1717,8 +1738,8 @@ def gather_windows(frames, starts, items, L, select=None, mean=0.0, std=1.0, up_
     if L < 1 or F < L or J_src < 1:
         raise ValueError("gather_windows: windows of %d frames out of %d frames of %d joints" % (L, F, J_src))
     dev = frames.device
-    starts, items = _int_operand(starts, "starts", dev), _int_operand(items, "items", dev)
-    W, B = int(starts.shape[0]), int(items.shape[0])
+    starts = _int_operand(starts, "starts", dev)
+    W = int(starts.shape[0])
     if W < 1:
         raise ValueError("gather_windows: no windows")
     if select is not None:
@@ -1735,16 +1756,106 @@ def gather_windows(frames, starts, items, L, select=None, mean=0.0, std=1.0, up_
         up_hi, up_lo = (int(v) for v in up_joints)
         if not (0 <= up_hi < J and 0 <= up_lo < J):
             raise IndexError("gather_windows: up_joints %s out of range for %d selected joints" % ((up_hi, up_lo), J))
-    raw = torch.empty(B, L, J, 3, dtype=torch.float32, device=dev)
-    if B == 0:
-        return raw
     frames = _contig(frames)
     a = _lib.GatherWindows()
-    a.B, a.L, a.J_src, a.J, a.W, a.up_hi, a.up_lo, a.F, a.mean, a.std = B, L, J_src, J, W, up_hi, up_lo, F, float(mean), float(std)
-    a.frames, a.starts, a.items, a.raw = _ptr(frames), _ptr(starts), _ptr(items), _ptr(raw)
+    a.L, a.J_src, a.J, a.W, a.up_hi, a.up_lo, a.F, a.mean, a.std = L, J_src, J, W, up_hi, up_lo, F, float(mean), float(std)
+    a.frames, a.starts = _ptr(frames), _ptr(starts)
     a.select = _ptr(_index_tensor(select, dev)) if select is not None else None
-    _lib.call("cg_gather_windows", ctypes.byref(a), stream)
-    return raw
+    return stream, frames, starts, a
+
+
+def gather_windows_at(frames, starts, order, cursor, B, L, select=None, mean=0.0, std=1.0, up_joints=None, out=None):
+    """`gather_windows` with the window ids read on the device: window b of the batch is order[min(cursor[0] + b, W - 1)], `order`
+    (W) and `cursor` (1) int32 tensors on the device of `frames` (taken as they are: a captured step keeps reading the same
+    buffers, `cursor_advance` moves the cursor).  A cursor past W - B repeats order[W - 1], nothing is read out of bounds.  `out`:
+    a contiguous (B, L, J, 3) fp32 tensor to fill (a static buffer of a captured step) instead of a new one."""
+    stream, frames, starts, a = _gather_block(frames, starts, L, select, mean, std, up_joints)
+    dev, B = frames.device, int(B)
+    if B < 1:
+        raise ValueError("gather_windows_at: B must be positive")
+    for t, name, n in ((order, "order", a.W), (cursor, "cursor", 1)):
+        if not torch.is_tensor(t) or t.dtype != torch.int32 or t.dim() != 1 or not t.is_contiguous():
+            raise TypeError("gather_windows_at: %s must be a contiguous 1-D int32 tensor" % name)
+        if t.device != dev:
+            raise ValueError("gather_windows_at: %s is on %s, the data on %s" % (name, t.device, dev))
+        if int(t.shape[0]) != n:
+            raise ValueError("gather_windows_at: %s has %d entries, expected %d" % (name, int(t.shape[0]), n))
+    shape = (B, a.L, a.J, 3)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=dev)
+    elif tuple(out.shape) != shape or out.dtype != torch.float32 or out.device != dev or not out.is_contiguous():
+        raise ValueError("gather_windows_at: out must be a contiguous float32 %s tensor on %s" % (shape, dev))
+    a.B, a.raw = B, _ptr(out)
+    _lib.call("cg_gather_windows_at", ctypes.byref(a), _ptr(order), _ptr(cursor), stream)
+    return out
+
+
+def cursor_advance(cursor, by):
+    """cursor[0] += by on the device, by one kernel (capturable)"""
+    if not torch.is_tensor(cursor) or cursor.dtype != torch.int32 or cursor.numel() != 1:
+        raise TypeError("cursor_advance: cursor must be a one-element int32 tensor")
+    _lib.call("cg_cursor_advance", _ptr(cursor), int(by), _stream(cursor))
+    return cursor
+
+
+# ----------------------------------------------------------------------------------------------
+# the random draws of the augmentations on the device (csrc/augment_draw.hip)
+# ----------------------------------------------------------------------------------------------
+DRAW_LAYOUTS = {"table24": _lib.LIMITS["CG_DRAW_TABLE24"], "steps4": _lib.LIMITS["CG_DRAW_STEPS4"]}
+DRAW_KINDS = {k: _lib.LIMITS["CG_PERTURB_" + k.upper()] for k in ("rotation", "scale", "noise", "translation", "flip", "invert")}
+DRAW_MAX_STEPS = _lib.LIMITS["CG_PERTURB_MAX_STEPS"]
+
+
+def draw_augmentation(steps, B, J, layout, stream=0, out=None, noise_out=None, device=None):
+    """The parameter table of `cg_augment_sequences` (layout "table24": (B, 24)) or `cg_perturb_sequences` ("steps4": (B, n_steps, 4))
+    drawn on the device from the seed word of `seed_state` (cistgcn_hip.h: cg_draw_augmentation gives the generator).  steps: up
+    to 16 tuples (kind, prob_threshold, lo, hi) - kind one of rotation / scale / noise / translation / flip / invert (or its
+    CG_PERTURB_* code), lo and hi three numbers each: the bounds of the amounts; a flip's enabled axes in lo; a noise step's amplitude
+    in lo[0].  stream 0 .. 65535 separates independent draws under one seed.  Returns (table, noise): noise (B, n_noise, J, 3) of
+    U(-1, 1) when the list holds noise steps (then J >= 1 is required), else None.  `out` / `noise_out`: contiguous fp32 tensors of
+    those shapes to fill (static buffers of a captured step); `device`: where to draw when neither is given (default "cuda").  The
+    seed is read, not advanced: two calls give the same bits until `advance_seed` / `begin_step(bump_seed=True)` / `manual_seed`."""
+    if layout not in DRAW_LAYOUTS:
+        raise ValueError("draw_augmentation: unknown layout %r (one of %s)" % (layout, ", ".join(sorted(DRAW_LAYOUTS))))
+    steps = list(steps)
+    B, n_steps, stream = int(B), len(steps), int(stream)
+    if B < 1:
+        raise ValueError("draw_augmentation: B must be positive")
+    if n_steps > DRAW_MAX_STEPS:
+        raise ValueError("draw_augmentation: %d steps, the kernel takes %d" % (n_steps, DRAW_MAX_STEPS))
+    if not 0 <= stream <= 0xFFFF:
+        raise ValueError("draw_augmentation: stream must be in [0, 65535], got %d" % stream)
+    tab = (_lib.DrawStep * max(1, n_steps))()
+    n_noise = 0
+    for i, (kind, thr, lo, hi) in enumerate(steps):
+        code = DRAW_KINDS.get(kind, kind)
+        if code not in DRAW_KINDS.values():
+            raise ValueError("draw_augmentation: unknown kind %r in step %d" % (kind, i))
+        lo, hi = [float(v) for v in lo], [float(v) for v in hi]
+        if len(lo) != 3 or len(hi) != 3:
+            raise ValueError("draw_augmentation: step %d needs three lower and three upper bounds" % i)
+        tab[i].kind, tab[i].prob_threshold = int(code), float(thr)
+        for a in range(3):
+            tab[i].lo[a], tab[i].hi[a] = lo[a], hi[a]
+        n_noise += code == DRAW_KINDS["noise"]
+    if n_noise and (J is None or int(J) < 1):
+        raise ValueError("draw_augmentation: a noise step draws one number per joint and axis: J must be positive")
+    J = 0 if J is None else int(J)
+    dev = _dev(out.device if out is not None else noise_out.device if noise_out is not None else "cuda" if device is None else device)
+    shape = (B, 24) if layout == "table24" else (B, n_steps, 4)
+
+    def buffer(t, shape, name):
+        if t is None:
+            return torch.empty(shape, dtype=torch.float32, device=dev)
+        if tuple(t.shape) != shape or t.dtype != torch.float32 or t.device != dev or not t.is_contiguous():
+            raise ValueError("draw_augmentation: %s must be a contiguous float32 %s tensor on %s" % (name, shape, dev))
+        return t
+    out = buffer(out, shape, "out")
+    noise = buffer(noise_out, (B, n_noise, J, 3), "noise_out") if n_noise else None
+    seed = seed_state(dev)
+    _lib.call("cg_draw_augmentation", tab, n_steps, _ptr(seed), stream, B, J, DRAW_LAYOUTS[layout], _ptr(out) if out.numel() else None,
+              _ptr(noise), _stream(seed))
+    return out, noise
 
 
 def cumsum_time(x):

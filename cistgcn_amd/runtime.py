@@ -485,6 +485,94 @@ class EagerStep(_StepBase):
         return self.loss
 
 
+class BankStep(_StepBase):
+    """A training step that starts at the motion bank: seed advance, window gather at the feed's device cursor, the augmentation
+    draws on the device, the augmentation kernel into static `sample` / `target` / `target_gvel` buffers, forward + loss + backward
+    (`_StepBase._pass`), cursor advance - with `graph=True` captured once in a HIP graph by the rules of `GraphedStep` (warm-up on a
+    side stream; BatchNorm buffers, the seed, the feed's `cursor` and `order` restored afterwards; FlatAdam before the step object),
+    with `graph=False` the same launches issued eagerly.  Nothing per sample runs on the host and nothing is uploaded between replays.
+    As for `GraphedStep`, no autograd graph of an earlier eager pass over the model (a loss kept with its grad_fn) may be alive while
+    the step is captured; the eager form of this step keeps only the value of its loss for that reason.
+
+    feed: `MotionBank.feed(batch_size)`; augmentation: a `DeviceAugmentation` or `RobustnessTest` (its device draws, stream
+    `stream`: another random stream than the host draws that reproduce the reference); `loss` and `flat` as in `GraphedStep`.
+    `replay()` returns the loss and raises RuntimeError, from a host-side count, when the feed's epoch is used up (`len(feed)` batches;
+    `feed.start_epoch()` re-arms it).  `batch` holds the static tensors of the batch the last replay trained on, `raw` its windows
+    before the augmentation; `feed.items()` names the windows of the next one."""
+
+    def __init__(self, model, feed, augmentation, input_n, *, loss=None, flat=None, graph=True, warmup=3, stream=0):
+        bank = feed.bank
+        dev, B, L, input_n = bank.device, feed.batch_size, bank.seq_len, int(input_n)
+        J = int(bank.frames.shape[1]) if bank.select is None else len(bank.select)
+        if not 0 < input_n < L:
+            raise ValueError("BankStep: input_n %d for windows of %d frames" % (input_n, L))
+        self.feed, self.aug, self.input_n, self.stream = feed, augmentation, input_n, int(stream)
+        f32, To = torch.float32, L - input_n
+        self.batch = {"sample": torch.zeros(B, input_n, J, 3, dtype=f32, device=dev), "target": torch.zeros(B, To, J, 3, dtype=f32, device=dev),
+                      "target_vel": torch.zeros(B, To, J, 3, dtype=f32, device=dev), "target_gvel": torch.zeros(B, To, J, 1, dtype=f32, device=dev),
+                      "sample_vel": torch.zeros(B, input_n, J, 3, dtype=f32, device=dev)}
+        # the cached index tensors (joint selection, joint permutation) are uploaded here, the draw buffers allocated: no capture sees it
+        self.raw = feed.gather()
+        self.draws = augmentation.draw_device(B, joints=J, device=dev, stream=self.stream)
+        augmentation._perm(J, dev)
+        self._init_common(model, self.batch["sample"], self.batch["target"], flat, loss, self.batch["target_gvel"])
+        self.graph = None
+        if graph:
+            self._capture(warmup)
+        self._freeze_param_pointers()
+
+    def _launches(self):
+        """one step on the current stream; the host-side count of the feed is the caller's"""
+        B, dev = self.feed.batch_size, self.raw.device
+        with ops.step_pool(self._pool):
+            ops.advance_seed(dev)
+            self.feed.gather(out=self.raw)
+            self.aug.draw_device(B, joints=self.raw.shape[2], device=dev, stream=self.stream, out=self.draws)
+            self.aug(self.raw, self.input_n, params=self.draws, out=self.batch)
+            loss = self._pass()
+        ops.cursor_advance(self.feed.cursor, B)
+        return loss
+
+    def _capture(self, warmup):
+        dev, feed = self.raw.device, self.feed
+        snap = _buffers_snapshot(self.model, dev)
+        cursor, order = feed.cursor.clone(), feed.order.clone()
+        _drop_graph_attributes(self.model)     # of earlier eager passes: nothing of their autograd graphs may be alive during the capture
+        side = torch.cuda.Stream()
+        side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(side):
+            for _ in range(warmup):
+                self._launches()
+        torch.cuda.current_stream().wait_stream(side)
+        torch.cuda.synchronize()
+        _drop_graph_attributes(self.model)
+        self.graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(self.graph):
+            loss = self._launches()
+        self.loss = loss.detach()          # the value only (see GraphedStep)
+        _drop_graph_attributes(self.model)
+        _buffers_restore(self.model, dev, snap)
+        with torch.no_grad():
+            feed.cursor.copy_(cursor)
+            feed.order.copy_(order)
+
+    def replay(self):
+        if self.feed.taken >= len(self.feed):
+            raise RuntimeError("BankStep: the epoch is used up (%d batches of %d): feed.start_epoch() starts the next one"
+                               % (len(self.feed), self.feed.batch_size))
+        self._check_param_pointers()
+        if self.graph is not None:
+            self.graph.replay()
+        else:
+            # the value only: a loss with its grad_fn keeps the pass's AccumulateGrad nodes (bound to this stream) alive, and a later
+            # capture of the same model would run its backward across mismatched streams (see GraphedStep)
+            self.loss = self._launches().detach()
+        self.feed.taken += 1
+        if self.flat is not None:
+            self.flat.gather()
+        return self.loss
+
+
 class DataParallelStep(_StepBase):
     """One data-parallel training step of this replica (BASELINE configs[3] and [4]): forward + MPJPE +
     backward on the local shard, gradient mean over the group, optional FlatAdam update.

@@ -876,6 +876,58 @@ typedef struct CgGatherWindows {
   float* raw;
 } CgGatherWindows;
 int cg_gather_windows(const CgGatherWindows* a, void* stream);
+/* The same gather with the window ids read at a device-resident cursor, so that a captured step takes the next batch of an epoch
+ * without the host naming it: window id b is order[min(*cursor + b, W - 1)] (then clamped as items[b] is).  order (W) and cursor (1)
+ * are device pointers, a->items is ignored (it may be NULL); everything else, the return codes included, as cg_gather_windows, with
+ * -1 for a missing order / cursor.  A cursor past W - B repeats window order[W - 1] instead of reading out of bounds; a negative
+ * one is taken as 0. */
+int cg_gather_windows_at(const CgGatherWindows* a, const int32_t* order, const int32_t* cursor, void* stream);
+/* *cursor += by: one thread, a plain vector store (like cg_seed_bump), so that the cursor moves inside a captured step */
+int cg_cursor_advance(int32_t* cursor, int by, void* stream);
+
+/* ---- the random draws of the augmentations on the device (csrc/augment_draw.hip) ---------------------------------------------
+ * Fills the parameter table cg_augment_sequences / cg_perturb_sequences read from the device-resident seed word of the dropout
+ * (cg_seed_bump advances it), so that a captured step draws its own augmentations.  This is a different random stream than the
+ * host draws of environment/input_pipeline.py, which reproduce the reference's np.random order.
+ *   steps   n_steps descriptors on the HOST (copied into the launch: validated without reading device memory, the call stays
+ *           capturable), kind = a CG_PERTURB_* code.  rotation / scale / translation: the amounts are drawn from [lo[a], hi[a]];
+ *           flip: lo[a] != 0 marks an enabled axis; noise: the amplitude is lo[0]; inversion: nothing else.
+ *   seed    the device seed word, read and never written;  stream_id 0 .. 65535 separates independent draws under one seed
+ * Generator (the specification a test restates):
+ *   bits = splitmix64 finaliser of (seed, salt, counter), the dropout hash:
+ *            z = counter + seed * 0x9E3779B97F4A7C15 + (salt << 40) + 0x632BE59BD9B4E019   (mod 2^64)
+ *            z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9;  z = (z ^ (z >> 27)) * 0x94D049BB133111EB;  bits = z ^ (z >> 31)
+ *   u = (bits >> 40) * 2^-24, in [0, 1) and exact in fp32
+ *   parameters  salt = CG_DRAW_SALT + stream_id, counter = (b * n_steps + step) * 4 + slot; slot 0 is the coin of the step, slots
+ *               1 - 3 its three amounts; a flip has the coins of x, y, z in slots 0 - 2 and draws only for its enabled axes
+ *   noise       salt = CG_DRAW_SALT + 0x10000 + stream_id, counter = ((b * n_noise + noise_slot) * J + j) * 3 + axis, value = 2 u - 1;
+ *               noise_slot counts the noise steps of the list in order; drawn whether or not the step's coin says 'apply'
+ *   a step applies iff u > prob_threshold (fp32 comparison; `rng.uniform() > thr` of the reference)
+ *   amount = lo + (hi - lo) * u in f64 from the fp32 bounds, rounded to fp32 once
+ * The counters are fixed: unlike the host path no draw depends on the outcome of another.  Dropout site ids share the salt field
+ * and stay below CG_DRAW_SALT (the model asserts it).
+ * Outputs (device):
+ *   layout CG_DRAW_TABLE24  table (B,24), the row of cg_augment_sequences: flips 0-2, rotate? 3, R row-major 4-12 (Rodrigues'
+ *                           formula in f64 on the drawn fp32 degrees, rounded once), scale 13-15, translation 16-18, noise
+ *                           amplitude 19, invert? 20, 21-23 zero.  A step that does not apply - and a kind the list does not hold -
+ *                           leaves the identity: scale 1, everything else 0.  Of a kind that occurs more than once the LAST step
+ *                           fills the columns (the others are drawn and dropped).
+ *   layout CG_DRAW_STEPS4   table (B,n_steps,4), the rows [apply?, v0, v1, v2] of cg_perturb_sequences: rotation in degrees, scale
+ *                           factors, translation rates, noise [1, amplitude, 0, 0], inversion [1, 0, 0, 0], flip [OR of the axes,
+ *                           x, y, z]; all four 0 when the step does not apply.  n_steps == 0: nothing to write.
+ *   noise_tab (B,n_noise,J,3) U(-1,1), with either layout, when the list holds noise steps
+ * One thread per (sample, step) and one per noise element (grid-stride past CG_DRAW_MAX_BLOCKS workgroups of CG_DRAW_THREADS);
+ * no atomics: two calls under the same seed give the same bits.
+ * Returns -1 for a missing seed / table / steps (n_steps > 0); -2 for B < 1, n_steps outside [0, CG_PERTURB_MAX_STEPS], an
+ * unknown kind or layout, stream_id outside [0, 65535], or a noise step with J < 1 or without noise_tab. */
+#define CG_DRAW_SALT 0x800000
+#define CG_DRAW_TABLE24 0
+#define CG_DRAW_STEPS4 1
+#define CG_DRAW_THREADS 256
+#define CG_DRAW_MAX_BLOCKS 4096
+typedef struct CgDrawStep { int kind; float prob_threshold; float lo[3]; float hi[3]; } CgDrawStep;
+int cg_draw_augmentation(const CgDrawStep* steps, int n_steps, const unsigned long long* seed, int stream_id, int B, int J, int layout,
+                         float* table, float* noise_tab, void* stream);
 
 #ifdef __cplusplus
 }
