@@ -8,9 +8,16 @@
 //   forward   A  streaming: a workgroup takes a contiguous span of a few channel planes, writes xn (16-byte accesses) and, from the LDS
 //                image of the span, the mean / centred sum of squares of every row of V joints (rm, rq: (B,C,T), kept for the backward)
 //             B  per sample, tiny: the four statistics from rm / rq
-//   backward  C  per sample, tiny: the statistics' gradient as a slope and an offset per row:  d xn[c,t,v] += xn P[c,t] + Q[c,t]
-//             D  streaming: G = sum_i g_i + xn P + Q  (xn recomputed from x, bit for bit), G stored once, BatchNorm sums in f64
+//   backward  C  per sample, tiny: the statistics' gradient as a slope and an offset per row:  d xn[c,t,v] += (xn - rm[c,t]) P[c,t] + Q[c,t]
+//             D  streaming: G = sum_i g_i + (xn - rm) P + Q  (xn recomputed from x, bit for bit), G stored once, BatchNorm sums in f64
 //             E  streaming: dx = gamma rstd (G - mean G - xhat mean(G xhat))
+// Constant rows, channels and samples (a dead coordinate, a padded sample): the rule of torch, which cg_dstd_stats_* (stages.hip) shares.
+//   * exact zero on equal values: a mean of the statistics - over the V joints of a row, over the T row means of a channel, over the
+//     C stds - whose values are all equal is that value itself, not sum / n: every difference from it and the std are then exactly 0
+//     (a plain sum of 22 copies of 0.7f is not 22 x 0.7f, and left a std of 1e-8).  Unequal values are summed as before, bit for bit
+//   * sub-gradient 0 at std = 0: each of the four quotients of backward C (row std, channel std, std over c of the row stds at a t, std
+//     over c of the channel stds) is 0 where its std is 0, as in std_backward.  Forward B and backward C form the stds with the same
+//     calls (cg_bin_channel_stats, cg_bin_over_c), so the backward tests the very value the forward wrote.  No epsilon anywhere.
 #include <initializer_list>
 #include "cg_common.h"
 #include "cg_phase.h"
@@ -55,13 +62,29 @@ __global__ __launch_bounds__(CG_BIN_THREADS) void cg_bin_fwd_kernel(CgBlockInput
   const long long rbase = ((long long)b * t.C + c0) * t.T;
   for (int r = tid; r < npl * t.T; r += CG_BIN_THREADS) {
     const float* row = sXn + r * t.V;
+    const float x0 = row[0];
     float s = 0.f;
-    for (int v = 0; v < t.V; ++v) s += row[v];
-    const float m = s / (float)t.V;
+    bool equal = true;
+    for (int v = 0; v < t.V; ++v) { s += row[v]; equal = equal && row[v] == x0; }
+    const float m = equal ? x0 : s / (float)t.V;                // a constant row: its value itself (sum / V rounds), rq exactly 0
     float q = 0.f;
     for (int v = 0; v < t.V; ++v) { const float d = row[v] - m; q += d * d; }
     t.rm[rbase + r] = m; t.rq[rbase + r] = q;
   }
+}
+
+// mean and unbiased std of the C values f(0) .. f(C - 1).  Equal values: the mean is that value itself, not sum / C (which rounds), so
+// that every difference and the std are exactly 0
+template <class F> __device__ __forceinline__ void cg_bin_over_c(int C, F f, float& mean, float& sd) {
+  const float f0 = f(0);
+  float s = 0.f;
+  bool equal = true;
+  for (int c = 0; c < C; ++c) { s += f(c); equal = equal && f(c) == f0; }
+  const float m = equal ? f0 : s / (float)C;
+  float q = 0.f;
+  for (int c = 0; c < C; ++c) { const float d = f(c) - m; q += d * d; }
+  mean = m;
+  sd = sqrtf(q / (float)(C - 1));
 }
 
 // rm / rq of one sample into LDS, then per-channel mean and unbiased std over (T,V)
@@ -70,9 +93,11 @@ __device__ __forceinline__ void cg_bin_channel_stats(const CgBlockInput& t, int 
   for (int r = threadIdx.x; r < C * T; r += blockDim.x) { rm[r] = t.rm[(long long)b * C * T + r]; rq[r] = t.rq[(long long)b * C * T + r]; }
   __syncthreads();
   for (int c = threadIdx.x; c < C; c += blockDim.x) {
+    const float m0 = rm[c * T];
     float m = 0.f;
-    for (int k = 0; k < T; ++k) m += rm[c * T + k];
-    m /= (float)T;
+    bool equal = true;
+    for (int k = 0; k < T; ++k) { m += rm[c * T + k]; equal = equal && rm[c * T + k] == m0; }
+    m = equal ? m0 : m / (float)T;
     float q = 0.f;
     for (int k = 0; k < T; ++k) { const float d = rm[c * T + k] - m; q += rq[c * T + k] + (float)V * d * d; }
     cm[c] = m;
@@ -95,26 +120,19 @@ __global__ __launch_bounds__(CG_BIN_THREADS) void cg_bin_stats_kernel(CgBlockInp
     float m = 0.f;
     for (int c = 0; c < C; ++c) m += cm[c];
     o[0] = m / (float)C;
-    float sm = 0.f;
-    for (int c = 0; c < C; ++c) sm += cs[c];
-    sm /= (float)C;
-    float q = 0.f;
-    for (int c = 0; c < C; ++c) { const float d = cs[c] - sm; q += d * d; }
-    o[1 + T] = sqrtf(q / (float)(C - 1));
+    float sm;
+    cg_bin_over_c(C, [&](int c) { return cs[c]; }, sm, o[1 + T]);
   }
   for (int k = threadIdx.x; k < T; k += blockDim.x) {
-    float m = 0.f, sm = 0.f;
-    for (int c = 0; c < C; ++c) { m += rm[c * T + k]; sm += sqrtf(rq[c * T + k] / (float)(V - 1)); }
+    float m = 0.f, sm;
+    for (int c = 0; c < C; ++c) m += rm[c * T + k];
     o[1 + k] = m / (float)C;
-    sm /= (float)C;
-    float q = 0.f;
-    for (int c = 0; c < C; ++c) { const float d = sqrtf(rq[c * T + k] / (float)(V - 1)) - sm; q += d * d; }
-    o[2 + T + k] = sqrtf(q / (float)(C - 1));
+    cg_bin_over_c(C, [&](int c) { return sqrtf(rq[c * T + k] / (float)(V - 1)); }, sm, o[2 + T + k]);
   }
 }
 
 // ======================================================================================================================
-// backward C: d xn[c,t,v] (from the statistics) = xn * P[c,t] + Q[c,t]
+// backward C: d xn[c,t,v] (from the statistics) = (xn - rm[c,t]) * P[c,t] + Q[c,t]
 // ======================================================================================================================
 __global__ __launch_bounds__(CG_BIN_THREADS) void cg_bin_coef_kernel(CgBlockInput t) {
   const int C = t.C, T = t.T, V = t.V;
@@ -134,47 +152,39 @@ __global__ __launch_bounds__(CG_BIN_THREADS) void cg_bin_coef_kernel(CgBlockInpu
     sg[i] = v;
   }
   cg_bin_channel_stats(t, b, rm, rq, cm, cs);
-  if (threadIdx.x == 0) {
-    float sm = 0.f;
-    for (int c = 0; c < C; ++c) sm += cs[c];
-    sm /= (float)C;
-    float q = 0.f;
-    for (int c = 0; c < C; ++c) { const float d = cs[c] - sm; q += d * d; }
-    gS = sqrtf(q / (float)(C - 1));
-    gSm = sm;
-  }
-  for (int k = threadIdx.x; k < T; k += blockDim.x) {
-    float sm = 0.f;
-    for (int c = 0; c < C; ++c) sm += sqrtf(rq[c * T + k] / (float)(V - 1));
-    sm /= (float)C;
-    float q = 0.f;
-    for (int c = 0; c < C; ++c) { const float d = sqrtf(rq[c * T + k] / (float)(V - 1)) - sm; q += d * d; }
-    tS[k] = sqrtf(q / (float)(C - 1));
-    tM[k] = sm;
-  }
+  // the same calls as forward B: the stds tested below are the very values it wrote
+  if (threadIdx.x == 0) cg_bin_over_c(C, [&](int c) { return cs[c]; }, gSm, gS);
+  for (int k = threadIdx.x; k < T; k += blockDim.x)
+    cg_bin_over_c(C, [&](int c) { return sqrtf(rq[c * T + k] / (float)(V - 1)); }, tM[k], tS[k]);
   __syncthreads();
   const float g0 = sg[0] / (float)(C * T * V);
   const float gall = sg[1 + T];
   float* pq = t.pq + (long long)b * C * T * 2;
   for (int r = threadIdx.x; r < C * T; r += blockDim.x) {
     const int c = r / T, k = r - c * T;
-    // std over c of s_c, s_c = std over (t,v);  std over c of s_ct, s_ct = std over v
-    const float pc = gall * (cs[c] - gSm) / ((float)(C - 1) * gS) / ((float)(T * V - 1) * cs[c]);
+    // std over c of s_c, s_c = std over (t,v);  std over c of s_ct, s_ct = std over v.  Each of the four quotients is 0 where its
+    // std is 0 (the sub-gradient torch's std_backward takes at the kink)
+    const float ac = gS > 0.f ? gall * (cs[c] - gSm) / ((float)(C - 1) * gS) : 0.f;
+    const float pc = cs[c] > 0.f ? ac / ((float)(T * V - 1) * cs[c]) : 0.f;
     const float sct = sqrtf(rq[r] / (float)(V - 1));
-    const float pr = sg[2 + T + k] * (sct - tM[k]) / ((float)(C - 1) * tS[k]) / ((float)(V - 1) * sct);
+    const float ar = tS[k] > 0.f ? sg[2 + T + k] * (sct - tM[k]) / ((float)(C - 1) * tS[k]) : 0.f;
+    const float pr = sct > 0.f ? ar / ((float)(V - 1) * sct) : 0.f;
+    // pc (xn - cm) + pr (xn - rm) = (pc + pr) (xn - rm) + pc (rm - cm): the slope meets differences from the row's own mean, so that on a
+    // nearly constant row (P ~ 1 / std) no product xn P of 1e5 is cancelled by the offset
     pq[2 * r] = pc + pr;
-    pq[2 * r + 1] = g0 + sg[1 + k] / (float)(C * V) - pc * cm[c] - pr * rm[r];
+    pq[2 * r + 1] = g0 + sg[1 + k] / (float)(C * V) + pc * (rm[r] - cm[c]);
   }
 }
 
 // ======================================================================================================================
-// backward D: G = sum_i g_i + xn P + Q over a span of channel planes; f64 sums of G and G xhat per channel
+// backward D: G = sum_i g_i + (xn - rm) P + Q over a span of channel planes; f64 sums of G and G xhat per channel
 // ======================================================================================================================
 template <int VW>
 __global__ __launch_bounds__(CG_BIN_THREADS) void cg_bin_bwd_sum_kernel(CgBlockInput t, CgBinGeom g) {
   float* sPQ = reinterpret_cast<float*>(cg_dyn_lds);           // [NPL * T][2]
   float* sAff = sPQ + 2 * g.NPL * t.T;                        // [NPL][4]: mean, rstd, scale, shift
   double* sRed = reinterpret_cast<double*>(sAff + 4 * g.NPL);      // [NPL][2]; an even number of floats in front of it
+  float* sRM = reinterpret_cast<float*>(sRed + 2 * g.NPL);        // [NPL * T] row means of xn (forward A)
   const int tid = threadIdx.x;
   const int b = blockIdx.x / g.cps, c0 = (blockIdx.x - b * g.cps) * g.NPL, npl = min(g.NPL, t.C - c0);
   if (tid < npl) {
@@ -183,6 +193,7 @@ __global__ __launch_bounds__(CG_BIN_THREADS) void cg_bin_bwd_sum_kernel(CgBlockI
     sRed[2 * tid] = 0.0; sRed[2 * tid + 1] = 0.0;
   }
   for (int i = tid; i < 2 * npl * t.T; i += CG_BIN_THREADS) sPQ[i] = t.pq ? t.pq[((long long)b * t.C + c0) * t.T * 2 + i] : 0.f;
+  for (int i = tid; i < npl * t.T; i += CG_BIN_THREADS) sRM[i] = t.pq ? t.rm[((long long)b * t.C + c0) * t.T + i] : 0.f;
   __syncthreads();
   const long long base = ((long long)b * t.C + c0) * g.TV;
   const int L = npl * g.TV;
@@ -220,7 +231,7 @@ __global__ __launch_bounds__(CG_BIN_THREADS) void cg_bin_bwd_sum_kernel(CgBlockI
       const int r = (int)cg_div_ge2((unsigned)(e + j), g.magicV);
       const float d = x[j] - a[0];
       const float xn = d * a[2] + a[3];                          // the forward's expression: the same xn bit for bit
-      const float G = acc[j] + xn * sPQ[2 * r] + sPQ[2 * r + 1];
+      const float G = acc[j] + (xn - sRM[r]) * sPQ[2 * r] + sPQ[2 * r + 1];
       acc[j] = G;
       s1 += (double)G; s2 += (double)G * (double)(d * a[1]);
     }
@@ -279,6 +290,8 @@ static int cg_bin_geometry(const CgBlockInput* t, CgBinGeom* g) {
   if (g->NPL > t->C) g->NPL = t->C;
   g->cps = (t->C + g->NPL - 1) / g->NPL;
   g->L = g->NPL * g->TV;
+  // dynamic LDS of backward D (the largest beside the span itself): thousands of tiny planes in one span would pass the default limit
+  if (((size_t)3 * g->NPL * t->T + 4 * g->NPL + 2) * sizeof(float) + (size_t)2 * g->NPL * sizeof(double) > 64 * 1024) return CG_ESHAPE;
   g->magicTV = cg_div_magic(g->TV); g->magicV = cg_div_magic(t->V);
   if ((long long)t->B * g->cps > 2147483647LL) return CG_ESHAPE;
   return CG_OK;
@@ -355,7 +368,7 @@ extern "C" int cg_block_input_bwd(const CgBlockInput* t, void* stream_) {
     if (st != CG_OK) return st;
   } else a.pq = nullptr;
   const dim3 grid(cg_bin_grid(t, g));
-  const size_t lds = ((size_t)2 * g.NPL * t->T + 4 * g.NPL + 2) * sizeof(float) + (size_t)2 * g.NPL * sizeof(double);
+  const size_t lds = ((size_t)3 * g.NPL * t->T + 4 * g.NPL + 2) * sizeof(float) + (size_t)2 * g.NPL * sizeof(double);
   int vw = cg_bin_vw(g, {t->x, t->gsum, t->g[0], t->g[1], t->g[2], t->g[3], t->g[4], t->g[5], t->g[6], t->g[7]});
   if (vw == 4) hipLaunchKernelGGL(cg_bin_bwd_sum_kernel<4>, grid, block, lds, stream, a, g);
   else if (vw == 2) hipLaunchKernelGGL(cg_bin_bwd_sum_kernel<2>, grid, block, lds, stream, a, g);

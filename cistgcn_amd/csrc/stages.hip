@@ -84,6 +84,10 @@ extern "C" int cg_feature_lift_bwd(const float* x, const float* df, float* dx, l
 //   out[b] = [ mean_c mean_{t,v} | mean_c mean_v (T) | std_c std_{t,v} | std_c std_v (T) ], all std unbiased.
 // One workgroup per sample.  LDS: per-(c,t) row mean and centred sum of squares, per-c mean and std.
 // Dynamic LDS layout (floats): rm[C*T] | rq[C*T] | cm[C] | cs[C]
+// Constant rows, channels and samples: the rule of torch, shared with cg_block_input_* (block_input.hip, whose header spells it out).
+// Exact zero on equal values: a mean (over V, over the T row means, over the C stds) of equal values is that value itself, not sum / n.
+// Sub-gradient 0 at std = 0: each of the four quotients of the backward is 0 where its std is 0; forward and backward form the stds
+// with the same calls (cg_stats_rows, cg_stats_over_c).  No epsilon.
 // ---------------------------------------------------------------------------------------------
 HIP_DYNAMIC_SHARED(unsigned char, cg_dyn_lds)
 
@@ -97,43 +101,73 @@ __device__ __forceinline__ float cg_stats_group_sum(float v, int lpr) {
   return v;
 }
 
+// mean and unbiased std of the C values f(0) .. f(C - 1).  Equal values: the mean is that value itself, not sum / C (which rounds), so
+// that every difference and the std are exactly 0
+template <class F> __device__ __forceinline__ void cg_stats_over_c(int C, F f, float& mean, float& sd) {
+  const float f0 = f(0);
+  float s = 0.f;
+  bool equal = true;
+  for (int c = 0; c < C; ++c) { s += f(c); equal = equal && f(c) == f0; }
+  const float m = equal ? f0 : s / (float)C;
+  float q = 0.f;
+  for (int c = 0; c < C; ++c) { const float d = f(c) - m; q += d * d; }
+  mean = m;
+  sd = sqrtf(q / (float)(C - 1));
+}
+
 // per-(c,t) row mean and centred sum of squares (one coalesced read of the sample: a group of lanes per row, the row's
-// values stay in registers between the two sums), then per-c mean and std
-__device__ __forceinline__ void cg_stats_rows(const float* xb, int C, int T, int V, float* rm, float* rq, float* cm, float* cs) {
+// values stay in registers between the two sums), then per-c mean and std.  A row of equal values, or a channel of equal row
+// means, takes that value itself as its mean (sum / n rounds): every difference, rq and cs are then exactly 0.
+// RESID (the backward): rd[c,t] = mean_v(x - rm[c,t]), what the rounded row mean rm is short of the mean of the row.  On a nearly constant
+// row (0.7 + 1e-6 noise) the differences are exact and rm is 1e-7 off, a tenth of the row's spread; rm stays what the forward wrote
+template <bool RESID>
+__device__ __forceinline__ void cg_stats_rows(const float* xb, int C, int T, int V, float* rm, float* rq, float* cm, float* cs, float* rd = nullptr) {
   const int lpr = cg_stats_lpr(V), gl = threadIdx.x & (lpr - 1), grp = threadIdx.x / lpr, ngrp = blockDim.x / lpr;
   const int rows = C * T, iters = (rows + CG_DSTD_ROWS_IN_FLIGHT * ngrp - 1) / (CG_DSTD_ROWS_IN_FLIGHT * ngrp);
   for (int it = 0; it < iters; ++it) {                 // every lane runs every iteration: the group sums are wave-wide exchanges
-    float x0[4], s[4], m[4], q[4];
+    float x0[4], f[4], s[4], m[4], q[4], ne[4], e[4];
     int rr[4];
 #pragma unroll
     for (int k = 0; k < 4; ++k) {                      // four rows per group in flight
       rr[k] = (CG_DSTD_ROWS_IN_FLIGHT * it + k) * ngrp + grp;
       const bool ok = rr[k] < rows && gl < V;
       x0[k] = ok ? xb[(long long)rr[k] * V + gl] : 0.f;
+      f[k] = rr[k] < rows ? xb[(long long)rr[k] * V] : 0.f;      // the row's first value, in every lane of its group
     }
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
       s[k] = x0[k];
-      if (V > 64 && rr[k] < rows) for (int v = gl + 64; v < V; v += 64) s[k] += xb[(long long)rr[k] * V + v];
+      ne[k] = (rr[k] < rows && gl < V && x0[k] != f[k]) ? 1.f : 0.f;      // values of the row that differ from its first
+      if (V > 64 && rr[k] < rows) for (int v = gl + 64; v < V; v += 64) { const float xv = xb[(long long)rr[k] * V + v]; s[k] += xv; if (xv != f[k]) ne[k] += 1.f; }
     }
 #pragma unroll
-    for (int k = 0; k < 4; ++k) m[k] = cg_stats_group_sum(s[k], lpr) / (float)V;
+    for (int k = 0; k < 4; ++k) {
+      m[k] = cg_stats_group_sum(s[k], lpr) / (float)V;
+      if (cg_stats_group_sum(ne[k], lpr) == 0.f) m[k] = f[k];
+    }
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
       q[k] = (rr[k] < rows && gl < V) ? (x0[k] - m[k]) * (x0[k] - m[k]) : 0.f;
-      if (V > 64 && rr[k] < rows) for (int v = gl + 64; v < V; v += 64) { const float d = xb[(long long)rr[k] * V + v] - m[k]; q[k] += d * d; }
+      e[k] = (RESID && rr[k] < rows && gl < V) ? x0[k] - m[k] : 0.f;
+      if (V > 64 && rr[k] < rows) for (int v = gl + 64; v < V; v += 64) { const float d = xb[(long long)rr[k] * V + v] - m[k]; q[k] += d * d; if (RESID) e[k] += d; }
     }
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
       q[k] = cg_stats_group_sum(q[k], lpr);
       if (rr[k] < rows && gl == 0) { rm[rr[k]] = m[k]; rq[rr[k]] = q[k]; }
+      if (RESID) {
+        e[k] = cg_stats_group_sum(e[k], lpr) / (float)V;
+        if (rr[k] < rows && gl == 0) rd[rr[k]] = e[k];
+      }
     }
   }
   __syncthreads();
   for (int c = threadIdx.x; c < C; c += blockDim.x) {
+    const float m0 = rm[c * T];
     float m = 0.f;
-    for (int t = 0; t < T; ++t) m += rm[c * T + t];
-    m /= (float)T;
+    bool equal = true;
+    for (int t = 0; t < T; ++t) { m += rm[c * T + t]; equal = equal && rm[c * T + t] == m0; }
+    m = equal ? m0 : m / (float)T;
     float q = 0.f;
     for (int t = 0; t < T; ++t) { const float d = rm[c * T + t] - m; q += rq[c * T + t] + (float)V * d * d; }
     cm[c] = m;
@@ -149,31 +183,24 @@ __global__ __launch_bounds__(CG_DSTD_THREADS) void cg_dstd_stats_fwd_kernel(cons
   float* cs = cm + C;
   const int b = blockIdx.x;
   const float* xb = x + (long long)b * C * T * V;
-  cg_stats_rows(xb, C, T, V, rm, rq, cm, cs);
+  cg_stats_rows<false>(xb, C, T, V, rm, rq, cm, cs);
   float* o = out + (long long)b * (2 + 2 * T);
   if (threadIdx.x == 0) {
     float m = 0.f;
     for (int c = 0; c < C; ++c) m += cm[c];
     o[0] = m / (float)C;
-    float sm = 0.f;
-    for (int c = 0; c < C; ++c) sm += cs[c];
-    sm /= (float)C;
-    float q = 0.f;
-    for (int c = 0; c < C; ++c) { const float d = cs[c] - sm; q += d * d; }
-    o[1 + T] = sqrtf(q / (float)(C - 1));
+    float sm;
+    cg_stats_over_c(C, [&](int c) { return cs[c]; }, sm, o[1 + T]);
   }
   for (int t = threadIdx.x; t < T; t += blockDim.x) {
-    float m = 0.f, sm = 0.f;
-    for (int c = 0; c < C; ++c) { m += rm[c * T + t]; sm += sqrtf(rq[c * T + t] / (float)(V - 1)); }
+    float m = 0.f, sm;
+    for (int c = 0; c < C; ++c) m += rm[c * T + t];
     o[1 + t] = m / (float)C;
-    sm /= (float)C;
-    float q = 0.f;
-    for (int c = 0; c < C; ++c) { const float d = sqrtf(rq[c * T + t] / (float)(V - 1)) - sm; q += d * d; }
-    o[2 + T + t] = sqrtf(q / (float)(C - 1));
+    cg_stats_over_c(C, [&](int c) { return sqrtf(rq[c * T + t] / (float)(V - 1)); }, sm, o[2 + T + t]);
   }
 }
 
-// backward: d x[c,t,v] = x * P[c,t] + Q[c,t] with row coefficients from the four statistics' gradients
+// backward: d x[c,t,v] = (x - rm[c,t]) * P[c,t] + Q[c,t] with row coefficients from the four statistics' gradients
 __global__ __launch_bounds__(CG_DSTD_THREADS) void cg_dstd_stats_bwd_kernel(const float* __restrict__ x, const float* __restrict__ dout, float* __restrict__ dx,
                                          int C, int T, int V) {
   float* rm = (float*)cg_dyn_lds;
@@ -188,44 +215,35 @@ __global__ __launch_bounds__(CG_DSTD_THREADS) void cg_dstd_stats_bwd_kernel(cons
   const int b = blockIdx.x;
   const float* xb = x + (long long)b * C * T * V;
   const float* g = dout + (long long)b * (2 + 2 * T);
-  cg_stats_rows(xb, C, T, V, rm, rq, cm, cs);
-  if (threadIdx.x == 0) {
-    float sm = 0.f;
-    for (int c = 0; c < C; ++c) sm += cs[c];
-    sm /= (float)C;
-    float q = 0.f;
-    for (int c = 0; c < C; ++c) { const float d = cs[c] - sm; q += d * d; }
-    gS = sqrtf(q / (float)(C - 1));
-    gSm = sm;
-  }
-  for (int t = threadIdx.x; t < T; t += blockDim.x) {
-    float sm = 0.f;
-    for (int c = 0; c < C; ++c) sm += sqrtf(rq[c * T + t] / (float)(V - 1));
-    sm /= (float)C;
-    float q = 0.f;
-    for (int c = 0; c < C; ++c) { const float d = sqrtf(rq[c * T + t] / (float)(V - 1)) - sm; q += d * d; }
-    tS[t] = sqrtf(q / (float)(C - 1));
-    tM[t] = sm;
-  }
+  cg_stats_rows<true>(xb, C, T, V, rm, rq, cm, cs, rQ);       // rQ holds the residuals rd until the offsets replace them below
+  // the same calls as the forward: the stds tested below are the very values it wrote
+  if (threadIdx.x == 0) cg_stats_over_c(C, [&](int c) { return cs[c]; }, gSm, gS);
+  for (int t = threadIdx.x; t < T; t += blockDim.x)
+    cg_stats_over_c(C, [&](int c) { return sqrtf(rq[c * T + t] / (float)(V - 1)); }, tM[t], tS[t]);
   __syncthreads();
   const float g0 = g[0] / (float)(C * T * V);
   const float gall = g[1 + T];
   for (int r = threadIdx.x; r < C * T; r += blockDim.x) {
     const int c = r / T, t = r - c * T;
-    // std over c of s_c, s_c = std over (t,v);  std over c of s_ct, s_ct = std over v
-    const float pc = gall * (cs[c] - gSm) / ((float)(C - 1) * gS) / ((float)(T * V - 1) * cs[c]);
+    // std over c of s_c, s_c = std over (t,v);  std over c of s_ct, s_ct = std over v.  Each of the four quotients is 0 where its
+    // std is 0 (the sub-gradient torch's std_backward takes at the kink)
+    const float ac = gS > 0.f ? gall * (cs[c] - gSm) / ((float)(C - 1) * gS) : 0.f;
+    const float pc = cs[c] > 0.f ? ac / ((float)(T * V - 1) * cs[c]) : 0.f;
     const float sct = sqrtf(rq[r] / (float)(V - 1));
-    const float pr = g[2 + T + t] * (sct - tM[t]) / ((float)(C - 1) * tS[t]) / ((float)(V - 1) * sct);
+    const float ar = tS[t] > 0.f ? g[2 + T + t] * (sct - tM[t]) / ((float)(C - 1) * tS[t]) : 0.f;
+    const float pr = sct > 0.f ? ar / ((float)(V - 1) * sct) : 0.f;
+    // pc (x - cm) + pr (x - rm) = (pc + pr) (x - rm) + pc (rm - cm): the slope meets differences from the row's own mean, so that on a
+    // nearly constant row (P ~ 1 / std) no product x P of 1e5 is cancelled by the offset
     rP[r] = pc + pr;
-    rQ[r] = g0 + g[1 + t] / (float)(C * V) - pc * cm[c] - pr * rm[r];
+    rQ[r] = g0 + g[1 + t] / (float)(C * V) + pc * (rm[r] - cm[c]) - pr * rQ[r];      // pr (x - rm - rd): the row mean to the residual
   }
   __syncthreads();
   float* dxb = dx + (long long)b * C * T * V;
   const int lpr = cg_stats_lpr(V), gl = threadIdx.x & (lpr - 1), grp = threadIdx.x / lpr, ngrp = blockDim.x / lpr;
 #pragma unroll 4
   for (int r = grp; r < C * T; r += ngrp) {
-    const float P = rP[r], Q = rQ[r];
-    for (int v = gl; v < V; v += 64) dxb[(long long)r * V + v] = xb[(long long)r * V + v] * P + Q;
+    const float P = rP[r], Q = rQ[r], m = rm[r];
+    for (int v = gl; v < V; v += 64) dxb[(long long)r * V + v] = (xb[(long long)r * V + v] - m) * P + Q;
   }
 }
 

@@ -1110,11 +1110,12 @@ def check_model_golden(device, name, modes=("eval", "train"), fused=True, staged
                 assert_close(net.state_dict()[k[len("train/state_after/"):]], ref, "%s %s" % (name, k))
 
 
-def check_model_vs_oracle(device, C, T, V, B, mode, seed=0, scale=350.0, fused=True, smooth=False, **cfg_kw):
+def check_model_vs_oracle(device, C, T, V, B, mode, seed=0, scale=350.0, fused=True, smooth=False, edit=None, **cfg_kw):
     """smooth=True sets every PReLU slope to 1 (no kink): the network is then differentiable everywhere except the
     ContextLayer max, and gradients are held to the strict criterion 'as accurate as the reference fp32 CPU path
     against fp64'.  With the real slopes, kink flips are legitimate (helpers.assert_grads_close)."""
-    """Product model vs the CPU oracle on fresh seeded inputs (any size the oracle finishes in seconds)."""
+    """Product model vs the CPU oracle on fresh seeded inputs (any size the oracle finishes in seconds).  edit: a function of the input
+    batch, applied before the target is derived from it (tests/degenerate_checks.py: a dead coordinate, a padded sample)."""
     g = _gen(1000 + seed)
     net, ora = build_pair(C, T, V, device, seed=seed, fused=fused, **cfg_kw)
     To = cfg_kw.get("To", 25)
@@ -1129,6 +1130,8 @@ def check_model_vs_oracle(device, C, T, V, B, mode, seed=0, scale=350.0, fused=T
                     p.fill_(1.0)
     net.load_state_dict(ora.state_dict())
     x = 50 + scale * torch.randn(B, T, V, 3, generator=g)
+    if edit is not None:
+        x = edit(x)
     tgt = x[:, -1:] + 20 * torch.randn(B, To, V, 3, generator=g)
     ora.train(); net.train()
     with torch.no_grad():                      # settle running statistics on both sides identically

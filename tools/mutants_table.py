@@ -102,6 +102,9 @@ ADAM = ["checks.check_flat_adam", "glue_checks.check_flat_adam"]
 ADAM_CLIP = "glue_checks.check_flat_adam_clip"
 
 
+STATS_DEGENERATE = ["checks.check_stage_kernels", "glue_checks.check_dstd_stats", "degenerate_checks.check_dstd_stats_degenerate"]
+BIN_DEGENERATE = ["checks.check_block_input", "degenerate_checks.check_block_input_degenerate"]
+
 FPN = ("checks.check_dilated_convs", (), {"shapes": ((3, 6, 5, 4, 6), (2, 5, 4, 10, 7))})
 
 def off_centre(name):
@@ -182,4 +185,20 @@ ROWS = [
     dict(id="maps-bias-dropped", file="tower_maps.hip", old="sBias[r] = (m < t.M[i] && t.bias[i]) ? t.bias[i][m] : 0.f;", new="sBias[r] = 0.f;", checks=["checks.check_pointwise_maps", "checks.check_tower_maps"]),
     dict(id="maps-bn-backward-mean-of-g", file="tower_maps.hip", old="k_m1[r] = (float)(t.bn_red[i][2 * m] / cnt);", new="k_m1[r] = (float)(t.bn_red[i][2 * m] / (cnt - 1.0));", checks=["checks.check_tower_maps"]),
     dict(id="maps-backward-prelu-ge", file="tower_maps.hip", old="const float gu = u > 0.f ? dbuf[4 * r + j] : k_alpha[r] * dbuf[4 * r + j];", new="const float gu = u >= 0.f ? dbuf[4 * r + j] : k_alpha[r] * dbuf[4 * r + j];", checks=["checks.check_tower_maps"]),
+    # ---- constant rows, channels and samples in the block statistics: each zero-std mask removed, each mean of equal values put back to sum / n;
+    #      the family's own check first (it must pass), then the degenerate case ----
+    dict(id="stats-mask-std-of-channel-stds", file="stages.hip", old="const float ac = gS > 0.f ? gall", new="const float ac = true ? gall", checks=STATS_DEGENERATE),
+    dict(id="stats-mask-channel-std", file="stages.hip", old="const float pc = cs[c] > 0.f ? ac", new="const float pc = true ? ac", checks=STATS_DEGENERATE),
+    dict(id="stats-mask-std-of-row-stds", file="stages.hip", old="const float ar = tS[t] > 0.f ? g[2 + T + t]", new="const float ar = true ? g[2 + T + t]", checks=STATS_DEGENERATE),
+    dict(id="stats-mask-row-std", file="stages.hip", old="const float pr = sct > 0.f ? ar", new="const float pr = true ? ar", checks=STATS_DEGENERATE),
+    dict(id="stats-row-mean-plain-sum", file="stages.hip", old="if (cg_stats_group_sum(ne[k], lpr) == 0.f) m[k] = f[k];", new="if (cg_stats_group_sum(ne[k], lpr) < 0.f) m[k] = f[k];", checks=STATS_DEGENERATE),
+    dict(id="stats-channel-mean-plain-sum", file="stages.hip", old="m = equal ? m0 : m / (float)T;", new="m = m / (float)T;", checks=STATS_DEGENERATE),
+    dict(id="stats-mean-over-c-plain-sum", file="stages.hip", old="const float m = equal ? f0 : s / (float)C;", new="const float m = s / (float)C;", checks=STATS_DEGENERATE),
+    dict(id="block-input-mask-std-of-channel-stds", file="block_input.hip", old="const float ac = gS > 0.f ? gall", new="const float ac = true ? gall", checks=BIN_DEGENERATE),
+    dict(id="block-input-mask-channel-std", file="block_input.hip", old="const float pc = cs[c] > 0.f ? ac", new="const float pc = true ? ac", checks=BIN_DEGENERATE),
+    dict(id="block-input-mask-std-of-row-stds", file="block_input.hip", old="const float ar = tS[k] > 0.f ? sg[2 + T + k]", new="const float ar = true ? sg[2 + T + k]", checks=BIN_DEGENERATE),
+    dict(id="block-input-mask-row-std", file="block_input.hip", old="const float pr = sct > 0.f ? ar", new="const float pr = true ? ar", checks=BIN_DEGENERATE),
+    dict(id="block-input-row-mean-plain-sum", file="block_input.hip", old="const float m = equal ? x0 : s / (float)t.V;", new="const float m = s / (float)t.V;", checks=BIN_DEGENERATE),
+    dict(id="block-input-channel-mean-plain-sum", file="block_input.hip", old="m = equal ? m0 : m / (float)T;", new="m = m / (float)T;", checks=BIN_DEGENERATE),
+    dict(id="block-input-mean-over-c-plain-sum", file="block_input.hip", old="const float m = equal ? f0 : s / (float)C;", new="const float m = s / (float)C;", checks=BIN_DEGENERATE),
 ]
